@@ -3,8 +3,12 @@
 Sersic source, ~10^6-cell octree dust grid (953 688 cells, tests/ski/cfg2.ski), monochromatic, peel-off to one
 FullInstrument 512^2 with component + statistics recording, 10^8 packets per step and GPU.
 
-  python bench.py --gpus N --steps K --warmup W [--packets P]
+  python bench.py --gpus N --steps K --warmup W [--packets P] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed -- the detector frames the engine
+filled (DIR/frames.npy) and, with a stored radiation field, its table (DIR/radiation_field.npy) -- as float64, so that two
+builds can be compared output for output on identical inputs.
 
 A "step" is one segment: every rank runs P histories of its own index range through the HIP engine and the
 detector frames of all ranks are summed onto rank 0 with ONE RCCL reduce -- the engine library's own
@@ -93,6 +97,29 @@ PMC_PASS_PACKETS = 20000000
 # what one unit of FETCH_SIZE / WRITE_SIZE stands for, calibrated on this box class with a KNOWN number of lines from beyond L2
 # (tools/fetch_calibration.sh, profiles/microbench/fetch_calibration_mi355x.txt; profiles/README.md "FETCH_SIZE calibration")
 FETCH_UNIT_BYTES = 1024.0
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 1
+
+
+def dump_outputs(outdir, arrays):
+    """writes each array as outdir/<name>.npy (flat, float64), at most DUMP_LIMIT_BYTES in all.  An array larger than its share of
+    what is left is replaced by a fixed sample of its values: the positions drawn from DUMP_SAMPLE_SEED and the array's size alone,
+    in ascending order, so that two runs with the same arguments sample the same positions."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_LIMIT_BYTES - 128 * len(arrays)   # (128 bytes: the header of a one-dimensional .npy file)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].size)
+    for i, (name, a) in enumerate(items):
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        share = left // (len(items) - i) // a.itemsize
+        note = ""
+        if a.size > share:
+            idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, a.size, share))
+            note = f" (a fixed sample of {idx.size} of its {a.size} values)"
+            a = a[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.nbytes
+        sys.stderr.write(f"[bench] wrote {os.path.join(outdir, name + '.npy')}{note}\n")
 
 
 def pmc_in_run(scene_file, passthrough):
@@ -205,7 +232,14 @@ def main():
                     help="skip the hardware-counter passes behind the timed region (one step of 2e7 packets re-run under rocprofv3 --pmc: FETCH_SIZE, "
                          "WRITE_SIZE, L2 requests / hits / misses; N = 1 only)")
     ap.add_argument("--scene-file", default=None, help="(internal: the counter passes) load the scene from this file (skh_scene_save) instead of setting it up")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in "
+                         "all: a larger array is replaced by a fixed, seeded sample of its values)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     import torch
     import torch.distributed as dist
@@ -326,9 +360,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(path, steps, warmup, save_scene_to=None):
+    def measure(path, steps, warmup, save_scene_to=None, keep_outputs=False):
         """sets the scene of ski file `path` up on this rank's GPU and times `steps` segments; returns the numbers of the
-        JSON line (rank 0) -- value, roofline inputs, counters"""
+        JSON line (rank 0) -- value, roofline inputs, counters -- and, with keep_outputs, rank 0's host copies of the arrays the
+        last timed step filled"""
         # Every rank needs a replica of the scene.  ONE rank sets it up (all host cores) and saves it as one file in /dev/shm
         # (skh_scene_save); the others load that file -- no second tree construction, no second density sampling.
         sim = None
@@ -373,7 +408,7 @@ def main():
             eng.bind_radiation_field(rf.data_ptr(), rf.numel())
         seed = sim.seed
 
-        def step(index):
+        def step(index, keep_rf=False):
             # static split of the segment's history range over the ranks (pmc_history_range); a fresh range
             # of history indices per step.  The engine runs on its own streams: torch's work on the bound tensors (zero_,
             # the previous reduce) must be complete before the segment starts.
@@ -388,7 +423,8 @@ def main():
                 eng.reduce_frames(comm.handles[0], 0)
                 if rf is not None:
                     eng.allreduce_radiation_field(comm.handles[0])
-                    rf.zero_()      # (a benchmark step is a whole segment: what follows would consume the field here)
+                    if not keep_rf:
+                        rf.zero_()  # (a benchmark step is a whole segment: what follows would consume the field here)
                 reduce_ms.append(1e3 * (time.perf_counter() - t_red))   # (includes waiting for the slowest rank's segment)
             elif world > 1:
                 # (BENCH_SHARE_DEVICE: all ranks on one device, exchange over gloo -- a flow check, RCCL refuses it)
@@ -397,7 +433,8 @@ def main():
                     frames.zero_()
                 if rf is not None:
                     dist.all_reduce(rf, op=dist.ReduceOp.SUM)
-                    rf.zero_()
+                    if not keep_rf:
+                        rf.zero_()
 
         for w in range(warmup):
             step(w)
@@ -407,13 +444,25 @@ def main():
         t0 = time.perf_counter()
         timings = []
         for k in range(steps):
-            step(warmup + k)
+            last = keep_outputs and k == steps - 1
+            if last:
+                # the bound arrays accumulate over the steps: cleared here, they hold the last step alone (step() synchronises
+                # before the segment starts)
+                frames.zero_()
+                if rf is not None:
+                    rf.zero_()
+            step(warmup + k, keep_rf=last)
             t = eng.last_timing()
             t["walk_ms"] = eng.last_kernel_ms()  # HIP events around every walk-kernel launch of the segment, summed
             t.update(eng.last_walk_timing())     # octree: the peel-off and the propagation kernels apart
             timings.append(t)
         fence()
         elapsed = time.perf_counter() - t0
+        outputs = None
+        if keep_outputs and rank == 0:
+            outputs = {"frames": frames.cpu().numpy()}
+            if rf is not None:
+                outputs["radiation_field"] = rf.cpu().numpy()
         if world > 1:
             t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -491,7 +540,8 @@ def main():
                   "breakdown": breakdown, "setup_s": setup_s, "reduce_ms": (sum(reduce_ms[warmup:]) / max(1, len(reduce_ms[warmup:]))) if reduce_ms else None,
                   "reduce_check": reduce_check, "walk_work": walk_work,
                   "packets_this_rank": history_range(total_per_step, rank, world)[1],
-                  "vnbr_mean": (grid.vnbr_start[grid.num_cells] / grid.num_cells) if args.config == 5 else None}
+                  "vnbr_mean": (grid.vnbr_start[grid.num_cells] / grid.num_cells) if args.config == 5 else None,
+                  "outputs": outputs}
         eng.close()
         del frames, rf
         return result
@@ -591,7 +641,9 @@ def main():
         fd, counter_scene = tempfile.mkstemp(prefix="pmc_scene_", suffix=".bin", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
         os.close(fd)
         os.chmod(counter_scene, 0o600)
-    main_run = measure(ski_path, args.steps, args.warmup, save_scene_to=counter_scene)
+    main_run = measure(ski_path, args.steps, args.warmup, save_scene_to=counter_scene, keep_outputs=args.dump_outputs is not None)
+    if main_run["outputs"] is not None:
+        dump_outputs(args.dump_outputs, main_run.pop("outputs"))
     counters_in_run = None
     if counter_scene:
         try:
