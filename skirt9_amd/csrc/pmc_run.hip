@@ -263,7 +263,8 @@ int pmc_run_primary(pmc_ctx* ctx, uint64_t first, uint64_t count, uint64_t seed)
     if (const char* env = pmcTune("PMC_LIST_TASKS_PER_LANE")) listTasksPerLane = std::max(1, atoi(env));
     const bool sparseLists = D.grid_kind == PMC_GRID_OCTREE && pmcTune("PMC_NO_LIVE_LISTS") == nullptr;
     {
-        const int per = ((numSlots / G) + PMC_TRANSITION_ALIGN - 1) / PMC_TRANSITION_ALIGN * PMC_TRANSITION_ALIGN;
+        // (ceil(numSlots / G): with the floor, 266 241 slots in four groups left the last slot idle -- test_gpu_slot_reuse, four-group case)
+        const int per = ((numSlots + G - 1) / G + PMC_TRANSITION_ALIGN - 1) / PMC_TRANSITION_ALIGN * PMC_TRANSITION_ALIGN;
         for (int g = 0; g < G; ++g)
         {
             base[g] = std::min(numSlots, g * per);
