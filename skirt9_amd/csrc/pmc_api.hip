@@ -94,8 +94,8 @@ void pmc_destroy(pmc_ctx* ctx)
     }
     for (void* p : ctx->allocations) hipFree(p);
     for (void* p : ctx->slotAllocations) hipFree(p);
-    for (void* p : ctx->rfAllocations) hipFree(p);
-    if (ctx->pinned) hipHostFree(ctx->pinned);
+    for (void* p : ctx->segmentAllocations) hipFree(p);
+    if (ctx->readback) hipHostFree(ctx->readback);
     for (hipEvent_t e : {ctx->evStart, ctx->evStop})
         if (e) hipEventDestroy(e);
     for (int g = 0; g < PMC_MAX_GROUPS; ++g)
@@ -162,23 +162,13 @@ int pmc_create(const pmc_scene* scene, int32_t device, pmc_ctx** out)
         pmc_destroy(ctx);
         return code;
     };
-    // (tuning aid PMC_STREAM_PRIORITY: "prop" = the group streams, which carry the propagation kernel -- the longest kernel of a generation -- and the
-    // transition side, at the highest priority and the peel-off side streams at the lowest; "peel" = the other way round)
-    int prioGroup = 0, prioPeel = 0;
-    if (const char* v = pmcTune("PMC_STREAM_PRIORITY"))
-    {
-        int least = 0, greatest = 0;
-        hipDeviceGetStreamPriorityRange(&least, &greatest);
-        const bool prop = std::strcmp(v, "prop") == 0;
-        prioGroup = prop ? greatest : least, prioPeel = prop ? least : greatest;
-    }
-    auto makeStream = [&](hipStream_t* out, int priority) { return hipStreamCreateWithPriority(out, hipStreamDefault, priority); };
-    if (makeStream(&ctx->stream, prioGroup) != hipSuccess) return bail(fail(PMC_ERR_DEVICE, "hipStreamCreate failed"));
+    auto makeStream = [&](hipStream_t* out) { return hipStreamCreateWithPriority(out, hipStreamDefault, 0); };
+    if (makeStream(&ctx->stream) != hipSuccess) return bail(fail(PMC_ERR_DEVICE, "hipStreamCreate failed"));
     ctx->groupStream[0] = ctx->stream;
     for (int g = 1; g < PMC_MAX_GROUPS; ++g)
-        if (makeStream(&ctx->groupStream[g], prioGroup) != hipSuccess) return bail(fail(PMC_ERR_DEVICE, "hipStreamCreate failed"));
+        if (makeStream(&ctx->groupStream[g]) != hipSuccess) return bail(fail(PMC_ERR_DEVICE, "hipStreamCreate failed"));
     for (int g = 0; g < PMC_MAX_GROUPS; ++g)
-        if (makeStream(&ctx->peelStream[g], prioPeel) != hipSuccess) return bail(fail(PMC_ERR_DEVICE, "hipStreamCreate failed"));
+        if (makeStream(&ctx->peelStream[g]) != hipSuccess) return bail(fail(PMC_ERR_DEVICE, "hipStreamCreate failed"));
     for (hipEvent_t* ev : {&ctx->evStart, &ctx->evStop})
         if (hipEventCreate(ev) != hipSuccess) return bail(fail(PMC_ERR_DEVICE, "hipEventCreate failed"));
     for (int g = 0; g < PMC_MAX_GROUPS; ++g)
@@ -189,7 +179,7 @@ int pmc_create(const pmc_scene* scene, int32_t device, pmc_ctx** out)
         ctx->numGroups = std::min(PMC_MAX_GROUPS, std::max(1, atoi(env)));
         ctx->groupsConfigured = true;  // (an explicit setting: also a Voronoi scene runs with it)
     }
-    if (hipHostMalloc(reinterpret_cast<void**>(&ctx->pinned), 24 * sizeof(unsigned long long)) != hipSuccess)
+    if (hipHostMalloc(reinterpret_cast<void**>(&ctx->readback), PMC_MAX_GROUPS * sizeof(GroupReadback)) != hipSuccess)
         return bail(fail(PMC_ERR_DEVICE, "hipHostMalloc failed"));
 
     DevScene& D = ctx->dev;

@@ -31,9 +31,9 @@ extern "C" int pmcWalkBlocksPerCU(int gridKind, int kind, int wide, int block, s
 extern "C" hipError_t pmcLaunchStatMerge(int slot, int blocks, hipStream_t stream);
 extern "C" int pmcPeelBlock(void);
 extern "C" int pmcPropBlock(void);
-extern "C" hipError_t pmcLaunchWalk(int slot, int gridKind, int storeRf, int taskBase, int numTaskRecords, int taskCounter, uint64_t seed, int grid,
+extern "C" hipError_t pmcLaunchWalk(int slot, int gridKind, int flavour, int taskBase, int numTaskRecords, int taskCounter, uint64_t seed, int grid,
                                     int block, size_t ldsBytes, const WalkStreamArgs* tasks, hipStream_t stream);
-extern "C" hipError_t pmcLaunchPeel(int slot, int wide, int slotBase, int numSlots, const int* list, int cursor, int obs, int sgn, int grid, size_t ldsBytes,
+extern "C" hipError_t pmcLaunchPeel(int slot, int form, int slotBase, int numSlots, const int* list, int cursor, int obs, int sgn, int grid, size_t ldsBytes,
                                     const PeelRec* sortedRec, const unsigned long long* sortedCount, unsigned long long* xcdCursor, hipStream_t stream);
 extern "C" int pmcVoroPropWavesPerSimd(void);
 extern "C" hipError_t pmcLaunchVoroProp(int slot, const int32_t* list, const unsigned long long* count, unsigned long long* xcdCursor, int segments, uint64_t seed,
@@ -41,11 +41,12 @@ extern "C" hipError_t pmcLaunchVoroProp(int slot, const int32_t* list, const uns
 extern "C" int pmcVoroPeelWavesPerSimd(void);
 extern "C" hipError_t pmcLaunchVoroPeel(int slot, int rec, int tab, const int32_t* list, const unsigned long long* count, unsigned long long* xcdCursor, int segments,
                                         int severalMedia, int grid, hipStream_t stream);
-extern "C" hipError_t pmcLaunchProp(int slot, int wide, int storeRf, int slotBase, int numSlots, const int* list, int cursor, uint64_t seed, int grid,
-                                    size_t ldsBytes, const RfLogArgs* rfLog, hipStream_t stream);
+extern "C" hipError_t pmcLaunchProp(int slot, int wide, int flavour, int checkpoints, int slotBase, int numSlots, const int* list, int cursor, uint64_t seed,
+                                    int grid, size_t ldsBytes, const RfLogArgs* rfLog, hipStream_t stream);
 extern "C" hipError_t pmcLaunchRfFlush(int slot, const uint32_t* keys, const double* vals, uint32_t* sortedKeys, double* sortedVals, unsigned long long n,
                                        int numParts, void* temp, int numCU, hipStream_t stream);
-extern "C" int pmcPeelHasQueues(int wide, size_t ldsBytes);
+extern "C" int pmcPeelHasQueues(int form, size_t ldsBytes);
+extern "C" int pmcPropHasCheckpoints(int flavour, size_t ldsBytes);
 extern "C" int pmcExperimentBuild(void);
 extern "C" const unsigned long long* pmcPeelSortedCount(void* temp);
 extern "C" size_t pmcPeelSortTempBytes();
@@ -54,7 +55,7 @@ extern "C" hipError_t pmcLaunchPeelSortCounts(int slot, int slotBase, int numSlo
 extern "C" size_t pmcRfTempBytes(int numParts);
 extern "C" int pmcRfMaxParts();
 extern "C" hipError_t pmcLaunchTransition(int slot, int slotBase, int numSlots, int group, uint64_t seed, const int* list, int listLen, int maxBlocks,
-                                          size_t ldsBytes, const StatLogArgs* statLog, uint64_t count, uint64_t keep, hipStream_t stream);
+                                          size_t ldsBytes, const StatLogArgs* statLog, uint64_t count, hipStream_t stream);
 extern "C" hipError_t pmcLaunchLaunch(int slot, int slotBase, int numSlots, int group, uint64_t first, uint64_t count, uint64_t seed, int initial,
                                       int maxBlocks, size_t ldsBytes, const StatLogArgs* statLog, hipStream_t stream);
 extern "C" hipError_t pmcLaunchStatFlush(int slot, const uint32_t* keys, const double* vals, uint32_t* sortedKeys, double* sortedVals, unsigned long long n,
@@ -88,6 +89,16 @@ namespace
         if (e_ != hipSuccess) return hipFail(e_, #call);        \
     } while (0)
 
+// what comes back to the host with a generation of a slot group (pmc_run.hip), in pinned host memory
+struct GroupReadback
+{
+    unsigned long long live;            // live slots after the generation
+    unsigned long long rfLogFill;       // entries claimed in the group's radiation-field log
+    unsigned long long statLogFill;     // entries claimed in the group's statistics log
+    unsigned long long historyCursor;   // the segment's history cursor (progress reports)
+    unsigned long long statFreeBlocks;  // free blocks of the group's share of the statistics pool
+};
+
 struct pmc_ctx
 {
     int device{0};
@@ -119,7 +130,7 @@ struct pmc_ctx
     int numCU{256};
     int64_t numSlots{0};         // requested pool size
     int64_t allocatedSlots{0};   // size of the allocated slot arrays
-    unsigned long long* pinned{nullptr};
+    GroupReadback* readback{nullptr};  // [PMC_MAX_GROUPS]
     unsigned long long internalErrorsSeen{0};
     pmc_progress_fn progress{nullptr};    // pmc_set_progress
     void* progressUser{nullptr};
@@ -131,9 +142,10 @@ struct pmc_ctx
     int32_t* statPoolIota{nullptr};       // 0, 1, 2, ...: the free list of a statistics pool none of whose blocks is in use
     int64_t statPoolBlocks{0};
     int statPoolGrowths{0};               // times the pool has grown (pmc_run_primary)
+    // every buffer that pmc_run_primary provisions per segment (sort buffers, logs, cursors): kept from one segment to the next, grown when needed
+    std::vector<void*> segmentAllocations;
     // radiation field on an octree: per slot group the log of a generation's contributions (two buffers each for the
     // partitioning sort) and the sort's temporary storage
-    std::vector<void*> rfAllocations;
     uint32_t* rfKeys[PMC_MAX_GROUPS][2]{};
     double* rfVals[PMC_MAX_GROUPS][2]{};
     unsigned long long rfCap[PMC_MAX_GROUPS]{};
@@ -198,6 +210,16 @@ struct pmc_ctx
         }
         *out = static_cast<T*>(d);
         return PMC_OK;
+    }
+    // frees a buffer of `owner` (as in allocate) and forgets it
+    template<typename T> void release(T*& p, std::vector<void*>* owner = nullptr)
+    {
+        if (!p) return;
+        void* d = const_cast<void*>(static_cast<const void*>(p));
+        std::vector<void*>& own = owner ? *owner : allocations;
+        own.erase(std::remove(own.begin(), own.end(), d), own.end());
+        hipFree(d);
+        p = nullptr;
     }
 };
 

@@ -66,7 +66,9 @@
 #include <math.h>
 #include <algorithm>
 #include <mutex>
+#include <array>
 #include <type_traits>
+#include <utility>
 
 #ifndef PMC_WALK_REFILL
     #define PMC_WALK_REFILL 40  // waiting (idle or pending) lanes in a wave that trigger a service round (a round costs
@@ -279,24 +281,73 @@ extern "C" hipError_t pmcUploadScene(int slot, const DevScene* scene, hipStream_
                                   hipMemcpyHostToDevice, stream);
 }
 
-// the dynamic-LDS limit is a property of the kernel, not of a context: it is only ever raised (a small scene created
-// after a large one must not lower the limit under the live context)
 // LDS bytes of the task queues of one peel-off workgroup (walkPeelKernel2)
 static size_t pmcPeelQueueBytes()
 {
     return size_t(PMC_PEEL_BLOCK / 64) * PEEL_QBYTES;
 }
-// the peel-off kernel with task queues: one instantiation per sign octant of the observer's direction (bit a of sgn: k_a < 0)
-typedef void (*PeelKernel2)(int, int, int, int, int, int, const int*, PeelSortedArgs);
-static PeelKernel2 peelKernel2For(int wide, int sgn)
+
+// ---- the instantiations of every walk kernel family, each listed once: entry f of a family's table is the kernel of flavour f and the
+// dynamic LDS it may be launched with beyond the grid tables (pmcConfigureKernels: min(walkLds + extraLds, 160 KiB))
+template<typename Kernel> struct KernelFlavour
 {
-    static const PeelKernel2 narrow[8] = {walkPeelKernel2<false, 0>, walkPeelKernel2<false, 1>, walkPeelKernel2<false, 2>, walkPeelKernel2<false, 3>,
-                                          walkPeelKernel2<false, 4>, walkPeelKernel2<false, 5>, walkPeelKernel2<false, 6>, walkPeelKernel2<false, 7>};
-    static const PeelKernel2 wider[8] = {walkPeelKernel2<true, 0>, walkPeelKernel2<true, 1>, walkPeelKernel2<true, 2>, walkPeelKernel2<true, 3>,
-                                         walkPeelKernel2<true, 4>, walkPeelKernel2<true, 5>, walkPeelKernel2<true, 6>, walkPeelKernel2<true, 7>};
-    return wide ? wider[sgn & 7] : narrow[sgn & 7];
+    Kernel kernel;
+    size_t extraLds;
+};
+// entry f = make(f) for f = 0 .. N - 1 (f as a compile-time constant: decltype(f)::value)
+template<typename Make, int... F> static auto expandFlavours(Make make, std::integer_sequence<int, F...>)
+{
+    return std::array<decltype(make(std::integral_constant<int, 0>())), sizeof...(F)>{{make(std::integral_constant<int, F>())...}};
+}
+template<int N, typename Make> static auto flavourTable(Make make) { return expandFlavours(make, std::make_integer_sequence<int, N>()); }
+// walk flavour (pmcLaunchWalk, pmcLaunchProp, pmcLaunchVoroProp): bit 0 the radiation field is stored, bit 1 explicit absorption, bit 2 several
+// medium components -- separate instantiations, so that the plain photon loop pays nothing for them
+// (only the propagation kernel without explicit absorption and several media keeps pass-1 checkpoints next to the grid tables)
+static bool flavourHasCheckpointRoom(int flavour) { return (flavour & 6) == 0; }
+// octree propagation: flavour | 8 for a wide octree
+typedef void (*PropKernel)(int, int, int, int, uint64_t, int, RfLogArgs, const int*);
+static const auto propKernels = flavourTable<16>([](auto f) {
+    constexpr int F = decltype(f)::value;
+    return KernelFlavour<PropKernel>{walkPropKernel<(F & 8) != 0, (F & 1) != 0, (F & 2) != 0, (F & 4) != 0>, flavourHasCheckpointRoom(F) ? size_t(16 + PROP_CKPT_BYTES) : 0};
+});
+// generic walks (Cartesian, Voronoi): flavour | 8 on a Voronoi grid
+typedef void (*WalkKernel)(int, int, int, int, uint64_t, WalkStreamArgs);
+static const auto walkKernels = flavourTable<16>([](auto f) {
+    constexpr int F = decltype(f)::value;
+    return KernelFlavour<WalkKernel>{walkKernel<(F & 8) ? GRID_VORO : GRID_CART, (F & 1) != 0, (F & 2) != 0, (F & 4) != 0>, 0};
+});
+// Voronoi propagation on the table of runs: static LDS only (launched without dynamic LDS; its limit is never raised)
+typedef void (*VoroPropKernel)(int, const int32_t*, const unsigned long long*, unsigned long long*, int, uint64_t);
+static const auto voroPropKernels = flavourTable<8>([](auto f) {
+    constexpr int F = decltype(f)::value;
+    return VoroPropKernel(voroPropKernel<(F & 1) != 0, (F & 2) != 0, (F & 4) != 0>);
+});
+// octree peel-off with service rounds: form & 3 (bit 0 wide, bit 1 several medium components)
+typedef void (*PeelKernel)(int, int, int, int, int, const int*);
+static const auto peelKernels = flavourTable<4>([](auto f) {
+    constexpr int F = decltype(f)::value;
+    return KernelFlavour<PeelKernel>{walkPeelKernel<(F & 1) != 0, (F & 2) != 0>, 0};
+});
+// octree peel-off with task queues: one instantiation per sign octant of the observer's direction (bit a of sgn: k_a < 0); sgn | 8 when wide
+typedef void (*PeelKernel2)(int, int, int, int, int, int, const int*, PeelSortedArgs);
+static const auto peel2Kernels = flavourTable<16>([](auto f) {
+    constexpr int F = decltype(f)::value;
+    return KernelFlavour<PeelKernel2>{walkPeelKernel2<(F & 8) != 0, F & 7>, 16 + pmcPeelQueueBytes()};
+});
+
+template<typename Table> static hipError_t raiseLdsLimits(const Table& table, size_t walkMax)
+{
+    for (const auto& k : table)
+    {
+        const size_t lds = k.extraLds ? std::min(walkMax + k.extraLds, size_t(160) * 1024) : walkMax;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
+// the dynamic-LDS limit is a property of the kernel, not of a context: it is only ever raised (a small scene created
+// after a large one must not lower the limit under the live context)
 extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
 {
     // (contexts are created concurrently by one host thread per device; the attribute is per device, so every pmc_create
@@ -319,94 +370,62 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
                                 (int)(5 * sizeof(double) << PMC_STAT_BUCKET_BITS));
         if (e != hipSuccess) return e;
     }
+    for (hipError_t e : {raiseLdsLimits(peelKernels, walkMax), raiseLdsLimits(peel2Kernels, walkMax), raiseLdsLimits(propKernels, walkMax),
+                         raiseLdsLimits(walkKernels, walkMax)})
+        if (e != hipSuccess) return e;
     const struct
     {
         const void* kernel;
         size_t lds;
-    } all[] = {{reinterpret_cast<const void*>(&walkPeelKernel<false, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkPeelKernel<true, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkPeelKernel<false, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkPeelKernel<true, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<false, false, false, false>), std::min(walkMax + 16 + PROP_CKPT_BYTES, size_t(160) * 1024)},
-               {reinterpret_cast<const void*>(&walkPropKernel<false, true, false, false>), std::min(walkMax + 16 + PROP_CKPT_BYTES, size_t(160) * 1024)},
-               {reinterpret_cast<const void*>(&walkPropKernel<true, false, false, false>), std::min(walkMax + 16 + PROP_CKPT_BYTES, size_t(160) * 1024)},
-               {reinterpret_cast<const void*>(&walkPropKernel<true, true, false, false>), std::min(walkMax + 16 + PROP_CKPT_BYTES, size_t(160) * 1024)},
-               {reinterpret_cast<const void*>(&walkPropKernel<false, false, true, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<false, true, true, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<true, false, true, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<true, true, true, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<false, false, false, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<false, false, true, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<false, true, false, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<false, true, true, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<true, false, false, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<true, false, true, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<true, true, false, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkPropKernel<true, true, true, true>), walkMax},
-               {reinterpret_cast<const void*>(&traceTreeKernel<false, false>), walkMax},
+    } all[] = {{reinterpret_cast<const void*>(&traceTreeKernel<false, false>), walkMax},
                {reinterpret_cast<const void*>(&traceTreeKernel<false, true>), walkMax},
                {reinterpret_cast<const void*>(&traceTreeKernel<true, false>), walkMax},
                {reinterpret_cast<const void*>(&traceTreeKernel<true, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_CART, false, false, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_CART, true, false, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_CART, false, true, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_CART, true, true, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_CART, false, false, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_CART, false, true, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_CART, true, false, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_CART, true, true, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_VORO, false, false, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_VORO, false, true, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_VORO, true, false, true>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_VORO, true, true, true>), walkMax},
                {reinterpret_cast<const void*>(&traceRayKernel<GRID_CART>), walkMax},
+               {reinterpret_cast<const void*>(&traceRayKernel<GRID_VORO>), walkMax},
                {reinterpret_cast<const void*>(&transitionKernel), transitionMax},
                {reinterpret_cast<const void*>(&launchKernel), transitionMax},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_TREE>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_CART>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
-               {reinterpret_cast<const void*>(&cycleStartKernel<GRID_VORO>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_VORO, false, false, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_VORO, true, false, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_VORO, false, true, false>), walkMax},
-               {reinterpret_cast<const void*>(&walkKernel<GRID_VORO, true, true, false>), walkMax},
-               {reinterpret_cast<const void*>(&traceRayKernel<GRID_VORO>), walkMax}};
+               {reinterpret_cast<const void*>(&cycleStartKernel<GRID_VORO>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)}};
     for (const auto& k : all)
     {
         hipError_t e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
         if (e != hipSuccess) return e;
     }
-    for (int wide = 0; wide < 2; ++wide)
-        for (int sgn = 0; sgn < 8; ++sgn)
-        {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(peelKernel2For(wide, sgn)), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)std::min(walkMax + 16 + pmcPeelQueueBytes(), size_t(160) * 1024));
-            if (e != hipSuccess) return e;
-        }
     return hipSuccess;
+}
+
+// does the octree propagation kernel of this walk flavour keep its pass-1 checkpoints in LDS, behind the grid tables of ldsBytes?
+extern "C" int pmcPropHasCheckpoints(int flavour, size_t ldsBytes)
+{
+    // (tuning aid PMC_PROP_NO_CHECKPOINTS: pass 2 walks every path from its start)
+    return flavourHasCheckpointRoom(flavour) && !pmcTune("PMC_PROP_NO_CHECKPOINTS") && ((ldsBytes + 15) & ~size_t(15)) + PROP_CKPT_BYTES <= size_t(160) * 1024;
+}
+// does the peel-off kernel of this octree run with task queues (the form that can take sorted records)?  form: bit 0 wide, bit 1 several medium
+// components (the form with service rounds); an octree of 12 levels leaves no room for the queues next to its coordinate table
+extern "C" int pmcPeelHasQueues(int form, size_t ldsBytes)
+{
+    return (form & 2) == 0 && ((ldsBytes + 15) & ~size_t(15)) + pmcPeelQueueBytes() <= size_t(160) * 1024;
 }
 
 // resident workgroups per CU of a walk kernel: kind 0 = generic (Cartesian / Voronoi), 1 = octree peel-off, 2 = octree
 // propagation
 extern "C" int pmcWalkBlocksPerCU(int gridKind, int kind, int wide, int block, size_t ldsBytes)
 {
-    int n = 0;
-    hipError_t e;
+    const void* kernel;
     if (gridKind == PMC_GRID_OCTREE && kind == 1)
-        e = wide ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(&walkPeelKernel<true, false>), block, ldsBytes)
-                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(&walkPeelKernel<false, false>), block, ldsBytes);
+        kernel = reinterpret_cast<const void*>(peelKernels[wide ? 1 : 0].kernel);
     else if (gridKind == PMC_GRID_OCTREE)
     {
         // (with the pass-1 checkpoints of pmcLaunchProp)
-        const size_t trimOffset = (ldsBytes + 15) & ~size_t(15);
-        if (!pmcTune("PMC_PROP_NO_CHECKPOINTS") && trimOffset + PROP_CKPT_BYTES <= size_t(160) * 1024) ldsBytes = trimOffset + PROP_CKPT_BYTES;
-        e = wide ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(&walkPropKernel<true, false, false, false>), block, ldsBytes)
-                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(&walkPropKernel<false, false, false, false>), block, ldsBytes);
+        if (pmcPropHasCheckpoints(0, ldsBytes)) ldsBytes = ((ldsBytes + 15) & ~size_t(15)) + PROP_CKPT_BYTES;
+        kernel = reinterpret_cast<const void*>(propKernels[wide ? 8 : 0].kernel);
     }
-    else if (gridKind == PMC_GRID_VORONOI)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(&walkKernel<GRID_VORO, false, false, false>), block, ldsBytes);
     else
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(&walkKernel<GRID_CART, false, false, false>), block, ldsBytes);
-    return e == hipSuccess ? n : 0;
+        kernel = reinterpret_cast<const void*>(walkKernels[gridKind == PMC_GRID_VORONOI ? 8 : 0].kernel);
+    int n = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, block, ldsBytes) == hipSuccess ? n : 0;
 }
 
 extern "C" int pmcPeelBlock(void)
@@ -420,25 +439,14 @@ extern "C" int pmcPropBlock(void)
 
 
 // walks of the task records [taskBase, taskBase + numTaskRecords) of one slot group on a Cartesian or Voronoi grid;
-// taskCounter = index of the group's (zeroed) cursor
-extern "C" hipError_t pmcLaunchWalk(int slot, int gridKind, int storeRf, int taskBase, int numTaskRecords, int taskCounter,
+// taskCounter = index of the group's (zeroed) cursor; flavour: the walk flavour (above)
+extern "C" hipError_t pmcLaunchWalk(int slot, int gridKind, int flavour, int taskBase, int numTaskRecords, int taskCounter,
                                     uint64_t seed, int grid, int block, size_t ldsBytes, const WalkStreamArgs* tasks, hipStream_t stream)
 {
     WalkStreamArgs ws;
     std::memset(&ws, 0, sizeof(ws));
     if (tasks) ws = *tasks;
-    // (the radiation-field and the explicit-absorption flavours are separate instantiations: the plain photon loop pays nothing for
-    // them; storeRf: bit 0 = the radiation field is stored, bit 1 = explicit absorption)
-    // (bit 2 = several medium components)
-    const int flavour = storeRf & 7;
-    typedef void (*Kernel)(int, int, int, int, uint64_t, WalkStreamArgs);
-    static const Kernel cart[8] = {walkKernel<GRID_CART, false, false, false>, walkKernel<GRID_CART, true, false, false>, walkKernel<GRID_CART, false, true, false>,
-                                   walkKernel<GRID_CART, true, true, false>,   walkKernel<GRID_CART, false, false, true>, walkKernel<GRID_CART, true, false, true>,
-                                   walkKernel<GRID_CART, false, true, true>,   walkKernel<GRID_CART, true, true, true>};
-    static const Kernel voro[8] = {walkKernel<GRID_VORO, false, false, false>, walkKernel<GRID_VORO, true, false, false>, walkKernel<GRID_VORO, false, true, false>,
-                                   walkKernel<GRID_VORO, true, true, false>,   walkKernel<GRID_VORO, false, false, true>, walkKernel<GRID_VORO, true, false, true>,
-                                   walkKernel<GRID_VORO, false, true, true>,   walkKernel<GRID_VORO, true, true, true>};
-    const Kernel kernel = gridKind == PMC_GRID_VORONOI ? voro[flavour] : cart[flavour];
+    const WalkKernel kernel = walkKernels[(flavour & 7) | (gridKind == PMC_GRID_VORONOI ? 8 : 0)].kernel;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), ldsBytes, stream, slot, taskBase, numTaskRecords, taskCounter, seed, ws);
     return hipGetLastError();
 }
@@ -449,43 +457,21 @@ extern "C" int pmcVoroPeelWavesPerSimd(void) { return PMC_VPEEL_MIN_WAVES; }
 extern "C" hipError_t pmcLaunchVoroPeel(int slot, int rec, int tab, const int32_t* list, const unsigned long long* count, unsigned long long* xcdCursor, int segments,
                                         int severalMedia, int grid, hipStream_t stream)
 {
-    if (severalMedia)
-        hipLaunchKernelGGL(voroPeelKernel<true>, dim3(grid), dim3(256), 0, stream, slot, rec, tab, list, count, xcdCursor, segments);
-    else
-        hipLaunchKernelGGL(voroPeelKernel<false>, dim3(grid), dim3(256), 0, stream, slot, rec, tab, list, count, xcdCursor, segments);
+    hipLaunchKernelGGL(severalMedia ? voroPeelKernel<true> : voroPeelKernel<false>, dim3(grid), dim3(256), 0, stream, slot, rec, tab, list, count, xcdCursor,
+                       segments);
     return hipGetLastError();
 }
 
 // Voronoi: the propagation walks (task record 0) of the slots in `list` on the table of runs DevScene::vgen_run
 extern "C" int pmcVoroPropWavesPerSimd(void) { return PMC_VPROP_MIN_WAVES; }
-// flavour: bit 0 radiation field, bit 1 explicit absorption, bit 2 several medium components
+// flavour: the walk flavour (above)
 extern "C" hipError_t pmcLaunchVoroProp(int slot, const int32_t* list, const unsigned long long* count, unsigned long long* xcdCursor, int segments, uint64_t seed,
                                         int flavour, int grid, hipStream_t stream)
 {
-#define PMC_VPROP_CASE(f, RF, EA, MM) \
-    case f: hipLaunchKernelGGL((voroPropKernel<RF, EA, MM>), dim3(grid), dim3(256), 0, stream, slot, list, count, xcdCursor, segments, seed); break;
-    switch (flavour & 7)
-    {
-        PMC_VPROP_CASE(0, false, false, false)
-        PMC_VPROP_CASE(1, true, false, false)
-        PMC_VPROP_CASE(2, false, true, false)
-        PMC_VPROP_CASE(3, true, true, false)
-        PMC_VPROP_CASE(4, false, false, true)
-        PMC_VPROP_CASE(5, true, false, true)
-        PMC_VPROP_CASE(6, false, true, true)
-        PMC_VPROP_CASE(7, true, true, true)
-    }
-#undef PMC_VPROP_CASE
+    hipLaunchKernelGGL(voroPropKernels[flavour & 7], dim3(grid), dim3(256), 0, stream, slot, list, count, xcdCursor, segments, seed);
     return hipGetLastError();
 }
 
-// octree: the peel-off walks towards observer `obs` of the slots [slotBase, slotBase + numSlots)
-// does the peel-off kernel of this octree run with task queues (the form that can take sorted records)?
-extern "C" int pmcPeelHasQueues(int wide, size_t ldsBytes)
-{
-    const bool first = pmcTune("PMC_PEEL_V1") != nullptr;
-    return !first && (wide & 2) == 0 && ((ldsBytes + 15) & ~size_t(15)) + pmcPeelQueueBytes() <= size_t(160) * 1024;
-}
 // sorted peel-off records (pmc_device.h PeelRec): the count pass of the sort over the slots of a group, behind its transition / launch kernels; the
 // cycle start kernel, launched with the SAME number of workgroups (returned through `groups`), is the scatter pass.  temp: pmcPeelSortTempBytes();
 // the number of sorted records is left at pmcPeelSortedCount(temp)
@@ -523,54 +509,35 @@ extern "C" hipError_t pmcLaunchPeelSortCounts(int slot, int slotBase, int numSlo
     return hipGetLastError();
 }
 
-extern "C" hipError_t pmcLaunchPeel(int slot, int wide, int slotBase, int numSlots, const int* list, int cursor, int obs, int sgn, int grid, size_t ldsBytes,
+// octree: the peel-off walks towards observer `obs` of the slots [slotBase, slotBase + numSlots); form: bit 0 wide, bit 1 several medium
+// components, bit 2 task queues (pmcPeelHasQueues)
+extern "C" hipError_t pmcLaunchPeel(int slot, int form, int slotBase, int numSlots, const int* list, int cursor, int obs, int sgn, int grid, size_t ldsBytes,
                                     const PeelRec* sortedRec, const unsigned long long* sortedCount, unsigned long long* xcdCursor, hipStream_t stream)
 {
-    const bool first = pmcTune("PMC_PEEL_V1") != nullptr;  // (tuning aid: the form with service rounds)
-    // (`wide` bit 1: several medium components -- the form with service rounds)
-    const bool mm = (wide & 2) != 0;
-    wide &= 1;
-    // (an octree of 12 levels leaves no room for the task queues next to its coordinate table: service rounds)
-    if (first || mm || ((ldsBytes + 15) & ~size_t(15)) + pmcPeelQueueBytes() > size_t(160) * 1024)
-    {
-        auto kernel = mm ? (wide ? walkPeelKernel<true, true> : walkPeelKernel<false, true>) : (wide ? walkPeelKernel<true, false> : walkPeelKernel<false, false>);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(PMC_PEEL_BLOCK), ldsBytes, stream, slot, slotBase, numSlots, cursor, obs, list);
-    }
+    if (!(form & 4))
+        hipLaunchKernelGGL(peelKernels[form & 3].kernel, dim3(grid), dim3(PMC_PEEL_BLOCK), ldsBytes, stream, slot, slotBase, numSlots, cursor, obs, list);
     else
     {
         // (the waves' task queues follow the grid tables in LDS)
         // (sgn: the sign octant of the observer's direction, DevInstrument::sgn)
-        const PeelKernel2 kernel = peelKernel2For(wide, sgn);
         const size_t queueOffset = (ldsBytes + 15) & ~size_t(15);
         const PeelSortedArgs sorted = {sortedRec, sortedCount, xcdCursor};
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(PMC_PEEL_BLOCK), queueOffset + pmcPeelQueueBytes(), stream, slot, slotBase, numSlots, cursor, obs,
-                           (int)queueOffset, list, sorted);
+        hipLaunchKernelGGL(peel2Kernels[(form & 1) * 8 + (sgn & 7)].kernel, dim3(grid), dim3(PMC_PEEL_BLOCK), queueOffset + pmcPeelQueueBytes(), stream, slot,
+                           slotBase, numSlots, cursor, obs, (int)queueOffset, list, sorted);
     }
     return hipGetLastError();
 }
 
-// octree: the propagation walks of the slots [slotBase, slotBase + numSlots)
-extern "C" hipError_t pmcLaunchProp(int slot, int wide, int storeRf, int slotBase, int numSlots, const int* list, int cursor, uint64_t seed, int grid,
-                                    size_t ldsBytes, const RfLogArgs* rfLog, hipStream_t stream)
+// octree: the propagation walks of the slots [slotBase, slotBase + numSlots); checkpoints: pmcPropHasCheckpoints (the pass-1 checkpoints follow
+// the grid tables in LDS)
+extern "C" hipError_t pmcLaunchProp(int slot, int wide, int flavour, int checkpoints, int slotBase, int numSlots, const int* list, int cursor, uint64_t seed,
+                                    int grid, size_t ldsBytes, const RfLogArgs* rfLog, hipStream_t stream)
 {
-    // (storeRf: bit 0 = the radiation field is stored, bit 1 = explicit absorption)
-    // (bit 2 = several medium components)
-    const bool ea = (storeRf & 2) != 0, mm = (storeRf & 4) != 0;
-    typedef void (*Kernel)(int, int, int, int, uint64_t, int, RfLogArgs, const int*);
-    static const Kernel narrow[8] = {walkPropKernel<false, false, false, false>, walkPropKernel<false, true, false, false>, walkPropKernel<false, false, true, false>,
-                                     walkPropKernel<false, true, true, false>,   walkPropKernel<false, false, false, true>, walkPropKernel<false, true, false, true>,
-                                     walkPropKernel<false, false, true, true>,   walkPropKernel<false, true, true, true>};
-    static const Kernel wider[8] = {walkPropKernel<true, false, false, false>, walkPropKernel<true, true, false, false>, walkPropKernel<true, false, true, false>,
-                                    walkPropKernel<true, true, true, false>,   walkPropKernel<true, false, false, true>, walkPropKernel<true, true, false, true>,
-                                    walkPropKernel<true, false, true, true>,   walkPropKernel<true, true, true, true>};
-    const Kernel kernel = wide ? wider[storeRf & 7] : narrow[storeRf & 7];
-    // (the pass-1 checkpoints follow the grid tables in LDS, if there is room)
-    const bool noTrim = pmcTune("PMC_PROP_NO_CHECKPOINTS") != nullptr;  // (tuning aid: pass 2 walks every path from its start)
+    const PropKernel kernel = propKernels[(flavour & 7) | (wide ? 8 : 0)].kernel;
     const size_t trimOffset = (ldsBytes + 15) & ~size_t(15);
-    const bool trim = !noTrim && !ea && !mm && trimOffset + PROP_CKPT_BYTES <= size_t(160) * 1024;
     RfLogArgs none = {nullptr, nullptr, 0ull, 0, 0u};
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(PMC_PROP_BLOCK), trim ? trimOffset + PROP_CKPT_BYTES : ldsBytes, stream, slot, slotBase, numSlots, cursor,
-                       seed, trim ? (int)trimOffset : -1, rfLog ? *rfLog : none, list);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(PMC_PROP_BLOCK), checkpoints ? trimOffset + PROP_CKPT_BYTES : ldsBytes, stream, slot, slotBase, numSlots, cursor,
+                       seed, checkpoints ? (int)trimOffset : -1, rfLog ? *rfLog : none, list);
     return hipGetLastError();
 }
 
@@ -633,7 +600,7 @@ extern "C" hipError_t pmcLaunchStatMerge(int slot, int blocks, hipStream_t strea
 // transitions of the slots [slotBase, slotBase + numSlots) of slot group `group`, followed by the scan of the group's
 // ended-history counts (the launch kernel's history indices)
 extern "C" hipError_t pmcLaunchTransition(int slot, int slotBase, int numSlots, int group, uint64_t seed, const int* list, int listLen, int maxBlocks,
-                                          size_t ldsBytes, const StatLogArgs* statLog, uint64_t count, uint64_t keep, hipStream_t stream)
+                                          size_t ldsBytes, const StatLogArgs* statLog, uint64_t count, hipStream_t stream)
 {
     const StatLogArgs none = {nullptr, nullptr, 0ull, 0, nullptr, nullptr, nullptr};
     const int block = PMC_TRANSITION_BLOCK;
@@ -642,8 +609,7 @@ extern "C" hipError_t pmcLaunchTransition(int slot, int slotBase, int numSlots, 
     hipLaunchKernelGGL(transitionKernel, dim3(grid), dim3(block), ldsBytes, stream, slot, slotBase, numSlots, group, seed, list, listLen, statLog ? *statLog : none);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || list) return e;  // (a sparse generation retires its ended histories in the transition kernel)
-    hipLaunchKernelGGL(endedScanKernel, dim3(1), dim3(PMC_SCAN_THREADS), 0, stream, slot, slotBase, numSlots, group, (unsigned long long)count,
-                       (unsigned long long)keep);
+    hipLaunchKernelGGL(endedScanKernel, dim3(1), dim3(PMC_SCAN_THREADS), 0, stream, slot, slotBase, numSlots, group, (unsigned long long)count);
     return hipGetLastError();
 }
 
@@ -671,12 +637,8 @@ extern "C" hipError_t pmcLaunchCycleStart(int slot, int gridKind, int slotBase, 
         ldsBytes = size_t(ps.ldsOffset) + size_t(ps.numObs + (ps.propIndex >= 0 ? 1 : 0)) * PEEL_SORT_PARTS * sizeof(uint32_t);
     }
     const int grid = std::max(1, std::min(((listIn ? listLen : numSlots) + 255) / 256, maxBlocks));
-    if (gridKind == PMC_GRID_OCTREE)
-        hipLaunchKernelGGL(cycleStartKernel<GRID_TREE>, dim3(grid), dim3(256), ldsBytes, stream, slot, slotBase, numSlots, listCounter, listOut, listIn, listLen, ps);
-    else if (gridKind == PMC_GRID_VORONOI)
-        hipLaunchKernelGGL(cycleStartKernel<GRID_VORO>, dim3(grid), dim3(256), ldsBytes, stream, slot, slotBase, numSlots, listCounter, listOut, listIn, listLen, ps);
-    else
-        hipLaunchKernelGGL(cycleStartKernel<GRID_CART>, dim3(grid), dim3(256), ldsBytes, stream, slot, slotBase, numSlots, listCounter, listOut, listIn, listLen, ps);
+    const auto kernel = gridKind == PMC_GRID_OCTREE ? cycleStartKernel<GRID_TREE> : gridKind == PMC_GRID_VORONOI ? cycleStartKernel<GRID_VORO> : cycleStartKernel<GRID_CART>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), ldsBytes, stream, slot, slotBase, numSlots, listCounter, listOut, listIn, listLen, ps);
     return hipGetLastError();
 }
 
@@ -693,11 +655,8 @@ extern "C" hipError_t pmcLaunchTrace(int slot, int gridKind, int wide, int unifo
                            : (uniform ? traceTreeKernel<false, true> : traceTreeKernel<false, false>);
         hipLaunchKernelGGL(kernel, dim3(1), dim3(64), ldsBytes, stream, slot, r[0], r[1], r[2], k[0], k[1], k[2], kdev, m, ds, cap, n);
     }
-    else if (gridKind == PMC_GRID_VORONOI)
-        hipLaunchKernelGGL(traceRayKernel<GRID_VORO>, dim3(1), dim3(64), ldsBytes, stream, slot, r[0], r[1], r[2], k[0], k[1],
-                           k[2], m, ds, cap, n);
     else
-        hipLaunchKernelGGL(traceRayKernel<GRID_CART>, dim3(1), dim3(64), ldsBytes, stream, slot, r[0], r[1], r[2], k[0], k[1],
-                           k[2], m, ds, cap, n);
+        hipLaunchKernelGGL(gridKind == PMC_GRID_VORONOI ? traceRayKernel<GRID_VORO> : traceRayKernel<GRID_CART>, dim3(1), dim3(64), ldsBytes, stream, slot, r[0],
+                           r[1], r[2], k[0], k[1], k[2], m, ds, cap, n);
     return hipGetLastError();
 }

@@ -1581,12 +1581,9 @@
     //  of another slot group, which a workgroup of 1024 lanes does not -- it then waits for a free CU, 1.3 ms on average with the groups
     //  overlapped, profiles/r05_v3_kernel_stats.csv); the group has at most 2^30 / 64 tiles.
     // ================================================================================================
-    //  Staggered end of a segment (round 6): a group only takes histories as long as more than `keep` of the segment's `count` are left
-    //  for the groups before it (keep = 0 for group 0), so the groups run empty ONE AFTER THE OTHER while the others still work at full
-    //  occupancy, instead of all draining together with the chip half idle (the last 100 ms of a 475 ms segment of 1e8 packets ran at 66 % of
-    //  the full-pool rate: profiles/sweeps/r06_a1_generation_dump.txt).  What a group may take this generation: [HBASE, HLIMIT).
+    //  What a group may take this generation: [HBASE, HLIMIT), HLIMIT = `count`.
     __global__ __launch_bounds__(PMC_SCAN_THREADS) void endedScanKernel(const int sceneSlot, const int slotBase, const int numSlots, const int group,
-                                                                        const unsigned long long count, const unsigned long long keep)
+                                                                        const unsigned long long count)
     {
         const DevScene& S = c_scene[sceneSlot];
         __shared__ unsigned int part[PMC_SCAN_THREADS];
@@ -1614,30 +1611,9 @@
         if (tid == PMC_SCAN_THREADS - 1)
         {
             const unsigned long long ended = (unsigned long long)part[PMC_SCAN_THREADS - 1];
-            unsigned long long base;
-            if (keep == 0ull)
-                base = atomicAdd(S.counters + PMC_CTR_HISTORY, ended);  // (the cursor may run past `count`: the launch kernel stops at it)
-            else
-            {
-                // (one lane per group and generation: a compare-and-swap loop among at most PMC_MAX_GROUPS contenders)
-                const unsigned long long limit = count > keep ? count - keep : 0ull;
-                // (the cursor's value by a compare-and-swap that changes nothing: a plain or atomic LOAD may be served by this XCD's L2)
-                unsigned long long seen = atomicCAS(S.counters + PMC_CTR_HISTORY, ~0ull, ~0ull);
-                while (true)
-                {
-                    const unsigned long long take = seen < limit ? min(ended, limit - seen) : 0ull;
-                    const unsigned long long was = atomicCAS(S.counters + PMC_CTR_HISTORY, seen, seen + take);
-                    if (was == seen)
-                    {
-                        base = seen;
-                        S.counters[PMC_CTR_HLIMIT(group)] = seen + take;
-                        break;
-                    }
-                    seen = was;
-                }
-            }
-            S.counters[PMC_CTR_HBASE(group)] = base;
-            if (keep == 0ull) S.counters[PMC_CTR_HLIMIT(group)] = count;
+            // (the cursor may run past `count`: the launch kernel stops at it)
+            S.counters[PMC_CTR_HBASE(group)] = atomicAdd(S.counters + PMC_CTR_HISTORY, ended);
+            S.counters[PMC_CTR_HLIMIT(group)] = count;
         }
         for (int i = lo; i < hi; i += 4)
         {

@@ -50,6 +50,17 @@ def test_the_library_reads_three_environment_settings_only():
     assert names == {"PMC_NUM_SLOTS", "PMC_NUM_GROUPS", "PMC_STAT_POOL_BLOCKS"}
 
 
+def test_tuning_header_lists_exactly_the_switches_the_library_reads():
+    """include/pmc_tuning.h names every switch passed to pmcTune under skirt9_amd/csrc/, and no other"""
+    csrc = os.path.join(ROOT, "skirt9_amd", "csrc")
+    read = set()
+    for f in os.listdir(csrc):
+        read |= set(re.findall(r'pmcTune\("([A-Z_0-9]+)"\)', open(os.path.join(csrc, f)).read()))
+    header = open(os.path.join(ROOT, "include", "pmc_tuning.h")).read()
+    table = header[header.index("A process-wide table of named switches"):header.index("value == NULL removes the switch")]
+    assert set(re.findall(r"\bPMC_[A-Z_0-9]+\b", table)) == read
+
+
 def test_tuning_switch_table(libpmc):
     from skirt9_amd import engine
     engine.set_tuning("PMC_NO_LIVE_LISTS", "1")
