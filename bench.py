@@ -3,8 +3,14 @@
 Sersic source, ~10^6-cell octree dust grid (953 688 cells, tests/ski/cfg2.ski), monochromatic, peel-off to one
 FullInstrument 512^2 with component + statistics recording, 10^8 packets per step and GPU.
 
-  python bench.py --gpus N --steps K --warmup W [--packets P] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--packets P] [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does what the headline figure needs and nothing more: it sets the scene up, warms up, times the K steps, writes
+its outputs if asked to, and prints the JSON line (roofline figures from the counters and HIP events of the timed steps).
+--full adds what takes runs of its own behind the timed region: the hardware-counter passes (N = 1), the one-slot-group
+per-kernel breakdown (octree), the uniform-box source as `secondary`, the CPU baseline and (N > 1) the reduce check;
+--no-counters, --no-breakdown, --no-secondary and --no-cpu-baseline leave single ones of them out again.
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed -- the detector frames the engine
 filled (DIR/frames.npy) and, with a stored radiation field, its table (DIR/radiation_field.npy) -- as float64, so that two
@@ -141,8 +147,8 @@ def pmc_in_run(scene_file, passthrough):
     for counters in ("FETCH_SIZE", "WRITE_SIZE", "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum SQ_INSTS_VALU SQ_WAVES"):
         out = tempfile.mkdtemp(prefix="bench_pmc_", dir="/tmp")
         cmd = [prof, "--pmc"] + counters.split() + ["--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__),
-               "--steps", "1", "--warmup", "0", "--packets", str(PMC_PASS_PACKETS), "--no-cpu-baseline", "--no-secondary", "--no-breakdown",
-               "--no-counters", "--scene-file", scene_file] + passthrough
+               "--steps", "1", "--warmup", "0", "--packets", str(PMC_PASS_PACKETS), "--full", "--no-cpu-baseline", "--no-secondary",
+               "--no-breakdown", "--no-counters", "--scene-file", scene_file] + passthrough
         try:
             subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=300, cwd="/tmp", env=env)
             files = glob.glob(os.path.join(out, "**", "*counter_collection.csv"), recursive=True)
@@ -226,7 +232,7 @@ def main():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the second measurement of the default run (the same octree with a uniform-box source)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--secondary", action="store_true", help="N > 1: also measure the uniform-box source (default at N = 1)")
+    ap.add_argument("--secondary", action="store_true", help="with --full, N > 1: also measure the uniform-box source (default at N = 1)")
     ap.add_argument("--no-breakdown", action="store_true", help="skip the per-kernel pass (one slot group, kernels in series) behind the timed region")
     ap.add_argument("--no-counters", action="store_true",
                     help="skip the hardware-counter passes behind the timed region (one step of 2e7 packets re-run under rocprofv3 --pmc: FETCH_SIZE, "
@@ -235,11 +241,17 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the arrays the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in "
                          "all: a larger array is replaced by a fixed, seeded sample of its values)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need, behind the timed region: counter passes, per-kernel "
+                         "breakdown, uniform-box secondary, CPU baseline, reduce check (the --no-* options leave single ones out)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    if not args.full:
+        args.no_counters = args.no_breakdown = args.no_secondary = args.no_cpu_baseline = True
+        args.secondary = False
 
     import torch
     import torch.distributed as dist
@@ -469,11 +481,11 @@ def main():
             elapsed = float(t.item())
         counters = eng.counters()
         walk_work = eng.walk_work()
-        # outside the timed region: one more (small) segment whose reduce is checked -- what rank 0 holds afterwards is the
+        # outside the timed region (--full): one more (small) segment whose reduce is checked -- what rank 0 holds afterwards is the
         # sum of what the ranks held before it.  wsed[0] (histories per wavelength bin that reached the first instrument's
         # SED) is a table of integer counts, so the comparison is exact.
         reduce_check = None
-        if world > 1 or comm is not None:
+        if args.full and (world > 1 or comm is not None):
             frames.zero_()
             torch.cuda.synchronize()
             n_check = 200000 * world
@@ -634,7 +646,7 @@ def main():
                 "rewalk_visits_per_packet": m["counters"]["rewalk_visits"] / launches / n,
                 "algorithmic_bytes_per_packet": bytes_per_launch / n, "algorithmic_bytes_per_visit": bytes_per_visit}
 
-    # behind the timed region (N = 1): hardware counters of this build on this box -- one step of 2e7 packets re-run under rocprofv3 --pmc on
+    # behind the timed region (--full, N = 1): hardware counters of this build on this box -- one step of 2e7 packets re-run under rocprofv3 --pmc on
     # the scene that the timed run saves
     counter_scene = None
     if rank == 0 and world == 1 and not args.no_counters and not args.scene_file:
@@ -653,7 +665,7 @@ def main():
             counters_in_run = pmc_in_run(counter_scene, passthrough)
         finally:
             os.unlink(counter_scene)
-    # the second source north_star names, measured in the same run on the same octree (default workload only): three steps
+    # the second source north_star names, measured in the same run on the same octree (--full, default workload only): three steps
     secondary = None
     if args.config == 2 and args.source == "sersic" and not args.store_radiation_field and not args.explicit_absorption and args.ski == SKI and not args.no_secondary \
             and (world == 1 or args.secondary):

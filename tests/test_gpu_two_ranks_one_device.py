@@ -75,12 +75,12 @@ def test_two_engine_ranks_on_one_device_equal_one(tmp_path):
 
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` without a launcher in front: the ranks are started by bench.py itself; on a one-GPU box they share
-    device 0 (BENCH_SHARE_DEVICE=1) and the line says that the exchange ran over gloo (nccl_ranks 0)"""
+    device 0 (BENCH_SHARE_DEVICE=1) and the line says that the exchange ran over gloo (nccl_ranks 0); --full adds the reduce check"""
     env = dict(os.environ, BENCH_SHARE_DEVICE="1", PMC_NUM_SLOTS=str(1 << 20))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--packets", "4e5",
-                          "--no-cpu-baseline", "--no-secondary", "--no-breakdown"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--no-secondary", "--no-breakdown"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["packets_per_step"] == 800000

@@ -7,7 +7,7 @@ O=$R/gpurun_out/${RUN_NAME:-r06_v2}
 rm -rf $O; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc $?" >> $O/pytest.log; tail -3 $O/pytest.log
 # (the headline run: with the driver's step counts, and with its own counter passes behind the timed region)
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
 # kernel trace of the bench command itself (three slot groups: launches overlap), and without overlap
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python $R/bench.py --steps 2 --warmup 1 --packets 2e7 --no-cpu-baseline --no-secondary --no-breakdown --no-counters > $O/kt.log 2>&1)
 (cd /tmp && PMC_NUM_GROUPS=1 PMC_SERIAL_WALKS=1 PMC_WALK_BLOCKS_PER_CU=3 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_one_group -- python $R/bench.py --steps 1 --warmup 0 --packets 5e7 --no-cpu-baseline --no-secondary --no-breakdown --no-counters > $O/kt1.log 2>&1)
@@ -25,11 +25,11 @@ PMC_PASS_ARGS="--config 5" tools/pmc_pass.sh ${RUN_NAME:-r06_v2}_voronoi_ta "TA_
 cat $R/gpurun_out/${RUN_NAME:-r06_v2}_voronoi_l2.txt $R/gpurun_out/${RUN_NAME:-r06_v2}_voronoi_ta.txt > $O/pmc_voronoi.txt; cat $O/pmc_voronoi.txt
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -size +8M -delete
 # the other workloads
-timeout 600 python bench.py --config 3 --steps 2 --warmup 1 --no-cpu-baseline --no-counters > $O/bench_config3.json 2> $O/c3.err
-timeout 900 python bench.py --config 4 --steps 2 --warmup 1 --packets 5e7 --no-counters > $O/bench_config4.json 2> $O/c4.err
-timeout 900 python bench.py --config 5 --steps 2 --warmup 1 > $O/bench_config5.json 2> $O/c5.err
-timeout 600 python bench.py --source uniform --steps 2 --warmup 1 --no-cpu-baseline --no-counters > $O/bench_uniform_source.json 2> $O/u.err
-timeout 600 python bench.py --store-radiation-field --steps 2 --warmup 1 --no-cpu-baseline --no-counters > $O/bench_radiation_field.json 2> $O/rf.err
+timeout 600 python bench.py --config 3 --steps 2 --warmup 1 --full --no-cpu-baseline --no-counters > $O/bench_config3.json 2> $O/c3.err
+timeout 900 python bench.py --config 4 --steps 2 --warmup 1 --packets 5e7 --full --no-counters > $O/bench_config4.json 2> $O/c4.err
+timeout 900 python bench.py --config 5 --steps 2 --warmup 1 --full > $O/bench_config5.json 2> $O/c5.err
+timeout 600 python bench.py --source uniform --steps 2 --warmup 1 --full --no-cpu-baseline --no-counters > $O/bench_uniform_source.json 2> $O/u.err
+timeout 600 python bench.py --store-radiation-field --steps 2 --warmup 1 --full --no-cpu-baseline --no-counters > $O/bench_radiation_field.json 2> $O/rf.err
 timeout 900 python bench.py --steps 1 --warmup 0 --packets 1e9 --no-cpu-baseline --no-secondary --no-breakdown --no-counters > $O/bench_one_segment_1e9.json 2> $O/b9.err
 for f in $O/bench*.json; do python -c "
 import json,sys
