@@ -159,23 +159,6 @@
         return __longlong_as_double(b);
     }
 
-    // TreeNode::leafChild from the given link downwards (TreeNode.cpp:66-76, OctTreeNode.cpp:36-41); returns a cell index
-    __device__ __forceinline__ int descend(const DevScene& S, const GridLds& L, uint32_t link, double x, double y, double z)
-    {
-        while ((int32_t)link < 0)
-        {
-            const NodeRec* rec = S.nodes + ((link >> PMC_LINK_EXP_BITS) & PMC_LINK_INDEX_MASK);
-            uint32_t ox, oy, oz, szb;
-            decodeBox(rec->code, L.stride, ox, oy, oz, szb);
-            const uint32_t hb = szb >> 1;
-            const double xc = tabAt(L.gtab, ox + hb);
-            const double yc = tabAt(L.gtab, oy + hb);
-            const double zc = tabAt(L.gtab, oz + hb);
-            const int l = (x < xc ? 0 : 1) + (y < yc ? 0 : 2) + (z < zc ? 0 : 4);
-            link = rec->child[l];
-        }
-        return link == PMC_LINK_NONE ? -1 : (int)(link >> PMC_LINK_EXP_BITS);
-    }
     // index of the finest-level interval [tab[i], tab[i+1]) of one axis that contains v (the last interval is closed):
     // exactly the sequence of `v < centre` decisions of the reference's descent, because every node centre IS an entry
     // of the coordinate table.  Arithmetic guess, corrected against the table in LDS.
@@ -864,7 +847,7 @@
     // loads the start state of the walk in task record t (pmc_device.h TaskArrays; all loads independent); returns the
     // record's bits word (PMC_TASK_NONE: no walk)
     template<int GRID>
-    __device__ __forceinline__ uint32_t loadTask(const DevScene& S, int64_t t, int slot, Walk& w, double& target, double& sext)
+    __device__ __forceinline__ uint32_t loadTask(const DevScene& S, int64_t t, Walk& w, double& target)
     {
         const TaskArrays& K = S.tasks;
         const uint32_t bits = K.bits[t];
@@ -876,9 +859,7 @@
         w.s = K.s0[t];
         w.ds = K.ds[t];
         target = K.target[t];
-        // (the extinction cross section at the history's wavelength travels in the slot; RN(1/k) is formed again here, as the
-        // cycle start kernel formed it: a record carries neither)
-        sext = S.mono ? S.mono_ext : S.slots.dustExt[slot];
+        // (RN(1/k) is formed again here, as the cycle start kernel formed it: a record does not carry it)
         setDirection(w, kx, ky, kz);
         if (GRID == GRID_CART)
         {
@@ -982,6 +963,197 @@
         return (x2 - x1) / (lnx2 - lnx1);
     }
 
+    // ------------------------------------------------------------------------------------------------
+    // what the walk kernels share: the reference's semantics of a segment, of the end of a walk and of its start, and the claiming of tasks
+
+    // the cross sections of the walk of `slot` at its packet's wavelength: extinction; EA scattering and absorption (the absorption depth
+    // starts from 0); MM each component's
+    template<bool EA, bool MM>
+    __device__ __forceinline__ void loadSections(const DevScene& S, const SlotArrays& A, int slot, double& sext, double& ssca, double& sabs, double& tabs,
+                                                 double* mx, double* msc, double* mab)
+    {
+        sext = S.mono ? S.mono_ext : A.dustExt[slot];
+        if (EA)
+        {
+            ssca = S.mono ? S.mono_sca : A.dustSca[slot];
+            sabs = S.mono ? S.mono_abs : A.dustAbs[slot];
+            tabs = 0.;
+        }
+        if (MM)
+            for (int h = 0; h < S.num_media; ++h) mediumSections(S, A, slot, h, mx[h], msc[h], mab[h]);
+    }
+    // (RF) a pass-1 walk starts: the packet's luminosity (PhotonPacket::luminosity()) and wavelength bin on this path
+    // (MonteCarloSimulation.cpp:638-662), no extinction before its first segment
+    __device__ __forceinline__ void rfStart(const DevScene& S, const SlotArrays& A, int slot, double& rfL, int& rfEll, double& rfExtBeg)
+    {
+        rfL = A.W[slot] / (S.mono ? S.mono_lambda : A.lambda[slot]);
+        rfEll = A.rfell[slot];
+        rfExtBeg = 1.;
+    }
+
+    // the optical depth(s) at the end of the pending segment (length ds through `cell`, density `dens`) from those at its start:
+    // MediumSystem.cpp:863-871 (sigma n ds); `apart` (EA: a walk that sums scattering and absorption depths apart) :920-926 (n ds first,
+    // then the two cross sections), non-forced :1099 (sigma_sca n ds); MM: mediaSegment
+    template<bool EA, bool MM>
+    __device__ __forceinline__ void segmentDepth(const DevScene& S, int cell, double dens, double ds, double tau, double tabs, bool apart, bool force,
+                                                 double sext, double ssca, double sabs, const double* mx, const double* msc, const double* mab,
+                                                 double& tau1, double& tabs1)
+    {
+        tau1 = tau + sext * dens * ds;
+        tabs1 = 0.;
+        if (MM)
+        {
+            tau1 = tau, tabs1 = tabs;
+            mediaSegment<EA>(S, cell, dens, ds, apart, mx, msc, mab, tau1, tabs1);
+        }
+        else if (EA && apart)
+        {
+            const double ns = dens * ds;
+            tau1 = force ? tau + ssca * ns : tau + ssca * dens * ds;
+            tabs1 = tabs + sabs * ns;
+        }
+    }
+
+    // (RF) the radiation-field contribution of a pass-1 segment of length ds > 0 (MonteCarloSimulation.cpp:648-661): L lnmean(e^-tau1, e^-tau0) ds
+    // into rf1(m, ell), tau = Segment::tauExt() (SpatialGridPath.hpp:108: scattering + absorption depth in the explicit-absorption cycle);
+    // extEnd = e^-tau1, the factor at the start of the next segment
+    template<bool EA>
+    __device__ __forceinline__ double rfSegment(double rfL, double rfExtBeg, double tau0, double tabs0, double tau1, double tabs1, double ds, double& extEnd)
+    {
+        const double lnExtEnd = EA ? -(tau1 + tabs1) : -tau1;
+#ifdef PMC_ABLATE_RF_MATH
+        extEnd = lnExtEnd;  // (tuning experiment only: wrong values)
+        return rfL * (extEnd + rfExtBeg) * ds;
+#else
+        extEnd = exp(lnExtEnd);
+        return rfL * lnmean(extEnd, rfExtBeg, lnExtEnd, EA ? -(tau0 + tabs0) : -tau0) * ds;
+#endif
+    }
+
+    // findInteractionPoint (SpatialGridPath.cpp:177-196) in the segment in which the walk stops, the first one with tau > target: its cell,
+    // the distance interpolated in it, and the density there -- EA: the absorption depth at the point instead, interpolated like the distance
+    // when the path was stored, or tau_sca x sigma_abs / sigma_sca in the non-forced walk (MediumSystem.cpp:1105-1106); several components:
+    // interpolated in both cycles (MediumSystem.cpp:1147-1149).  The segment's depths are formed again from its start.
+    template<bool EA, bool MM>
+    __device__ __forceinline__ void storeInteraction(const DevScene& S, const SlotArrays& A, int slot, int cell, double dens, double ds, double s,
+                                                     double tau, double tabs, double target, bool force, double sext, double ssca, double sabs,
+                                                     const double* mx, const double* msc, const double* mab)
+    {
+        double tau1, tabs1;
+        segmentDepth<EA, MM>(S, cell, dens, ds, tau, tabs, true, force, sext, ssca, sabs, mx, msc, mab, tau1, tabs1);
+        const double f = (target - tau) / (tau1 - tau);
+        A.mint[slot] = cell;
+        A.sint[slot] = s + f * ((s + ds) - s);
+        A.nint[slot] = EA && (MM || force) ? tabs + f * (tabs1 - tabs) : EA ? target * sabs / ssca : dens;
+    }
+
+    // the end of a pass-2 or non-forced walk that has not stopped in a segment: the interaction point beyond the last segment
+    // (SpatialGridPath.cpp:198-204; `density(m)`: the grid's density of cell m), or none (non-forced: the packet escapes)
+    template<bool EA, typename Density>
+    __device__ __forceinline__ void storeWalkEnd(const SlotArrays& A, int slot, bool force, int lastm, double s, double tabs, Density density)
+    {
+        if (force && lastm >= 0)
+        {
+            A.mint[slot] = lastm;
+            A.sint[slot] = s;
+            A.nint[slot] = EA ? tabs : density(lastm);
+        }
+        else
+            A.mint[slot] = -1;
+    }
+
+    // new tasks for the lanes of `want` from a wave-local pool that is refilled `chunk` tasks (a sparse generation's list of live slots: 64)
+    // at a time from the cursor S.counters[cursor] (one device-scope atomic per chunk: a single word saturates near 90 returning atomics per
+    // microsecond); returns the task index of this lane or -1
+    __device__ __forceinline__ int claimSlots(const DevScene& S, int cursor, unsigned long long numTasks, int lane, bool want,
+                                              unsigned long long& poolNext, unsigned long long& poolEnd, bool& exhausted,
+                                              unsigned long long chunk = PMC_TASK_CHUNK)
+    {
+        const unsigned long long idle = __ballot(want);
+        const int nidle = __popcll(idle);
+        if (!nidle || exhausted) return -1;
+        if (poolNext >= poolEnd)
+        {
+            unsigned long long got = 0;
+            if (lane == 0) got = atomicAdd(S.counters + cursor, chunk);
+            got = __shfl(got, 0, 64);
+            poolNext = got;
+            poolEnd = got + chunk;
+            if (poolEnd > numTasks) poolEnd = numTasks;
+            if (poolNext >= poolEnd)
+            {
+                poolNext = poolEnd = 0;
+                exhausted = true;
+                return -1;
+            }
+        }
+        const unsigned long long base = poolNext;
+        const unsigned long long avail = poolEnd - poolNext;
+        poolNext += (unsigned long long)nidle < avail ? (unsigned long long)nidle : avail;
+        if (!want) return -1;
+        const unsigned long long rank = __popcll(idle & ((1ull << lane) - 1ull));
+        return rank < avail ? (int)(base + rank) : -1;
+    }
+
+    // the XCD this wave runs on (0-7): a hint for locality only, nothing depends on it for correctness
+    __device__ __forceinline__ uint32_t xccId()
+    {
+        uint32_t v;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
+        return v & 7u;
+    }
+    // claimSlots over a task range cut into eight segments with a cursor each: a wave takes chunks from segment `seg` (its XCD's to begin
+    // with) until that is used up, then moves on to the next one; all eight used up: exhausted (the L2 of an XCD sees an eighth of the
+    // cells the walks in flight run through)
+    __device__ __forceinline__ int claimSegmented(unsigned long long* cursors, unsigned long long numTasks, int lane, bool want, unsigned long long& poolNext,
+                                                  unsigned long long& poolEnd, bool& exhausted, uint32_t& seg, uint32_t& tried)
+    {
+        const unsigned long long idle = __ballot(want);
+        const int nidle = __popcll(idle);
+        if (!nidle || exhausted) return -1;
+        while (poolNext >= poolEnd)
+        {
+            if (tried >= 8u)
+            {
+                poolNext = poolEnd = 0;
+                exhausted = true;
+                return -1;
+            }
+            const unsigned long long lo = (numTasks * seg) >> 3, hi = (numTasks * (seg + 1u)) >> 3;
+            unsigned long long got = 0;
+            if (lane == 0) got = atomicAdd(cursors + seg, (unsigned long long)PMC_TASK_CHUNK);
+            got = __shfl(got, 0, 64);
+            if (lo + got < hi)
+            {
+                poolNext = lo + got;
+                poolEnd = lo + got + PMC_TASK_CHUNK < hi ? lo + got + PMC_TASK_CHUNK : hi;
+            }
+            else
+            {
+                seg = (seg + 1u) & 7u;
+                tried += 1u;
+            }
+        }
+        const unsigned long long base = poolNext;
+        const unsigned long long avail = poolEnd - poolNext;
+        poolNext += (unsigned long long)nidle < avail ? (unsigned long long)nidle : avail;
+        if (!want) return -1;
+        const unsigned long long rank = __popcll(idle & ((1ull << lane) - 1ull));
+        return rank < avail ? (int)(base + rank) : -1;
+    }
+
+    // the wave's walk counters at the end of a walk kernel: pass-2 paths, visits, re-walked segments (DevScene::counters 1, 2, 6)
+    __device__ __forceinline__ void flushWalkCounters(const DevScene& S, int lane, uint32_t paths, uint32_t visits, uint32_t rewalks)
+    {
+        unsigned long long v;
+        v = waveSum(paths);
+        if (lane == 0 && v) atomicAdd(S.counters + 1, v);
+        v = waveSum(visits);
+        if (lane == 0 && v) atomicAdd(S.counters + 2, v);
+        v = waveSum(rewalks);
+        if (lane == 0 && v) atomicAdd(S.counters + 6, v);
+    }
+
     // Generic walk kernel of the Cartesian and Voronoi grids (the octree has its own kernels, pmc_walk_tree.inc): persistent
     // wavefronts, one walk per lane; a lane runs the task records of a slot one after the other (record 0: propagation
     // walk, continued from pass 1 into pass 2; record 1 + g: peel-off walk towards observer g).
@@ -1032,12 +1204,7 @@
         int rec = 0;        // task record of the slot that the lane is walking (0: propagation, 1 + g: peel-off)
         int vtab = -1;      // (Voronoi) table of the observer of the lane's peel-off walk (DevScene::vobs_*), or -1
         int streamRec = 0;  // (task stream) the record of the task the lane has just taken
-        uint32_t xcdSeg = 0u, xcdTried = 0u;  // (task stream) the eighth of the stream this wave takes its tasks from (its XCD's to begin with)
-        {
-            uint32_t v;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-            xcdSeg = v & 7u;
-        }
+        uint32_t xcdSeg = xccId(), xcdTried = 0u;  // (task stream) the eighth of the stream this wave takes its tasks from (its XCD's to begin with)
         uint32_t todoRecs = 0;  // records of the slot that are still to be walked (bit r: record r)
         uint32_t visits = 0, rewalks = 0, paths = 0;
         // radiation field (RF only): luminosity of the packet on this path, its wavelength bin, and the extinction
@@ -1073,37 +1240,7 @@
                         if (mode == MODE_PEEL)
                             A.ptau[(int64_t)(rec - 1) * A.num_slots + slot] = INFINITY;  // tau >= taumax (MediumSystem.cpp:1215-1218)
                         else
-                        {
-                            // findInteractionPoint (SpatialGridPath.cpp:177-196): first segment with tau > target
-                            // (target is the sampled optical depth here)
-                            const double s1 = w.s + w.ds;
-                            A.mint[slot] = w.cell;
-                            if (MM)
-                            {
-                                double tau1 = w.tau, tabs1 = tabs;
-                                mediaSegment<EA>(S, w.cell, w.dens, w.ds, true, mx, msc, mab, tau1, tabs1);
-                                const double f = (target - w.tau) / (tau1 - w.tau);
-                                // (several components, explicit absorption: interpolated in both cycles, MediumSystem.cpp:1147-1149)
-                                A.nint[slot] = EA ? tabs + f * (tabs1 - tabs) : w.dens;
-                                A.sint[slot] = w.s + f * (s1 - w.s);
-                            }
-                            else if (EA)
-                            {
-                                // (the absorption depth at the interaction point: interpolated like the distance when the path was stored
-                                // -- SpatialGridPath.cpp:177-196 --, or tau_sca x sigma_abs / sigma_sca in the non-forced walk, MediumSystem.cpp:1105-1106)
-                                const double ns = w.dens * w.ds;
-                                const double tau1 = force ? w.tau + ssca * ns : w.tau + ssca * w.dens * w.ds;
-                                const double f = (target - w.tau) / (tau1 - w.tau);
-                                A.nint[slot] = force ? tabs + f * ((tabs + sabs * ns) - tabs) : target * sabs / ssca;
-                                A.sint[slot] = w.s + f * (s1 - w.s);
-                            }
-                            else
-                            {
-                                const double tau1 = w.tau + sext * w.dens * w.ds;
-                                A.nint[slot] = w.dens;
-                                A.sint[slot] = w.s + ((target - w.tau) / (tau1 - w.tau)) * (s1 - w.s);
-                            }
-                        }
+                            storeInteraction<EA, MM>(S, A, slot, w.cell, w.dens, w.ds, w.s, w.tau, tabs, target, force, sext, ssca, sabs, mx, msc, mab);
                     }
                     else if (mode == MODE_PASS1 && w.tau > 0.)
                     {
@@ -1114,15 +1251,9 @@
                         A.ptau[(int64_t)(rec - 1) * A.num_slots + slot] = w.tau;
                     else if (mode == MODE_PASS1)
                         A.mint[slot] = -1;  // tau_path <= 0: the packet cannot scatter, the history ends
-                    else if (force && w.lastm >= 0)
-                    {
-                        // beyond the last segment (SpatialGridPath.cpp:198-204)
-                        A.mint[slot] = w.lastm;
-                        A.sint[slot] = w.s;
-                        A.nint[slot] = EA ? tabs : (GRID == GRID_VORO) ? S.vsite[4 * (int64_t)w.lastm + 3] : S.cell_density[w.lastm];
-                    }
                     else
-                        A.mint[slot] = -1;  // non-forced: the packet escapes
+                        storeWalkEnd<EA>(A, slot, force, w.lastm, w.s, tabs,
+                                         [&](int m) { return GRID == GRID_VORO ? S.vsite[4 * (int64_t)m + 3] : S.cell_density[m]; });
                     if (mode == MODE_PASS2 && force)
                         rewalks += nseg;
                     else
@@ -1130,84 +1261,31 @@
                     st = ST_IDLE;
                 }
                 const bool chain = st == ST_IDLE && !again && todoRecs != 0u;
-                // ---- new slots for the idle lanes from a wave-local pool that is refilled in chunks from the global
-                // cursor: one device-scope atomic per PMC_TASK_CHUNK slots (a single word saturates near 90 returning
-                // atomics per microsecond)
-                bool refill = false;
-                if (!exhausted)
+                // ---- new tasks for the idle lanes: from the stream in eight segments with a cursor each, or from the one cursor
+                const bool want = st == ST_IDLE && !again && !chain;
+                const int got = stream.xcdCursor ? claimSegmented(stream.xcdCursor, numTasks, lane, want, poolNext, poolEnd, exhausted, xcdSeg,
+                                                                  xcdTried)
+                                                 : claimSlots(S, taskCounter, numTasks, lane, want, poolNext, poolEnd, exhausted);
+                const bool refill = got >= 0;
+                if (refill)
                 {
-                    const unsigned long long idle = __ballot(st == ST_IDLE && !again && !chain);
-                    const int nidle = __popcll(idle);
-                    if (nidle && poolNext >= poolEnd && stream.xcdCursor)
+                    unsigned long long j = (unsigned long long)got;
+                    streamRec = 0;
+                    if (j < numProp)
+                        slot = stream.propList ? stream.propList[j] : taskBase + (int)j;
+                    else
                     {
-                        // (the stream in eight segments with a cursor each: this wave takes chunks of its XCD's segment until that is used
-                        // up, then of the next one -- the L2 of an XCD sees an eighth of the cells the walks in flight run through)
-                        while (poolNext >= poolEnd && !exhausted)
+                        j -= numProp;
+                        for (int k = 0; k < PMC_SORT_OBS; ++k)
                         {
-                            if (xcdTried >= 8u)
+                            if (k >= stream.numLists) break;
+                            if (j < listCount[k])
                             {
-                                poolNext = poolEnd = 0;
-                                exhausted = true;
+                                slot = stream.list[k][j];
+                                streamRec = stream.rec[k];
                                 break;
                             }
-                            const unsigned long long lo = (numTasks * xcdSeg) >> 3, hi = (numTasks * (xcdSeg + 1u)) >> 3;
-                            unsigned long long got = 0;
-                            if (lane == 0) got = atomicAdd(stream.xcdCursor + xcdSeg, (unsigned long long)PMC_TASK_CHUNK);
-                            got = __shfl(got, 0, 64);
-                            if (lo + got < hi)
-                            {
-                                poolNext = lo + got;
-                                poolEnd = lo + got + PMC_TASK_CHUNK < hi ? lo + got + PMC_TASK_CHUNK : hi;
-                            }
-                            else
-                            {
-                                xcdSeg = (xcdSeg + 1u) & 7u;
-                                xcdTried += 1u;
-                            }
-                        }
-                    }
-                    else if (nidle && poolNext >= poolEnd)
-                    {
-                        unsigned long long got = 0;
-                        if (lane == 0) got = atomicAdd(S.counters + taskCounter, (unsigned long long)PMC_TASK_CHUNK);
-                        got = __shfl(got, 0, 64);
-                        poolNext = got;
-                        poolEnd = got + PMC_TASK_CHUNK;
-                        if (poolEnd > numTasks) poolEnd = numTasks;
-                        if (poolNext >= poolEnd)
-                        {
-                            poolNext = poolEnd = 0;
-                            exhausted = true;
-                        }
-                    }
-                    const unsigned long long base = poolNext;
-                    const unsigned long long avail = poolEnd - poolNext;
-                    poolNext += (unsigned long long)nidle < avail ? (unsigned long long)nidle : avail;
-                    if (st == ST_IDLE && !again && !chain && !exhausted)
-                    {
-                        const unsigned long long rank = __popcll(idle & ((1ull << lane) - 1ull));
-                        if (rank < avail)
-                        {
-                            unsigned long long j = base + rank;
-                            streamRec = 0;
-                            if (j < numProp)
-                                slot = stream.propList ? stream.propList[j] : taskBase + (int)j;
-                            else
-                            {
-                                j -= numProp;
-                                for (int k = 0; k < PMC_SORT_OBS; ++k)
-                                {
-                                    if (k >= stream.numLists) break;
-                                    if (j < listCount[k])
-                                    {
-                                        slot = stream.list[k][j];
-                                        streamRec = stream.rec[k];
-                                        break;
-                                    }
-                                    j -= listCount[k];
-                                }
-                            }
-                            refill = true;
+                            j -= listCount[k];
                         }
                     }
                 }
@@ -1226,7 +1304,7 @@
                 double recTarget = 0., u1 = 0., u2 = 0.;
                 if (again || chain || refill)
                 {
-                    bits = loadTask<GRID>(S, (int64_t)rec * A.num_slots + slot, slot, w, recTarget, sext);
+                    bits = loadTask<GRID>(S, (int64_t)rec * A.num_slots + slot, w, recTarget);
                     if (again)
                     {
                         // the uniforms drawn for this step by the transition kernel (see startCycle)
@@ -1238,15 +1316,8 @@
                     else if (refill)
                         for (int r = 0; r < numRecords; ++r)
                             if (K.bits[(int64_t)r * A.num_slots + slot] != PMC_TASK_NONE) have |= 1u << r;
+                    loadSections<EA, MM>(S, A, slot, sext, ssca, sabs, tabs, mx, msc, mab);
                 }
-                if (EA && (again || chain || refill))
-                {
-                    ssca = S.mono ? S.mono_sca : A.dustSca[slot];
-                    sabs = S.mono ? S.mono_abs : A.dustAbs[slot];
-                    tabs = 0.;
-                }
-                if (MM && (again || chain || refill))
-                    for (int h = 0; h < S.num_media; ++h) mediumSections(S, A, slot, h, mx[h], msc[h], mab[h]);
                 if (again)
                 {
                     // ---- simulateForcedPropagation between the two passes (MonteCarloSimulation.cpp:696-722): the whole
@@ -1273,7 +1344,7 @@
                     {
                         // (rare: no propagation walk in this cycle) the first record that holds a walk
                         rec = __ffs((int)have) - 1;
-                        bits = loadTask<GRID>(S, (int64_t)rec * A.num_slots + slot, slot, w, recTarget, sext);
+                        bits = loadTask<GRID>(S, (int64_t)rec * A.num_slots + slot, w, recTarget);
                     }
                     mode = bits & 3u;
                     target = recTarget;
@@ -1282,13 +1353,7 @@
                 }
                 // (Voronoi) a peel-off walk reads its observer's packed neighbour lists
                 if (GRID == GRID_VORO) vtab = (st == ST_ACTIVE && mode == MODE_PEEL) ? (int)S.vobs_of_inst[rec - 1] : -1;
-                // (RF) a propagation walk of the forced-scattering cycle starts: the packet's luminosity and bin
-                if (RF && st == ST_ACTIVE && !again && (chain || refill) && mode == MODE_PASS1)
-                {
-                    rfL = A.W[slot] / (S.mono ? S.mono_lambda : A.lambda[slot]);  // PhotonPacket::luminosity()
-                    rfEll = A.rfell[slot];
-                    rfExtBeg = 1.;
-                }
+                if (RF && st == ST_ACTIVE && !again && (chain || refill) && mode == MODE_PASS1) rfStart(S, A, slot, rfL, rfEll, rfExtBeg);
                 // (Voronoi) a walk whose first cell the cycle start kernel has located only: its first step finds the exit
                 if (GRID == GRID_VORO && st == ST_ACTIVE && (again || chain || refill) && w.ci == PMC_VORO_FIRST_SCAN) st = ST_FIRST;
             }
@@ -1305,20 +1370,8 @@
                     // MediumSystem.cpp:1207-1219 (peel-off: stop once tau >= taumax), :988-1008 (non-forced).
                     // A zero-length segment changes neither tau nor s, so it may be added unconditionally.
                     const double ds = w.ds;
-                    double tau1 = w.tau + sext * w.dens * ds;
-                    double tabs1 = 0.;
-                    if (MM)
-                    {
-                        tau1 = w.tau, tabs1 = tabs;
-                        mediaSegment<EA>(S, w.cell, w.dens, ds, mode != MODE_PEEL, mx, msc, mab, tau1, tabs1);
-                    }
-                    else if (EA && mode != MODE_PEEL)
-                    {
-                        // MediumSystem.cpp:920-926 (n ds first, then the two cross sections); non-forced: :1099 (sigma_sca n ds)
-                        const double ns = w.dens * ds;
-                        tau1 = force ? w.tau + ssca * ns : w.tau + ssca * w.dens * ds;
-                        tabs1 = tabs + sabs * ns;
-                    }
+                    double tau1, tabs1;
+                    segmentDepth<EA, MM>(S, w.cell, w.dens, ds, w.tau, tabs, mode != MODE_PEEL, force, sext, ssca, sabs, mx, msc, mab, tau1, tabs1);
                     if (tau1 > target)
                         st = ST_HIT;
                     else
@@ -1337,15 +1390,9 @@
                         }
                         if (RF && mode == MODE_PASS1 && ds > 0.)
                         {
-                            // MonteCarloSimulation.cpp:648-661: L * lnmean(e^-tau1, e^-tau0) * ds into rf1(m, ell); tau = Segment::tauExt()
-                            // (SpatialGridPath.hpp:108: scattering + absorption depth in the explicit-absorption cycle)
-                            const double lnExtEnd = EA ? -(tau1 + tabs1) : -tau1;
-                            const double extEnd = exp(lnExtEnd);
-                            if (rfEll >= 0)
-                            {
-                                const double extMean = lnmean(extEnd, rfExtBeg, lnExtEnd, EA ? -(tau0 + tabs0) : -tau0);
-                                unsafeAtomicAdd(S.rf + ((int64_t)w.cell * S.rf_num_lambda + rfEll), rfL * extMean * ds);
-                            }
+                            double extEnd;
+                            const double rfValue = rfSegment<EA>(rfL, rfExtBeg, tau0, tabs0, tau1, tabs1, ds, extEnd);
+                            if (rfEll >= 0) unsafeAtomicAdd(S.rf + ((int64_t)w.cell * S.rf_num_lambda + rfEll), rfValue);
                             rfExtBeg = extEnd;
                         }
                         if (GRID == GRID_VORO)
@@ -1368,13 +1415,7 @@
                 }
             }
         }
-        unsigned long long v;
-        v = waveSum(paths);
-        if (lane == 0 && v) atomicAdd(S.counters + 1, v);
-        v = waveSum(visits);
-        if (lane == 0 && v) atomicAdd(S.counters + 2, v);
-        v = waveSum(rewalks);
-        if (lane == 0 && v) atomicAdd(S.counters + 6, v);
+        flushWalkCounters(S, lane, paths, visits, rewalks);
     }
 
     // ================================================================================================

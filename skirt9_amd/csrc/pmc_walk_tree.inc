@@ -327,85 +327,6 @@
         C.numCells = (uint32_t)S.cell_slots;
     }
 
-    // new slots for the lanes of `want` from a wave-local pool that is refilled PMC_TASK_CHUNK slots (a sparse generation's list
-    // of live slots: 64) at a time from the
-    // group's cursor (one device-scope atomic per chunk); returns the slot offset of this lane or -1
-    __device__ __forceinline__ int claimSlots(const DevScene& S, int cursor, unsigned long long numTasks, int lane, bool want,
-                                              unsigned long long& poolNext, unsigned long long& poolEnd, bool& exhausted,
-                                              unsigned long long chunk = PMC_TASK_CHUNK)
-    {
-        const unsigned long long idle = __ballot(want);
-        const int nidle = __popcll(idle);
-        if (!nidle || exhausted) return -1;
-        if (poolNext >= poolEnd)
-        {
-            unsigned long long got = 0;
-            if (lane == 0) got = atomicAdd(S.counters + cursor, chunk);
-            got = __shfl(got, 0, 64);
-            poolNext = got;
-            poolEnd = got + chunk;
-            if (poolEnd > numTasks) poolEnd = numTasks;
-            if (poolNext >= poolEnd)
-            {
-                poolNext = poolEnd = 0;
-                exhausted = true;
-                return -1;
-            }
-        }
-        const unsigned long long base = poolNext;
-        const unsigned long long avail = poolEnd - poolNext;
-        poolNext += (unsigned long long)nidle < avail ? (unsigned long long)nidle : avail;
-        if (!want) return -1;
-        const unsigned long long rank = __popcll(idle & ((1ull << lane) - 1ull));
-        return rank < avail ? (int)(base + rank) : -1;
-    }
-
-    // the XCD this wave runs on (0-7): a hint for locality only, nothing depends on it for correctness
-    __device__ __forceinline__ uint32_t xccId()
-    {
-        uint32_t v;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-        return v & 7u;
-    }
-    // claimSlots over a task range cut into eight segments with a cursor each: a wave takes chunks from segment `seg` (its XCD's to begin
-    // with) until that is used up, then moves on to the next one; all eight used up: exhausted
-    __device__ __forceinline__ int claimSegmented(unsigned long long* cursors, unsigned long long numTasks, int lane, bool want, unsigned long long& poolNext,
-                                                  unsigned long long& poolEnd, bool& exhausted, uint32_t& seg, uint32_t& tried)
-    {
-        const unsigned long long idle = __ballot(want);
-        const int nidle = __popcll(idle);
-        if (!nidle || exhausted) return -1;
-        while (poolNext >= poolEnd)
-        {
-            if (tried >= 8u)
-            {
-                poolNext = poolEnd = 0;
-                exhausted = true;
-                return -1;
-            }
-            const unsigned long long lo = (numTasks * seg) >> 3, hi = (numTasks * (seg + 1u)) >> 3;
-            unsigned long long got = 0;
-            if (lane == 0) got = atomicAdd(cursors + seg, (unsigned long long)PMC_TASK_CHUNK);
-            got = __shfl(got, 0, 64);
-            if (lo + got < hi)
-            {
-                poolNext = lo + got;
-                poolEnd = lo + got + PMC_TASK_CHUNK < hi ? lo + got + PMC_TASK_CHUNK : hi;
-            }
-            else
-            {
-                seg = (seg + 1u) & 7u;
-                tried += 1u;
-            }
-        }
-        const unsigned long long base = poolNext;
-        const unsigned long long avail = poolEnd - poolNext;
-        poolNext += (unsigned long long)nidle < avail ? (unsigned long long)nidle : avail;
-        if (!want) return -1;
-        const unsigned long long rank = __popcll(idle & ((1ull << lane) - 1ull));
-        return rank < avail ? (int)(base + rank) : -1;
-    }
-
     // ================================================================================================
     //  peel-off walks towards observer `obs` (the instrument that starts an observer group) of the slots
     //  [slotBase, slotBase + numSlots): task record 1 + obs of every slot; result: SlotArrays::ptau
@@ -962,32 +883,8 @@
                 {
                     if (st == ST_HIT)
                     {
-                        // findInteractionPoint (SpatialGridPath.cpp:177-196): first segment with tau > target
                         nseg += 1;
-                        const double s1 = w.s + w.ds;
-                        A.mint[slot] = (int)w.cell;
-                        if (MM)
-                        {
-                            double tau1 = w.tau, tabs1 = tabs;
-                            mediaSegment<EA>(S, (int)w.cell, w.dens, w.ds, true, mx, msc, mab, tau1, tabs1);
-                            const double f = (target - w.tau) / (tau1 - w.tau);
-                            A.nint[slot] = EA ? tabs + f * (tabs1 - tabs) : w.dens;
-                            A.sint[slot] = w.s + f * (s1 - w.s);
-                        }
-                        else if (EA)
-                        {
-                            const double ns = w.dens * w.ds;
-                            const double tau1 = force ? w.tau + ssca * ns : w.tau + ssca * w.dens * w.ds;
-                            const double f = (target - w.tau) / (tau1 - w.tau);
-                            A.nint[slot] = force ? tabs + f * ((tabs + sabs * ns) - tabs) : target * sabs / ssca;
-                            A.sint[slot] = w.s + f * (s1 - w.s);
-                        }
-                        else
-                        {
-                            const double tau1 = w.tau + sext * w.dens * w.ds;
-                            A.nint[slot] = w.dens;
-                            A.sint[slot] = w.s + ((target - w.tau) / (tau1 - w.tau)) * (s1 - w.s);
-                        }
+                        storeInteraction<EA, MM>(S, A, slot, (int)w.cell, w.dens, w.ds, w.s, w.tau, tabs, target, force, sext, ssca, sabs, mx, msc, mab);
                     }
                     else if (mode == MODE_PASS1 && w.tau > 0.)
                     {
@@ -1032,15 +929,8 @@
                     }
                     else if (mode == MODE_PASS1)
                         A.mint[slot] = -1;  // tau_path <= 0: the packet cannot scatter, the history ends
-                    else if (force && w.lastm >= 0)
-                    {
-                        // beyond the last segment (SpatialGridPath.cpp:198-204)
-                        A.mint[slot] = w.lastm;
-                        A.sint[slot] = w.s;
-                        A.nint[slot] = EA ? tabs : S.leaves[w.lastm].density;
-                    }
                     else
-                        A.mint[slot] = -1;  // non-forced: the packet escapes
+                        storeWalkEnd<EA>(A, slot, force, w.lastm, w.s, tabs, [&](int m) { return S.leaves[m].density; });
                     if (!resumed)
                     {
                         if (mode == MODE_PASS2 && force)
@@ -1056,8 +946,9 @@
                 if (again || got >= 0)
                 {
                     // the start state of the propagation walk (record 0): for a new slot, and again for pass 2
-                    // (all fields at once: one round trip; the first cell first, so that its record can be requested while
-                    // the others are still on their way)
+                    // (all fields of the record at once: one round trip; the first cell first, so that its record can be requested
+                    // while the others are still on their way.  The cross sections -- loadSections -- follow once the flags have
+                    // arrived, with the first cell's record: the first step waits for that record anyway)
                     const int64_t t = slot;
                     const uint32_t cell0 = (uint32_t)K.cell[t];
                     const uint32_t bits = K.bits[t];
@@ -1069,7 +960,7 @@
                     const double rx0 = A.rx[slot], ry0 = A.ry[slot], rz0 = A.rz[slot];
                     const double kx0 = A.kx[slot], ky0 = A.ky[slot], kz0 = A.kz[slot];
                     // (forced scattering: every record is a pass 1, without a stop value)
-                    const double ds0 = K.ds[t], target0 = force ? INFINITY : K.target[t], sext0 = S.mono ? S.mono_ext : A.dustExt[slot];
+                    const double ds0 = K.ds[t], target0 = force ? INFINITY : K.target[t];
                     double s0 = 0.;
                     if (bits != PMC_TASK_NONE)
                     {
@@ -1092,20 +983,12 @@
                         w.s = s0;
                         w.ds = ds0;
                         if (!again) target = target0;
-                        sext = sext0;
                         w.axis = (bits >> 2) & 3u;
                         d.sgn = (bits >> 4) & 7u;
                         setDirMasks(d);
                         w.tau = 0.;
                         w.lastm = -1;
-                        if (EA)
-                        {
-                            ssca = S.mono ? S.mono_sca : A.dustSca[slot];
-                            sabs = S.mono ? S.mono_abs : A.dustAbs[slot];
-                            tabs = 0.;
-                        }
-                        if (MM)
-                            for (int h = 0; h < S.num_media; ++h) mediumSections(S, A, slot, h, mx[h], msc[h], mab[h]);
+                        loadSections<EA, MM>(S, A, slot, sext, ssca, sabs, tabs, mx, msc, mab);
                         mode = bits & 3u;
                         nseg = 0;
                         st = ST_ACTIVE;
@@ -1119,12 +1002,7 @@
                     if (again)
                         mode = MODE_PASS2;  // (the same path again from its start, up to the depth sampled above)
                     else if (RF && st == ST_ACTIVE && mode == MODE_PASS1)
-                    {
-                        // the packet's luminosity and bin on this path (MonteCarloSimulation.cpp:638-662)
-                        rfL = A.W[slot] / (S.mono ? S.mono_lambda : A.lambda[slot]);
-                        rfEll = A.rfell[slot];
-                        rfExtBeg = 1.;
-                    }
+                        rfStart(S, A, slot, rfL, rfEll, rfExtBeg);
                 }
                 if (fresh) cellIssue(C, w.cell, g);
                 PMC_WSTAMP(6);
@@ -1183,20 +1061,8 @@
                     // the pending segment: MediumSystem.cpp:863-871 (pass 1), SpatialGridPath.cpp:177-196 (pass 2: stop in
                     // the first segment with tau > target), :988-1008 (non-forced)
                     const double ds = w.ds;
-                    double tau1 = w.tau + sext * w.dens * ds;
-                    double tabs1 = 0.;
-                    if (MM)
-                    {
-                        tau1 = w.tau, tabs1 = tabs;
-                        mediaSegment<EA>(S, (int)w.cell, w.dens, ds, true, mx, msc, mab, tau1, tabs1);
-                    }
-                    else if (EA)
-                    {
-                        // MediumSystem.cpp:920-926 (n ds first, then the two cross sections); non-forced: :1099 (sigma_sca n ds)
-                        const double ns = w.dens * ds;
-                        tau1 = force ? w.tau + ssca * ns : w.tau + ssca * w.dens * ds;
-                        tabs1 = tabs + sabs * ns;
-                    }
+                    double tau1, tabs1;
+                    segmentDepth<EA, MM>(S, (int)w.cell, w.dens, ds, w.tau, tabs, true, force, sext, ssca, sabs, mx, msc, mab, tau1, tabs1);
                     if (tau1 > target)
                         st = ST_HIT;
                     else
@@ -1215,25 +1081,15 @@
                         }
                         if (RF && mode == MODE_PASS1 && ds > 0.)
                         {
-                            // MonteCarloSimulation.cpp:648-661: L * lnmean(e^-tau1, e^-tau0) * ds into rf1(m, ell)
-                            const double lnExtEnd = EA ? -(tau1 + tabs1) : -tau1;  // (Segment::tauExt(), SpatialGridPath.hpp:108)
-#ifdef PMC_ABLATE_RF_MATH
-                            const double extEnd = lnExtEnd;  // (tuning experiment only: wrong values)
-#else
-                            const double extEnd = exp(lnExtEnd);
-#endif
+                            double extEnd;
+                            const double value = rfSegment<EA>(rfL, rfExtBeg, tau0, tabs0, tau1, tabs1, ds, extEnd);
                             if (rfEll >= 0)
                             {
-#ifdef PMC_ABLATE_RF_MATH
-                                const double extMean = extEnd + rfExtBeg;
-#else
-                                const double extMean = lnmean(extEnd, rfExtBeg, lnExtEnd, EA ? -(tau0 + tabs0) : -tau0);
-#endif
                                 // (the contribution is handed over below, where the lanes of the wave have converged)
                                 // (the key of the log counts cells in the DEVICE numbering: the caller's cell index is looked up when the
                                 // sums are added to the table -- once per key and partition instead of once per step)
                                 rfAt = (int64_t)w.cell * S.rf_num_lambda + rfEll;
-                                rfValue = rfL * extMean * ds;
+                                rfValue = value;
                                 rfPending = true;
                             }
                             rfExtBeg = extEnd;
@@ -1339,13 +1195,7 @@
         if (RF && rfLog.cap != 0ull)
             for (uint32_t i = logFill + (uint32_t)lane; i < (uint32_t)PMC_RF_LOG_CHUNK; i += 64u) rfLog.keys[logBase + i] = rfLog.padKey;
         PMC_PERTURB_FINISH;
-        unsigned long long v;
-        v = waveSum(paths);
-        if (lane == 0 && v) atomicAdd(S.counters + 1, v);
-        v = waveSum(visits);
-        if (lane == 0 && v) atomicAdd(S.counters + 2, v);
-        v = waveSum(rewalks);
-        if (lane == 0 && v) atomicAdd(S.counters + 6, v);
+        flushWalkCounters(S, lane, paths, visits, rewalks);
         if (lane == 0 && waveSteps)
         {
             atomicAdd(S.counters + PMC_CTR_WALKWORK + 3, waveSteps);
