@@ -267,6 +267,20 @@ typedef struct pmc_scene
     const pmc_medium* media;
 } pmc_scene;
 
+/* What the scene's layout of ABI version 9 has no room for, handed to pmc_create_ext next to the scene (struct_size = sizeof(pmc_scene_ext) of
+   the caller: members are only ever added at the end).
+   phase_function[h]: the scattering phase function of medium component h (the only component: h = 0).  PMC_PHASE_HG: Henyey-Greenstein with
+   pmc_medium::asymmpar (DustMix.cpp:395-445, 490-511).  PMC_PHASE_DIPOLE: the dipole phase function of unpolarized Thomson scattering by free
+   electrons without thermal dispersion (ElectronMix.cpp:99-146, DipolePhaseFunction.cpp:47-59, 122-133, 164-172); such a component's pmc_medium
+   holds ordinary tables -- sigma_sca = sigma_ext = the Thomson cross section, sigma_abs = 0, asymmpar = 0 (not read) -- with borders that span
+   the simulation's wavelength range. */
+enum { PMC_PHASE_HG = 0, PMC_PHASE_DIPOLE = 1 };
+typedef struct pmc_scene_ext
+{
+    int32_t struct_size;
+    int32_t phase_function[PMC_MAX_MEDIA];
+} pmc_scene_ext;
+
 /* counted work, accumulated over all pmc_run_primary calls since create/reset (roofline inputs) */
 typedef struct pmc_counter_values
 {
@@ -294,6 +308,9 @@ int64_t pmc_frame_layout_of(const pmc_scene* scene, int32_t instrument, pmc_fram
 
 /* --- device API */
 int pmc_create(const pmc_scene* scene, int32_t device, pmc_ctx** out);
+/* pmc_create with the scene's extension; ext == NULL: every component is Henyey-Greenstein (what pmc_create does).  An unknown phase function
+   kind fails with PMC_ERR_UNSUPPORTED. */
+int pmc_create_ext(const pmc_scene* scene, const pmc_scene_ext* ext, int32_t device, pmc_ctx** out);
 void pmc_destroy(pmc_ctx* ctx);
 /* Use caller-owned DEVICE memory (num_doubles f64, zero-initialised by the caller) for the frames instead of the
    context's own allocation -- e.g. a torch tensor, so that torch.distributed can reduce it over RCCL. */

@@ -52,6 +52,10 @@ typedef struct pmc_debug_table_values
 } pmc_debug_table_values;
 int pmc_debug_tables(pmc_ctx* ctx, pmc_debug_table_values* out);
 
+/* Test aid: the device function with which the transition kernel turns a uniform deviate X into the scattering cosine of the dipole phase
+   function (DipolePhaseFunction::generateCosineFromPhaseFunction), run over n host-supplied deviates u; cos_out: n doubles on the host. */
+int pmc_tune_dipole_cosines(pmc_ctx* ctx, const double* u, int64_t n, double* cos_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,8 @@ int skh_set_particle_sampler(skh_simulation* sim, void* create, void* density, v
 int skh_setup(skh_simulation* sim);
 /* valid after skh_setup, owned by the simulation */
 const pmc_scene* skh_scene(const skh_simulation* sim);
+/* what goes to pmc_create_ext next to the scene: the phase function of every medium component (valid after skh_setup, owned by the simulation) */
+const pmc_scene_ext* skh_scene_ext(const skh_simulation* sim);
 uint64_t skh_num_packets(const skh_simulation* sim);
 int32_t  skh_seed(const skh_simulation* sim);
 uint64_t skh_setup_draws(const skh_simulation* sim);
@@ -55,12 +57,14 @@ int skh_summary(const skh_simulation* sim, char* buffer, int32_t capacity);
 /* A set-up scene as ONE file: everything pmc_create reads plus the numbers a driver of the photon loop needs.  In a job of
    one process per GPU, one process sets the simulation up (all host cores) and saves it, the others load it instead of
    repeating the setup -- the reference repeats Simulation::setupSimulation in every MPI process.  A loaded scene serves
-   pmc_create and the frame layout; the output files are written by the process that holds the simulation. */
+   pmc_create_ext and the frame layout; the output files are written by the process that holds the simulation. */
 int skh_scene_save(const skh_simulation* sim, const char* path);
 typedef struct skh_scene_file skh_scene_file;
 skh_scene_file* skh_scene_load(const char* path);
 void skh_scene_file_free(skh_scene_file* file);
 const pmc_scene* skh_scene_file_scene(const skh_scene_file* file);
+/* the extension saved with the scene; a file written before scenes had one gives every component as Henyey-Greenstein */
+const pmc_scene_ext* skh_scene_file_scene_ext(const skh_scene_file* file);
 enum { SKH_SCENE_SEED = 0, SKH_SCENE_NUM_PACKETS = 1, SKH_SCENE_FRAME_SIZE = 2, SKH_SCENE_RADIATION_FIELD_SIZE = 3, SKH_SCENE_SETUP_DRAWS = 4 };
 int64_t skh_scene_file_number(const skh_scene_file* file, int32_t what);
 int skh_scene_file_layout(const skh_scene_file* file, int32_t instrument, pmc_frame_layout* out);

@@ -116,9 +116,29 @@ void pmc_destroy(pmc_ctx* ctx)
 
 int pmc_create(const pmc_scene* scene, int32_t device, pmc_ctx** out)
 {
+    return pmc_create_ext(scene, nullptr, device, out);
+}
+
+int pmc_create_ext(const pmc_scene* scene, const pmc_scene_ext* ext, int32_t device, pmc_ctx** out)
+{
     if (!scene || !out) return fail(PMC_ERR_INVALID, "null argument");
     *out = nullptr;
     if (scene->abi_version != PMC_ABI_VERSION) return fail(PMC_ERR_INVALID, "pmc_scene ABI version mismatch");
+    // the phase function of every component (a shorter pmc_scene_ext of an older caller has none: Henyey-Greenstein)
+    int32_t phaseKind[PMC_MAX_MEDIA];
+    for (int h = 0; h < PMC_MAX_MEDIA; ++h) phaseKind[h] = PMC_PHASE_HG;
+    if (ext)
+    {
+        if (ext->struct_size < int32_t(sizeof(int32_t))) return fail(PMC_ERR_INVALID, "pmc_scene_ext::struct_size is not set");
+        const int components = scene->num_media > 1 ? scene->num_media : 1;
+        for (int h = 0; h < components && h < PMC_MAX_MEDIA; ++h)
+        {
+            if (size_t(ext->struct_size) < offsetof(pmc_scene_ext, phase_function) + sizeof(int32_t) * size_t(h + 1)) break;
+            phaseKind[h] = ext->phase_function[h];
+            if (phaseKind[h] != PMC_PHASE_HG && phaseKind[h] != PMC_PHASE_DIPOLE)
+                return fail(PMC_ERR_UNSUPPORTED, "unknown phase function kind " + std::to_string(phaseKind[h]) + " of medium component " + std::to_string(h));
+        }
+    }
     if (pmcExperimentBuild())
     {
         static std::atomic<bool> said{false};
@@ -257,6 +277,12 @@ int pmc_create(const pmc_scene* scene, int32_t device, pmc_ctx** out)
             if ((rc = ctx->upload(sigmaAbs, mh.num_lambda, &M.sigma_abs))) return bail(rc);
             if ((rc = ctx->upload(mh.asymmpar, mh.num_lambda, &M.asymmpar))) return bail(rc);
         }
+    }
+    D.any_dipole = 0;
+    for (int h = 0; h < PMC_MAX_MEDIA; ++h)
+    {
+        D.phase_kind[h] = h < D.num_media ? phaseKind[h] : PMC_PHASE_HG;
+        if (D.phase_kind[h] == PMC_PHASE_DIPOLE) D.any_dipole = 1;
     }
     int walkDoubles = D.lds_grid_len;   // walk kernels and cycle start kernel: the grid tables, at offset 0
     int transDoubles = 0;               // transition and launch kernels: no grid tables

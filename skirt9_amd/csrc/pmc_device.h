@@ -360,6 +360,10 @@ struct DevScene
     int32_t lds_dust_off;
     int32_t lds_src_off, lds_sed_off, lds_sed_len, lds_hot_off, lds_sort_off, lds_total_transition, lds_total_launch, lds_total_walk;
     int32_t dust_in_lds;           // the launch kernel stages the index borders of the dust mix (DustMix::_lambdav) in LDS
+    // ---- phase function of every medium component (pmc.h PMC_PHASE_*, pmc_scene_ext): read only by the dipole flavour of the transition
+    //      kernel, which runs when some component has the dipole (any_dipole)
+    int32_t phase_kind[PMC_MAX_MEDIA];
+    int32_t any_dipole;
 };
 
 // The radiation-field contributions of the propagation walks of one slot group and generation (octree): (key, value)

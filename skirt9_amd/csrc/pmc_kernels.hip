@@ -384,6 +384,7 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
                {reinterpret_cast<const void*>(&traceRayKernel<GRID_CART>), walkMax},
                {reinterpret_cast<const void*>(&traceRayKernel<GRID_VORO>), walkMax},
                {reinterpret_cast<const void*>(&transitionKernel), transitionMax},
+               {reinterpret_cast<const void*>(&transitionDipoleKernel), transitionMax},
                {reinterpret_cast<const void*>(&launchKernel), transitionMax},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_TREE>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_CART>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
@@ -599,14 +600,16 @@ extern "C" hipError_t pmcLaunchStatMerge(int slot, int blocks, hipStream_t strea
 
 // transitions of the slots [slotBase, slotBase + numSlots) of slot group `group`, followed by the scan of the group's
 // ended-history counts (the launch kernel's history indices)
-extern "C" hipError_t pmcLaunchTransition(int slot, int slotBase, int numSlots, int group, uint64_t seed, const int* list, int listLen, int maxBlocks,
+// dipole: some medium component has the dipole phase function (DevScene::any_dipole): the kernel flavour that knows it
+extern "C" hipError_t pmcLaunchTransition(int slot, int dipole, int slotBase, int numSlots, int group, uint64_t seed, const int* list, int listLen, int maxBlocks,
                                           size_t ldsBytes, const StatLogArgs* statLog, uint64_t count, hipStream_t stream)
 {
     const StatLogArgs none = {nullptr, nullptr, 0ull, 0, nullptr, nullptr, nullptr};
     const int block = PMC_TRANSITION_BLOCK;
     // (a sparse generation: one list entry per lane; otherwise persistent workgroups over runs of 256 slots per wave)
     const int grid = std::max(1, std::min(((list ? listLen : numSlots) + block - 1) / block, maxBlocks));
-    hipLaunchKernelGGL(transitionKernel, dim3(grid), dim3(block), ldsBytes, stream, slot, slotBase, numSlots, group, seed, list, listLen, statLog ? *statLog : none);
+    hipLaunchKernelGGL(dipole ? transitionDipoleKernel : transitionKernel, dim3(grid), dim3(block), ldsBytes, stream, slot, slotBase, numSlots, group, seed, list, listLen,
+                       statLog ? *statLog : none);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || list) return e;  // (a sparse generation retires its ended histories in the transition kernel)
     hipLaunchKernelGGL(endedScanKernel, dim3(1), dim3(PMC_SCAN_THREADS), 0, stream, slot, slotBase, numSlots, group, (unsigned long long)count);
@@ -639,6 +642,23 @@ extern "C" hipError_t pmcLaunchCycleStart(int slot, int gridKind, int slotBase, 
     const int grid = std::max(1, std::min(((listIn ? listLen : numSlots) + 255) / 256, maxBlocks));
     const auto kernel = gridKind == PMC_GRID_OCTREE ? cycleStartKernel<GRID_TREE> : gridKind == PMC_GRID_VORONOI ? cycleStartKernel<GRID_VORO> : cycleStartKernel<GRID_CART>;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), ldsBytes, stream, slot, slotBase, numSlots, listCounter, listOut, listIn, listLen, ps);
+    return hipGetLastError();
+}
+
+// test aid (pmc_tuning.h pmc_tune_dipole_cosines): the transition kernel's own conversion of a uniform deviate into the scattering cosine of
+// the dipole phase function, over n deviates in device memory
+namespace
+{
+    __global__ __launch_bounds__(256) void dipoleCosineKernel(const double* __restrict__ u, const int64_t n, double* __restrict__ out)
+    {
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n) out[i] = PhaseDipole::cosineFor(u[i]);
+    }
+}
+extern "C" hipError_t pmcLaunchDipoleCosines(const double* u, int64_t n, double* out, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(dipoleCosineKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, u, n, out);
     return hipGetLastError();
 }
 

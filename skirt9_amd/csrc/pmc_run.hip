@@ -781,7 +781,7 @@ namespace
         HIP_TRY(hipEventRecord(ctx->evB[g], sg));
         HIP_TRY(hipMemsetAsync(ctr + PMC_CTR_LIVE(g), 0, sizeof(unsigned long long), sg));
         const StatLogArgs statLog = statLogOf(ctx, P, g);
-        HIP_TRY(pmcLaunchTransition(ctx->slot, P.base[g], P.size[g], g, P.seed, listIn, listLen, P.transitionBlocks, ctx->transitionLds, &statLog, P.count, sg));
+        HIP_TRY(pmcLaunchTransition(ctx->slot, ctx->dev.any_dipole, P.base[g], P.size[g], g, P.seed, listIn, listLen, P.transitionBlocks, ctx->transitionLds, &statLog, P.count, sg));
         if (!listIn)
             HIP_TRY(pmcLaunchLaunch(ctx->slot, P.base[g], P.size[g], g, P.first, P.count, P.seed, 0, P.launchBlocks, ctx->launchLds, &statLog, sg));
         return enqueueCycleStart(ctx, P, S, g, initial, listIn, listLen);

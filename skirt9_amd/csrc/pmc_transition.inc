@@ -69,6 +69,28 @@
         }
     };
 
+    // Dipole phase function of Thomson scattering by free electrons, unpolarized (DipolePhaseFunction.cpp:47-59): its value for a
+    // scattering cosine, and the cosine that belongs to a uniform deviate X (the inverse of the cumulative distribution, a cubic).
+    // The operations are the reference's, in its order.
+    struct PhaseDipole
+    {
+        static __device__ __forceinline__ double value(double c) { return 0.75 * (c * c + 1.); }
+        static __device__ __forceinline__ double cosineFor(double X)
+        {
+            const double p = cbrt(4. * X - 2. + sqrt(16. * X * (X - 1.) + 5.));
+            return p - 1. / p;
+        }
+    };
+    // value of the phase function of medium component h (asymmetry parameter g where it is Henyey-Greenstein) for a scattering cosine
+    // (DustMix.cpp:430-445, DipolePhaseFunction.cpp:122-133).  DIPOLE: the kernel flavour of a scene in which some component has the
+    // dipole; the other flavour never looks at the kinds.
+    template<bool DIPOLE> __device__ __forceinline__ double phaseValue(const DevScene& S, int h, double g, double costheta)
+    {
+        if (DIPOLE && S.phase_kind[h] == PMC_PHASE_DIPOLE) return PhaseDipole::value(costheta);
+        const PhaseHG phase(g);
+        return fabs(g) > 0.95 ? phase.coneMean(costheta) : phase.value(costheta);
+    }
+
     // Direction(theta, phi) + Random::direction() (Direction.cpp:11-38, Random.cpp:121-126)
     __device__ __forceinline__ void randomDirection(Rng& rng, uint64_t seed, double& kx, double& ky, double& kz)
     {
@@ -640,11 +662,11 @@
         return (6. / 7.) * costheta * (2. * costheta + sign);
     }
     // weight factor of a scattering peel-off packet towards instrument I (DustMix.cpp:430-445, MediumSystem.cpp:734-767)
-    __device__ __forceinline__ double scatteringPeelFactor(double g, double kx, double ky, double kz, const DevInstrument& I)
+    template<bool DIPOLE>
+    __device__ __forceinline__ double scatteringPeelFactor(const DevScene& S, double g, double kx, double ky, double kz, const DevInstrument& I)
     {
         double costheta = kx * I.kx + ky * I.ky + kz * I.kz;
-        const PhaseHG phase(g);
-        double value = fabs(g) > 0.95 ? phase.coneMean(costheta) : phase.value(costheta);
+        double value = phaseValue<DIPOLE>(S, 0, g, costheta);
         return 0. + value * 1.;
     }
     // taumax of MediumSystem::getExtinctionOpticalDepth (MediumSystem.cpp:1195-1199); -inf flags a dead packet
@@ -928,6 +950,7 @@
     // Several medium components: `shares` holds every component's share of the scattering opacity in the interaction cell and
     // `asyms` its asymmetry parameter; the peel-off weight is the sum of the components' phase functions weighted by the shares
     // (MediumSystem::peelOffScattering, consolidated form, MediumSystem.cpp:734-767; components with share 0 are skipped).
+    template<bool DIPOLE = false>
     __device__ __forceinline__ void announceCycle(const DevScene& S, int slot, uint64_t seed, Rng& rng, double rx, double ry, double rz, double kinx,
                                                   double kiny, double kinz, double W, double asym, int pscatt, const double* shares = nullptr,
                                                   const double* asyms = nullptr, const DevSource* emitter = nullptr)
@@ -948,14 +971,13 @@
                 for (int h = 0; h < S.num_media; ++h)
                     if (shares[h] > 0.)
                     {
-                        const PhaseHG phase(asyms[h]);
-                        const double value = fabs(asyms[h]) > 0.95 ? phase.coneMean(costheta) : phase.value(costheta);
+                        const double value = phaseValue<DIPOLE>(S, h, asyms[h], costheta);
                         sum += value * shares[h];
                     }
                 pW = W * sum;
             }
             else if (pscatt != 0)
-                pW = W * scatteringPeelFactor(asym, kinx, kiny, kinz, I);
+                pW = W * scatteringPeelFactor<DIPOLE>(S, asym, kinx, kiny, kinz, I);
             else if (emitter)
                 pW = W * angularProbability(*emitter, I.kx, I.ky, I.kz);  // (an anisotropic point source: PhotonPacket::launchEmissionPeelOff)
             A.ppW[(int64_t)i * NS + slot] = pW;
@@ -1060,6 +1082,7 @@
     //      then the interaction the propagation walk found (MonteCarloSimulation.cpp:724-741 / 746-780): albedo and
     //      escape weights, termination test, scattering (DustMix::performScattering, HG), and the next cycle.
     //      All slot loads are issued as one batch first.
+    template<bool DIPOLE>
     __device__ __forceinline__ int onCycleDone(const DevScene& S, const DustLds& L, Counters& cnt, int slot, int modeWord, uint64_t seed, int group)
     {
         const SlotArrays& A = S.slots;
@@ -1152,6 +1175,7 @@
         double kxn, kyn, kzn;
         {
             double g = asym;
+            int scatterer = 0;
             if (multi)
             {
                 // the scattering component: ONE uniform deviate against the cumulative distribution of the components' scattering
@@ -1161,9 +1185,17 @@
                 for (int h = 0; h < S.num_media; ++h) X[h + 1] = X[h] + shares[h];
                 const double norm = X[S.num_media];
                 for (int h = 0; h <= S.num_media; ++h) X[h] /= norm;
-                g = asyms[locateClip(X, S.num_media + 1, rngUniform(rng, seed))];
+                scatterer = locateClip(X, S.num_media + 1, rngUniform(rng, seed));
+                g = asyms[scatterer];
             }
-            if (fabs(g) < 1e-6)
+            if (DIPOLE && S.phase_kind[scatterer] == PMC_PHASE_DIPOLE)
+            {
+                // DipolePhaseFunction::performScattering (DipolePhaseFunction.cpp:164-172): ONE uniform deviate for the cosine, then
+                // Random::direction(bfk, costheta) with one more
+                const double costheta = PhaseDipole::cosineFor(rngUniform(rng, seed));
+                directionAbout(rng, seed, kx, ky, kz, costheta, kxn, kyn, kzn);
+            }
+            else if (fabs(g) < 1e-6)
                 randomDirection(rng, seed, kxn, kyn, kzn);
             else
             {
@@ -1186,10 +1218,10 @@
             // (MediumSystem::weightsForScattering: no peel-off packets at all from a cell in which no component scatters)
             const bool some = ksca > 0.;
             for (int h = 0; h < S.num_media; ++h) shares[h] = some ? shares[h] / ksca : 0.;
-            announceCycle(S, slot, seed, rng, rx, ry, rz, kx, ky, kz, W, asym, nscatt + 1, shares, asyms);
+            announceCycle<DIPOLE>(S, slot, seed, rng, rx, ry, rz, kx, ky, kz, W, asym, nscatt + 1, shares, asyms);
         }
         else
-            announceCycle(S, slot, seed, rng, rx, ry, rz, kx, ky, kz, W, asym, nscatt + 1);
+            announceCycle<DIPOLE>(S, slot, seed, rng, rx, ry, rz, kx, ky, kz, W, asym, nscatt + 1);
         PMC_T_STAMP(6);
         storeRng(A, slot, rng);
         return EV_TASK;
@@ -1445,9 +1477,11 @@
     // ================================================================================================
     //  transition kernel: one lane per slot of the group [slotBase, slotBase + numSlots)
     // ================================================================================================
-    __global__ __launch_bounds__(PMC_TRANSITION_BLOCK, PMC_TRANSITION_MIN_WAVES) void transitionKernel(const int sceneSlot, const int slotBase, const int numSlots,
-                                                            const int group, const uint64_t seed, const int* const list, const int listLen,
-                                                            const StatLogArgs statLog)
+    //  DIPOLE: the flavour of a scene in which some medium component has the dipole phase function (transitionDipoleKernel); every other
+    //  scene runs transitionKernel, which holds no trace of it
+    template<bool DIPOLE>
+    __device__ __forceinline__ void transitionBody(const int sceneSlot, const int slotBase, const int numSlots, const int group, const uint64_t seed,
+                                                   const int* const list, const int listLen, const StatLogArgs& statLog)
     {
         const DevScene& S = c_scene[sceneSlot];
         extern __shared__ double lds[];
@@ -1532,7 +1566,7 @@
                     const int entry = myList[c + lane];
                     slot = entry & 0x3FFFFFFF;
                     sub = (int)((unsigned)entry >> 30);
-                    event = onCycleDone(S, L, cnt, slot, myMode[c + lane], seed, group);
+                    event = onCycleDone<DIPOLE>(S, L, cnt, slot, myMode[c + lane], seed, group);
                 }
                 PMC_T_STAMP(2);
                 if (list)
@@ -1571,6 +1605,18 @@
         PMC_T_STAMP(7);
         PMC_T_PROF_END(192);
         addCounters(S, cnt, lane);
+    }
+    __global__ __launch_bounds__(PMC_TRANSITION_BLOCK, PMC_TRANSITION_MIN_WAVES) void transitionKernel(const int sceneSlot, const int slotBase, const int numSlots,
+                                                            const int group, const uint64_t seed, const int* const list, const int listLen,
+                                                            const StatLogArgs statLog)
+    {
+        transitionBody<false>(sceneSlot, slotBase, numSlots, group, seed, list, listLen, statLog);
+    }
+    __global__ __launch_bounds__(PMC_TRANSITION_BLOCK, PMC_TRANSITION_MIN_WAVES) void transitionDipoleKernel(const int sceneSlot, const int slotBase,
+                                                            const int numSlots, const int group, const uint64_t seed, const int* const list,
+                                                            const int listLen, const StatLogArgs statLog)
+    {
+        transitionBody<true>(sceneSlot, slotBase, numSlots, group, seed, list, listLen, statLog);
     }
 
     // ================================================================================================

@@ -47,3 +47,19 @@ extern "C" void pmc_tuning_clear(void)
     std::lock_guard<std::mutex> lock(g_tuneMutex);
     tuneTable().clear();
 }
+
+extern "C" int pmc_tune_dipole_cosines(pmc_ctx* ctx, const double* u, int64_t n, double* cos_out)
+{
+    if (!ctx || n < 0 || (n > 0 && (!u || !cos_out))) return fail(PMC_ERR_INVALID, "pmc_tune_dipole_cosines: invalid argument");
+    if (n == 0) return PMC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    double* d = nullptr;
+    HIP_TRY(hipMalloc(&d, sizeof(double) * size_t(2 * n)));
+    hipError_t e = hipMemcpyAsync(d, u, sizeof(double) * size_t(n), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = pmcLaunchDipoleCosines(d, n, d + n, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cos_out, d + n, sizeof(double) * size_t(n), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    hipFree(d);
+    if (e != hipSuccess) return hipFail(e, "pmc_tune_dipole_cosines");
+    return PMC_OK;
+}

@@ -10,19 +10,19 @@ import os
 
 import numpy as np
 
-from .host import CounterValues, FrameLayout
+from .host import CounterValues, FrameLayout, SceneExt
 
 _LIBDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 
 # every symbol include/pmc.h and include/pmc_tuning.h declare
-SYMBOLS = ["pmc_abi_version", "pmc_build_info", "pmc_last_error", "pmc_frame_layout_of", "pmc_create", "pmc_destroy", "pmc_bind_frames",
+SYMBOLS = ["pmc_abi_version", "pmc_build_info", "pmc_last_error", "pmc_frame_layout_of", "pmc_create", "pmc_create_ext", "pmc_destroy", "pmc_bind_frames",
            "pmc_clear_frames", "pmc_run_primary", "pmc_set_progress", "pmc_sync", "pmc_download", "pmc_frames_device", "pmc_frames_size",
            "pmc_last_kernel_ms", "pmc_counters", "pmc_reset_counters", "pmc_trace_ray", "pmc_set_launch",
            "pmc_set_num_slots", "pmc_last_timing", "pmc_last_walk_timing", "pmc_walk_work", "pmc_radiation_field_size", "pmc_radiation_field_device",
            "pmc_download_radiation_field", "pmc_clear_radiation_field", "pmc_bind_radiation_field", "pmc_sampler_create",
            "pmc_sampler_density", "pmc_sampler_destroy", "pmc_history_range", "pmc_comm_init_all", "pmc_comm_unique_id",
            "pmc_comm_init_rank", "pmc_comm_size", "pmc_comm_destroy", "pmc_reduce_frames", "pmc_allreduce_radiation_field",
-           "pmc_debug_tables", "pmc_tuning_set", "pmc_tuning_clear"]
+           "pmc_debug_tables", "pmc_tuning_set", "pmc_tuning_clear", "pmc_tune_dipole_cosines"]
 
 _lib = None
 
@@ -52,6 +52,9 @@ def lib():
         L.pmc_frame_layout_of.restype = C.c_int64
         L.pmc_frame_layout_of.argtypes = [C.c_void_p, C.c_int32, C.POINTER(FrameLayout)]
         L.pmc_create.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+        if hasattr(L, "pmc_create_ext"):  # (absent from engines built from an older commit and loaded through PMC_LIBRARY)
+            L.pmc_create_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+            L.pmc_tune_dipole_cosines.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.pmc_destroy.argtypes = [C.c_void_p]
         L.pmc_bind_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.pmc_clear_frames.argtypes = [C.c_void_p]
@@ -186,9 +189,18 @@ class Engine:
     """One engine context on one MI355X: device copies of a scene plus the detector arrays."""
 
     def __init__(self, scene_ptr, device=0):
-        """scene_ptr: address of a pmc_scene (e.g. ``skirt9_amd.host.Simulation.scene``)"""
+        """scene_ptr: address of a pmc_scene (e.g. ``skirt9_amd.host.Simulation.scene``, which carries the address of the scene's
+        extension along: ``skirt9_amd.host.ScenePointer``; a plain int means no extension)"""
         self._h = C.c_void_p()
-        _check(lib().pmc_create(scene_ptr, device, C.byref(self._h)))
+        L = lib()
+        ext = getattr(scene_ptr, "ext", None)
+        if hasattr(L, "pmc_create_ext"):
+            _check(L.pmc_create_ext(int(scene_ptr), ext, device, C.byref(self._h)))
+        else:
+            # (an engine from before the extension knows Henyey-Greenstein only: another phase function must not run as that)
+            if ext and any(SceneExt.from_address(ext).phase_function):
+                raise RuntimeError("this libpmc.so has no pmc_create_ext: it cannot run a scene with a dipole component")
+            _check(L.pmc_create(int(scene_ptr), device, C.byref(self._h)))
         self.device = device
 
     def close(self):
@@ -312,6 +324,13 @@ class Engine:
 
     def reset_counters(self):
         _check(lib().pmc_reset_counters(self._h))
+
+    def dipole_cosines(self, u):
+        """test aid (pmc_tune_dipole_cosines): the scattering cosines that the transition kernel's dipole sampler makes of the uniform deviates u"""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        out = np.empty_like(u)
+        _check(lib().pmc_tune_dipole_cosines(self._h, u.ctypes.data_as(C.c_void_p), u.size, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def trace_ray(self, r, k, cap=4096):
         r = np.ascontiguousarray(r, dtype=np.float64)

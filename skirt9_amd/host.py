@@ -32,6 +32,17 @@ class CounterValues(C.Structure):
 _lib = None
 
 
+class ScenePointer(int):
+    """address of a pmc_scene; ``ext`` is the address of the pmc_scene_ext that belongs to it (the phase function of every medium
+    component), which ``skirt9_amd.engine.Engine`` hands to pmc_create_ext.  A plain int in its place means: no extension."""
+    ext = None
+
+    def __new__(cls, scene, ext):
+        self = super().__new__(cls, scene)
+        self.ext = ext
+        return self
+
+
 # ---- ctypes mirrors of the leading members of pmc_scene (include/pmc.h): inspection of the tables a Simulation hands over
 
 class Grid(C.Structure):
@@ -51,6 +62,11 @@ class Medium(C.Structure):
                 ("lambda_border", C.POINTER(C.c_double)), ("sigma_ext", C.POINTER(C.c_double)),
                 ("sigma_sca", C.POINTER(C.c_double)), ("asymmpar", C.POINTER(C.c_double)),
                 ("sigma_abs", C.POINTER(C.c_double))]
+
+
+class SceneExt(C.Structure):
+    """pmc_scene_ext (include/pmc.h)"""
+    _fields_ = [("struct_size", C.c_int32), ("phase_function", C.c_int32 * 4)]
 
 
 class SceneHead(C.Structure):
@@ -79,6 +95,8 @@ def lib():
         L.skh_setup.argtypes = [C.c_void_p]
         L.skh_scene.restype = C.c_void_p
         L.skh_scene.argtypes = [C.c_void_p]
+        L.skh_scene_ext.restype = C.c_void_p
+        L.skh_scene_ext.argtypes = [C.c_void_p]
         L.skh_num_packets.restype = C.c_uint64
         L.skh_num_packets.argtypes = [C.c_void_p]
         L.skh_seed.restype = C.c_int32
@@ -102,6 +120,8 @@ def lib():
         L.skh_scene_file_free.argtypes = [C.c_void_p]
         L.skh_scene_file_scene.restype = C.c_void_p
         L.skh_scene_file_scene.argtypes = [C.c_void_p]
+        L.skh_scene_file_scene_ext.restype = C.c_void_p
+        L.skh_scene_file_scene_ext.argtypes = [C.c_void_p]
         L.skh_scene_file_number.restype = C.c_int64
         L.skh_scene_file_number.argtypes = [C.c_void_p, C.c_int32]
         L.skh_scene_file_layout.argtypes = [C.c_void_p, C.c_int32, C.POINTER(FrameLayout)]
@@ -155,9 +175,15 @@ class Simulation:
 
     @property
     def scene(self):
-        """address of the pmc_scene (valid while this object lives)"""
+        """address of the pmc_scene, with that of its extension (valid while this object lives)"""
         assert self._setup, "call setup() first"
-        return lib().skh_scene(self._h)
+        return ScenePointer(lib().skh_scene(self._h), lib().skh_scene_ext(self._h))
+
+    @property
+    def phase_functions(self):
+        """PMC_PHASE_* of every medium component slot (pmc_scene_ext::phase_function)"""
+        assert self._setup, "call setup() first"
+        return list(SceneExt.from_address(lib().skh_scene_ext(self._h)).phase_function)
 
     @property
     def num_packets(self):
@@ -249,7 +275,11 @@ class SceneFile:
 
     @property
     def scene(self):
-        return lib().skh_scene_file_scene(self._f)
+        return ScenePointer(lib().skh_scene_file_scene(self._f), lib().skh_scene_file_scene_ext(self._f))
+
+    @property
+    def phase_functions(self):
+        return list(SceneExt.from_address(lib().skh_scene_file_scene_ext(self._f)).phase_function)
 
     def _number(self, what):
         return int(lib().skh_scene_file_number(self._f, what))

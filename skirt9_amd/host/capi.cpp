@@ -132,6 +132,11 @@ const pmc_scene* skh_scene(const skh_simulation* h)
     return &h->sim->scene();
 }
 
+const pmc_scene_ext* skh_scene_ext(const skh_simulation* h)
+{
+    return &h->sim->sceneExt();
+}
+
 uint64_t skh_num_packets(const skh_simulation* h)
 {
     return h->sim->numPackets();

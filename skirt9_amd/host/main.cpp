@@ -139,7 +139,7 @@ int main(int argc, char** argv)
     };
     auto work = [&](int g) {
         auto failed = [&]() { errors[g] = pmc_last_error(); };
-        bool ok = pmc_create(skh_scene(sim), devices[g], &ctxs[g]) == PMC_OK;
+        bool ok = pmc_create_ext(skh_scene(sim), skh_scene_ext(sim), devices[g], &ctxs[g]) == PMC_OK;
         if (ok)
         {
             // (the first device reports for all: MonteCarloSimulation::logProgress / Log::infoIfElapsed, every 3 s)

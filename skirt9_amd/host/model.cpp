@@ -567,6 +567,18 @@ namespace skh
         }
     }
 
+    // ================================================================ ElectronMix (ElectronMix.cpp:99-146)
+
+    void ElectronMix::setup(double rangeMin, double rangeMax, const std::vector<double>&)
+    {
+        lambdaSample = {rangeMin, rangeMax};
+        lambdaBorder = {rangeMin, rangeMax};
+        sigmaAbs = {0., 0.};
+        sigmaSca = {constants::sigmaThomson, constants::sigmaThomson};
+        sigmaExt = sigmaSca;
+        asymmpar = {0., 0.};
+    }
+
     // ================================================================ GeometricMedium
 
     void GeometricMedium::setup()
@@ -811,12 +823,23 @@ namespace skh
     // consumed in node order
     void OctreeSpatialGrid::setup(const Medium& medium, int numDensitySamples, Random& random)
     {
-        bool hasDustFraction = maxDustFraction > 0;
-        bool hasDustOpticalDepth = maxDustOpticalDepth > 0;
-        bool hasDustDensityDispersion = maxDustDensityDispersion > 0;
+        // (a medium system with electron components comes as a CompositeMedium: its Medium interface is the dust, DensityTreePolicy.cpp:35-43)
+        const CompositeMedium* all = dynamic_cast<const CompositeMedium*>(&medium);
+        const bool hasDust = !all || !all->parts.empty();
+        bool hasDustFraction = hasDust && maxDustFraction > 0;
+        bool hasDustOpticalDepth = hasDust && maxDustOpticalDepth > 0;
+        bool hasDustDensityDispersion = hasDust && maxDustDensityDispersion > 0;
         double dustMass = hasDustFraction ? medium.totalMass() : 0.;
         double dustKappa = 0.;
         if (hasDustOpticalDepth) dustKappa = medium.dustKappa(policyWavelength);
+        // the electron criterion (DensityTreePolicy.cpp:87-94): the number of electrons in a node over that of all electron components
+        const bool hasElectronFraction = all && !all->electrons.empty() && maxElectronFraction > 0;
+        double electronNumber = 0.;
+        if (hasElectronFraction)
+            for (const Medium* part : all->electrons) electronNumber += part->totalNumber();
+        // (no criterion that needs samples: no position is drawn, DensityTreePolicy.cpp:130)
+        const bool needSamples = hasDust || hasElectronFraction;
+        std::vector<std::vector<double>> electronSamples(hasElectronFraction ? all->electrons.size() : 0);
 
         nodes.clear();
         Node root;
@@ -840,10 +863,14 @@ namespace skh
                 for (size_t l = b0; l != b1; ++l)
                 {
                     const Node& node = nodes[levelFirst + l];
-                    if (node.level >= minLevel && node.level < maxLevel)
+                    if (needSamples && node.level >= minLevel && node.level < maxLevel)
                         for (int i = 0; i != numDensitySamples; ++i) pos.push_back(random.position(node.box));
                 }
-                medium.massDensities(pos, sampleDensities);
+                if (hasDust)
+                    medium.massDensities(pos, sampleDensities);
+                else
+                    sampleDensities.assign(pos.size(), 0.);
+                for (size_t e = 0; e != electronSamples.size(); ++e) all->electrons[e]->numberDensities(pos, electronSamples[e]);
                 size_t at = 0;
                 for (size_t l = b0; l != b1; ++l)
                 {
@@ -855,9 +882,10 @@ namespace skh
                         need = false;
                     else
                     {
-                        double lowest = DBL_MAX, highest = 0., sampleSum = 0;
-                        for (int i = 0; i != numDensitySamples; ++i)
+                        double lowest = DBL_MAX, highest = 0., sampleSum = 0, electronSum = 0;
+                        for (int i = 0; needSamples && i != numDensitySamples; ++i)
                         {
+                            for (const auto& samples : electronSamples) electronSum += samples[at];
                             double sampled = 0.;
                             sampled += sampleDensities[at++];
                             sampleSum += sampled;
@@ -874,6 +902,7 @@ namespace skh
                             const double contrast = highest > 0 ? (highest - lowest) / highest : 0.;
                             if (contrast > maxDustDensityDispersion) need = true;
                         }
+                        if (!need && hasElectronFraction && electronSum / numDensitySamples * V / electronNumber > maxElectronFraction) need = true;
                     }
                     divide[l] = need;
                 }

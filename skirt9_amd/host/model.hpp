@@ -9,6 +9,7 @@
 #include "../../include/pmc.h"
 #include "mathutil.hpp"
 #include "particles.hpp"
+#include "units.hpp"
 #include "voronoi.hpp"
 #include "xml.hpp"
 #include <memory>
@@ -272,26 +273,55 @@ namespace skh
         Array tableR_, tableCdf_;
     };
 
-    // ---------------------------------------------------------------- dust mix (tabulated mean properties)
+    // ---------------------------------------------------------------- material mixes
 
-    // DustMix tables for a TabulatedDustMix subclass (MeanListDustMix / MeanFileDustMix):
-    // SKIRT/core/DustMix.cpp:47-162, TabulatedDustMix.cpp:12-45, MeanListDustMix.cpp:12-27
-    class DustMix
+    // What the medium system and the engine ask of a material (SKIRT/core/MaterialMix.hpp), for materials with spatially
+    // constant cross sections: the entity mass and, built by setup(), cross sections tabulated on index borders as pmc_medium
+    // takes them (include/pmc.h), together with the kind of scattering phase function
+    class MaterialMix
     {
     public:
+        virtual ~MaterialMix() {}
         std::string typeName;
-        Array inLambda, inKappaExt, inAlbedo, inAsymmpar;  // as configured
-        double mu{1.5e-29};
         // built by setup()
         Array lambdaSample;  // sampling wavelengths (DustMix.cpp local lambdav)
         Array lambdaBorder;  // DustMix::_lambdav (shifted borders used by indexForLambda)
         Array sigmaAbs, sigmaSca, sigmaExt, asymmpar;
 
-        void setup(double rangeMin, double rangeMax, const std::vector<double>& simulationWavelengths);
+        virtual void setup(double rangeMin, double rangeMax, const std::vector<double>& simulationWavelengths) = 0;
+        virtual double mass() const = 0;
+        // MaterialMix::materialType() == Electrons: counted by the electron criterion of the tree policy, not by the dust criteria
+        virtual bool isElectrons() const { return false; }
+        // PMC_PHASE_* of include/pmc.h
+        virtual int32_t phaseFunction() const { return PMC_PHASE_HG; }
         int indexForLambda(double lambda) const { return tab::bracketClipped(lambdaBorder, lambda); }
         double sectionExt(double lambda) const { return sigmaExt[indexForLambda(lambda)]; }
         double sectionSca(double lambda) const { return sigmaSca[indexForLambda(lambda)]; }
-        double mass() const { return mu; }
+    };
+
+    // DustMix tables for a TabulatedDustMix subclass (MeanListDustMix / MeanFileDustMix):
+    // SKIRT/core/DustMix.cpp:47-162, TabulatedDustMix.cpp:12-45, MeanListDustMix.cpp:12-27
+    class DustMix : public MaterialMix
+    {
+    public:
+        Array inLambda, inKappaExt, inAlbedo, inAsymmpar;  // as configured
+        double mu{1.5e-29};
+
+        void setup(double rangeMin, double rangeMax, const std::vector<double>& simulationWavelengths) override;
+        double mass() const override { return mu; }
+    };
+
+    // ElectronMix without polarization and without thermal dispersion, above the Compton limit (SKIRT/core/ElectronMix.cpp:99-146):
+    // Thomson scattering with the dipole phase function -- the Thomson cross section at every wavelength, no absorption.  The
+    // tables are constant over two borders that span the simulation's wavelength range.
+    class ElectronMix : public MaterialMix
+    {
+    public:
+        static constexpr double comptonWavelength = 9.999999e-9;  // ElectronMix.cpp:19: below it the reference switches to Compton scattering
+        void setup(double rangeMin, double rangeMax, const std::vector<double>& simulationWavelengths) override;
+        double mass() const override { return constants::Melectron; }
+        bool isElectrons() const override { return true; }
+        int32_t phaseFunction() const override { return PMC_PHASE_DIPOLE; }
     };
 
     // ---------------------------------------------------------------- medium
@@ -301,7 +331,7 @@ namespace skh
     {
     public:
         virtual ~Medium() {}
-        std::unique_ptr<DustMix> mix;
+        std::unique_ptr<MaterialMix> mix;
         virtual std::string type() const = 0;
         virtual void setup() = 0;
         virtual double numberDensity(Vec3 r) const = 0;
@@ -332,14 +362,17 @@ namespace skh
         virtual double dustKappa(double lambda) const { return mix->sectionExt(lambda) / mix->mass(); }
     };
 
-    // Several medium components seen as ONE dust distribution by the setup of the spatial grid: DensityTreePolicy sums the mass
-    // densities of all dust media at a sample position (DensityTreePolicy.cpp:141), their masses (:72) and, for the optical depth
-    // criterion, their cross sections and entity masses (:78-83).  The photon loop never sees this object: every component keeps
-    // its own cell densities and material mix (MediumSystem.cpp:874-887).
+    // Several medium components as the setup of the spatial grid sees them.  The DUST components are one dust distribution:
+    // DensityTreePolicy sums the mass densities of all dust media at a sample position (DensityTreePolicy.cpp:141), their masses
+    // (:72) and, for the optical depth criterion, their cross sections and entity masses (:78-83); this is what the Medium
+    // interface of this object answers.  The ELECTRON components are kept apart: the policy sums their number densities at the
+    // same sample positions for its electron criterion (:87-94, 146-147, 211-216).  The photon loop never sees this object: every
+    // component keeps its own cell densities and material mix (MediumSystem.cpp:874-887).
     class CompositeMedium : public Medium
     {
     public:
-        std::vector<Medium*> parts;
+        std::vector<Medium*> parts;      // the dust components
+        std::vector<Medium*> electrons;  // the electron components
         std::string type() const override { return "media"; }
         void setup() override {}
         double numberDensity(Vec3) const override { throw std::runtime_error("number density of a composite medium"); }
@@ -507,6 +540,7 @@ namespace skh
         // policy configuration
         int minLevel{3}, maxLevel{7};
         double maxDustFraction{1e-6}, maxDustOpticalDepth{0}, policyWavelength{0.55e-6}, maxDustDensityDispersion{0};
+        double maxElectronFraction{1e-6};
 
         struct Node
         {

@@ -1,5 +1,5 @@
-// scenefile.cpp -- a set-up scene as ONE file: everything pmc_create reads (include/pmc.h pmc_scene: grid, densities, dust tables,
-// sources, instruments) plus the few numbers a driver of the photon loop needs (seed, packets of the segment, frame layout).
+// scenefile.cpp -- a set-up scene as ONE file: everything pmc_create_ext reads (include/pmc.h pmc_scene: grid, densities, dust tables,
+// sources, instruments; pmc_scene_ext: the components' phase functions) plus the few numbers a driver of the photon loop needs (seed, packets of the segment, frame layout).
 //
 // In a job of one process per GPU every process needs the same scene.  The reference repeats the whole setup in every MPI
 // process (Simulation::setupSimulation runs everywhere; only the photon packets are distributed, SKIRT/mpi/ProcessManager.cpp).
@@ -29,7 +29,9 @@ namespace
         int32_t abi, seed;
         uint64_t num_packets, setup_draws;
         int64_t frame_size, rf_size;
-        int32_t num_instruments, pad;
+        int32_t num_instruments;
+        uint32_t phase_kinds;  // pmc_scene_ext::phase_function, one byte per medium component (component h: bits 8 h .. 8 h + 7); a file written
+                               // before scenes had an extension holds 0 here (the member was padding): every component Henyey-Greenstein
         uint64_t scene_offset, layout_offset, total_bytes;
         uint32_t sizeof_scene, sizeof_instrument, sizeof_source, sizeof_layout;
         uint64_t checksum;  // FNV-1a (64 bit) of the bytes behind the header
@@ -137,6 +139,7 @@ struct skh_scene_file
     const Header* header{nullptr};
     const pmc_scene* scene{nullptr};
     const pmc_frame_layout* layouts{nullptr};
+    pmc_scene_ext ext{};
 };
 
 extern "C" {
@@ -193,6 +196,13 @@ int skh_scene_save(const skh_simulation* h, const char* path)
         head.frame_size = skh_frame_size(h);
         head.rf_size = skh_radiation_field_size(h);
         head.num_instruments = live.num_instruments;
+        static_assert(PMC_MAX_MEDIA <= 4, "one byte per component in Header::phase_kinds");
+        const pmc_scene_ext& ext = *skh_scene_ext(h);
+        for (int c = 0; c < PMC_MAX_MEDIA; ++c)
+        {
+            if (ext.phase_function[c] < 0 || ext.phase_function[c] > 255) throw std::runtime_error("skh_scene_save: phase function kind out of range");
+            head.phase_kinds |= uint32_t(ext.phase_function[c]) << (8 * c);
+        }
         head.scene_offset = sceneAt;
         head.layout_offset = layoutAt;
         head.total_bytes = S.blob.size();
@@ -262,6 +272,8 @@ skh_scene_file* skh_scene_load(const char* path)
             member = reinterpret_cast<P>(base + off);
         });
         file->header = head;
+        file->ext.struct_size = int32_t(sizeof(pmc_scene_ext));
+        for (int c = 0; c < PMC_MAX_MEDIA; ++c) file->ext.phase_function[c] = int32_t((head->phase_kinds >> (8 * c)) & 0xFFu);
         file->scene = &scene;
         file->layouts = reinterpret_cast<const pmc_frame_layout*>(base + head->layout_offset);
         return file.release();
@@ -281,6 +293,11 @@ void skh_scene_file_free(skh_scene_file* file)
 const pmc_scene* skh_scene_file_scene(const skh_scene_file* file)
 {
     return file ? file->scene : nullptr;
+}
+
+const pmc_scene_ext* skh_scene_file_scene_ext(const skh_scene_file* file)
+{
+    return file ? &file->ext : nullptr;
 }
 
 int64_t skh_scene_file_number(const skh_scene_file* file, int32_t what)

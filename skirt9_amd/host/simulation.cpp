@@ -460,17 +460,34 @@ namespace skh
             unsupported("a medium with a magnetic field");
         const XmlElement* mm = med.item("materialMix");
         if (!mm) throw std::runtime_error("ski: " + med.name + " lacks a material mix");
-        if (mm->name != "MeanListDustMix" && mm->name != "MeanFileDustMix") unsupported("material mix " + mm->name);
-        auto mix = std::make_unique<DustMix>();
-        mix->typeName = mm->name;
-        if (mm->name == "MeanListDustMix")
+        if (mm->name != "MeanListDustMix" && mm->name != "MeanFileDustMix" && mm->name != "ElectronMix") unsupported("material mix " + mm->name);
+        std::unique_ptr<MaterialMix> material;
+        DustMix* mix = nullptr;  // (the tabulated dust mix being read, if the material is one)
+        if (mm->name == "ElectronMix")
+        {
+            // ElectronMix.cpp:24-37, 55-70: unpolarized Thomson scattering only.  Thermal dispersion is ignored by the reference in an
+            // oligochromatic simulation (:29), and so it is here; the Compton regime is refused once the wavelength range is known (setup)
+            if (rd.boolean(*mm, "includePolarization", false)) unsupported("ElectronMix with includePolarization");
+            if (rd.boolean(*mm, "includeThermalDispersion", false) && !_oligo)
+                unsupported("ElectronMix with includeThermalDispersion in a panchromatic simulation");
+            if (med.name != "GeometricMedium") unsupported("ElectronMix in a " + med.name);
+            material = std::make_unique<ElectronMix>();
+            material->typeName = mm->name;
+        }
+        else
+        {
+            material = std::make_unique<DustMix>();
+            mix = static_cast<DustMix*>(material.get());
+            mix->typeName = mm->name;
+        }
+        if (mix && mm->name == "MeanListDustMix")
         {
             mix->inLambda = rd.list(*mm, "wavelengths", "wavelength", "");
             mix->inKappaExt = rd.list(*mm, "extinctionCoefficients", "masscoefficient", "");
             mix->inAlbedo = rd.list(*mm, "albedos", "", "");
             mix->inAsymmpar = rd.list(*mm, "asymmetryParameters", "", "");
         }
-        else
+        else if (mix)
         {
             // MeanFileDustMix.cpp:11-22: four columns of a text file (wavelength, kappa_ext, albedo, g)
             std::string filename = mm->attr("filename", "");
@@ -534,11 +551,16 @@ namespace skh
             if (const XmlElement* sk = med.item("smoothingKernel")) pm->kernelType = sk->name;
             one = std::move(pm);
         }
-        one->mix = std::move(mix);
+        one->mix = std::move(material);
         _media.push_back(std::move(one));
         }  // media
-        for (auto& part : _media) _composite.parts.push_back(part.get());
-        _medium = _media.size() == 1 ? _media[0].get() : &_composite;
+        bool anyElectrons = false;
+        for (auto& part : _media)
+        {
+            (part->mix->isElectrons() ? _composite.electrons : _composite.parts).push_back(part.get());
+            anyElectrons |= part->mix->isElectrons();
+        }
+        _medium = _media.size() == 1 && !anyElectrons ? _media[0].get() : &_composite;
 
         const XmlElement* ge = ms->item("grid");
         if (!ge) throw std::runtime_error("ski: MediumSystem lacks a spatial grid");
@@ -604,6 +626,7 @@ namespace skh
                 grid->maxDustOpticalDepth = rd.number(*pol, "maxDustOpticalDepth", "0");
                 grid->policyWavelength = rd.quantity(*pol, "wavelength", "wavelength", "0.55 micron");
                 grid->maxDustDensityDispersion = rd.number(*pol, "maxDustDensityDispersion", "0");
+                grid->maxElectronFraction = rd.number(*pol, "maxElectronFraction", "1e-6");
             }
             _grid = std::move(grid);
         }
@@ -763,9 +786,12 @@ namespace skh
         rangeMin /= (1. + 1. / 100.);  // Range::extendWithRedshift
         rangeMax *= (1. + 1. / 100.);
 
-        // ---- dust mix, medium normalisation
+        // ---- material mixes, medium normalisation
         for (auto& part : _media)
         {
+            // (ElectronMix.cpp:36, 116: below the Compton limit the cross section and the phase function are Compton's)
+            if (part->mix->isElectrons() && rangeMin < ElectronMix::comptonWavelength)
+                unsupported("ElectronMix with a source or instrument wavelength below 10 nm (Compton scattering)");
             part->mix->setup(rangeMin, rangeMax, std::vector<double>(simWavelengths.begin(), simWavelengths.end()));
             if (auto pm = dynamic_cast<ParticleMedium*>(part.get())) pm->snapshot.useDeviceSampler(_samplerApi);
             part->setup();
@@ -1068,7 +1094,7 @@ namespace skh
         for (size_t h = 0; h != _media.size(); ++h)
         {
             pmc_medium& m = _sceneMedia[h];
-            const DustMix& mix = *_media[h]->mix;
+            const MaterialMix& mix = *_media[h]->mix;
             m.number_density = _density[h].data();
             m.num_lambda = static_cast<int32_t>(mix.lambdaBorder.size());
             m.lambda_border = mix.lambdaBorder.data();
@@ -1080,6 +1106,9 @@ namespace skh
         _scene.medium = _sceneMedia[0];
         _scene.num_media = static_cast<int32_t>(_media.size());
         _scene.media = _media.size() > 1 ? _sceneMedia.data() : nullptr;
+        _sceneExt = pmc_scene_ext{};
+        _sceneExt.struct_size = static_cast<int32_t>(sizeof(pmc_scene_ext));
+        for (size_t h = 0; h != _media.size(); ++h) _sceneExt.phase_function[h] = _media[h]->mix->phaseFunction();
 
         _scene.options = _options;
 

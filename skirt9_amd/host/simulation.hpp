@@ -25,6 +25,8 @@ namespace skh
         void setup();
 
         const pmc_scene& scene() const { return _scene; }
+        // what the scene's layout has no room for (pmc_create_ext): the phase function of every medium component
+        const pmc_scene_ext& sceneExt() const { return _sceneExt; }
         uint64_t numPackets() const { return _numPackets; }
         int seed() const { return _seed; }
         // number of uniform deviates drawn from the parent stream during setup (the photon loop of the
@@ -91,8 +93,8 @@ namespace skh
         bool _hasMedium{true};                              // Configuration::hasMedium(): false in the NoMedium simulation modes
         std::unique_ptr<XmlElement> _standInMediumSystem;   // (those modes: the empty one-cell medium system the engine runs with)
         std::vector<std::unique_ptr<Medium>> _media;   // the medium components, in ski order (MediumSystem::_media)
-        CompositeMedium _composite;                    // all of them as one dust distribution (grid setup)
-        Medium* _medium{nullptr};                      // the only component, or the composite
+        CompositeMedium _composite;                    // all of them as the grid setup sees them: one dust distribution, the electrons apart
+        Medium* _medium{nullptr};                      // the only component if it is dust, or the composite
         std::unique_ptr<SpatialGrid> _grid;
         std::vector<char> _topology;
         std::vector<Array> _density;                   // [component][cell] number densities
@@ -120,6 +122,7 @@ namespace skh
         std::vector<pmc_frame_layout> _layouts;
         int64_t _frameSize{0};
         pmc_scene _scene{};
+        pmc_scene_ext _sceneExt{};
     };
 
     // FITS primary image (BITPIX -32) + ASCII table of the third axis, byte-compatible with what the reference

@@ -26,6 +26,8 @@ namespace skh
         constexpr double Msun = 1.9891e30;
         constexpr double Lsun = 3.839e26;
         constexpr double Qelectron = 1.602176634e-19;
+        constexpr double Melectron = 9.10938215e-31;
+        constexpr double sigmaThomson = 6.6524587158e-29;
         constexpr double year = 31557600.;
     }
 
