@@ -275,10 +275,34 @@ typedef struct pmc_scene
    holds ordinary tables -- sigma_sca = sigma_ext = the Thomson cross section, sigma_abs = 0, asymmpar = 0 (not read) -- with borders that span
    the simulation's wavelength range. */
 enum { PMC_PHASE_HG = 0, PMC_PHASE_DIPOLE = 1 };
+/* source_velocity[i]: the bulk velocity of source i (the only source: i = 0) in a panchromatic simulation, which Doppler-shifts what it emits
+   (PhotonPacket.cpp:18-40, 66-85: a packet launched into direction k has wavelength lambda0 (1 - k.v/c), the emission peel-off packet towards an
+   observer its own).  The velocity at launch position r is  magnitude * field(r)  (GeometricSource.cpp:66-82; evaluating it draws no random number):
+     PMC_VELOCITY_NONE         the source is at rest
+     PMC_VELOCITY_CONSTANT     field = vector: the unit vector of a UnidirectionalVectorField; or, with magnitude 1, the velocity of a PointSource
+                               itself (SpecialtySource.cpp:34-50)
+     PMC_VELOCITY_RADIAL       RadialVectorField.cpp:17-35 about the point `vector` (an OffsetVectorFieldDecorator; zeros: the origin): the unit vector
+                               away from it, times (r/unity_radius)^exponent where unity_radius > 0 and (exponent > 0 and r < unity_radius, or exponent < 0
+                               and r > unity_radius); the null vector at the point itself
+     PMC_VELOCITY_CYLINDRICAL  CylindricalVectorField.cpp:17-36 likewise: the unit vector of rotation about the z-axis through `vector`, with the
+                               distance R to that axis; the null vector on the axis
+   A scene with a moving source has ONE medium component, at rest, and stores no radiation field: pmc_create_ext refuses the others, and an
+   unknown kind, with PMC_ERR_UNSUPPORTED.  A shorter pmc_scene_ext of an older caller has no velocities: every source is at rest. */
+enum { PMC_VELOCITY_NONE = 0, PMC_VELOCITY_CONSTANT = 1, PMC_VELOCITY_RADIAL = 2, PMC_VELOCITY_CYLINDRICAL = 3 };
+#define PMC_EXT_MAX_SOURCES 16
+typedef struct pmc_source_velocity
+{
+    int32_t kind;          /* PMC_VELOCITY_* */
+    double  magnitude;     /* m/s */
+    double  vector[3];     /* CONSTANT: the field's vector; RADIAL, CYLINDRICAL: the offset of the field's centre (m) */
+    double  unity_radius;  /* m; 0: magnitude 1 everywhere */
+    double  exponent;
+} pmc_source_velocity;
 typedef struct pmc_scene_ext
 {
     int32_t struct_size;
     int32_t phase_function[PMC_MAX_MEDIA];
+    pmc_source_velocity source_velocity[PMC_EXT_MAX_SOURCES];
 } pmc_scene_ext;
 
 /* counted work, accumulated over all pmc_run_primary calls since create/reset (roofline inputs) */
@@ -309,7 +333,8 @@ int64_t pmc_frame_layout_of(const pmc_scene* scene, int32_t instrument, pmc_fram
 /* --- device API */
 int pmc_create(const pmc_scene* scene, int32_t device, pmc_ctx** out);
 /* pmc_create with the scene's extension; ext == NULL: every component is Henyey-Greenstein (what pmc_create does).  An unknown phase function
-   kind fails with PMC_ERR_UNSUPPORTED. */
+   kind fails with PMC_ERR_UNSUPPORTED, and so do an unknown velocity kind and a moving source next to several medium components or a stored
+   radiation field. */
 int pmc_create_ext(const pmc_scene* scene, const pmc_scene_ext* ext, int32_t device, pmc_ctx** out);
 void pmc_destroy(pmc_ctx* ctx);
 /* Use caller-owned DEVICE memory (num_doubles f64, zero-initialised by the caller) for the frames instead of the

@@ -56,6 +56,11 @@ int pmc_debug_tables(pmc_ctx* ctx, pmc_debug_table_values* out);
    function (DipolePhaseFunction::generateCosineFromPhaseFunction), run over n host-supplied deviates u; cos_out: n doubles on the host. */
 int pmc_tune_dipole_cosines(pmc_ctx* ctx, const double* u, int64_t n, double* cos_out);
 
+/* Test aid: the device function with which the launch kernel evaluates the bulk velocity of source `source` (pmc_scene_ext::source_velocity;
+   GeometricSource.cpp:66-82 with the vector fields) at n host-supplied launch positions r[n][3] (m); v_out: n x 3 doubles on the host (m/s).  A
+   source at rest gives zeros. */
+int pmc_tune_source_velocities(pmc_ctx* ctx, int32_t source, const double* r, int64_t n, double* v_out);
+
 #ifdef __cplusplus
 }
 #endif

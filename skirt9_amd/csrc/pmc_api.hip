@@ -139,6 +139,32 @@ int pmc_create_ext(const pmc_scene* scene, const pmc_scene_ext* ext, int32_t dev
                 return fail(PMC_ERR_UNSUPPORTED, "unknown phase function kind " + std::to_string(phaseKind[h]) + " of medium component " + std::to_string(h));
         }
     }
+    // the velocity of every source (a shorter pmc_scene_ext has none: every source at rest)
+    pmc_source_velocity velocity[PMC_MAX_SOURCES];
+    std::memset(velocity, 0, sizeof(velocity));
+    bool moving = false;
+    static_assert(PMC_EXT_MAX_SOURCES == PMC_MAX_SOURCES, "one velocity per source slot");
+    if (ext)
+    {
+        const int sources = scene->num_sources > 1 ? scene->num_sources : 1;
+        for (int i = 0; i < sources && i < PMC_MAX_SOURCES; ++i)
+        {
+            if (size_t(ext->struct_size) < offsetof(pmc_scene_ext, source_velocity) + sizeof(pmc_source_velocity) * size_t(i + 1)) break;
+            velocity[i] = ext->source_velocity[i];
+            if (velocity[i].kind < PMC_VELOCITY_NONE || velocity[i].kind > PMC_VELOCITY_CYLINDRICAL)
+                return fail(PMC_ERR_UNSUPPORTED, "unknown velocity kind " + std::to_string(velocity[i].kind) + " of source " + std::to_string(i));
+            // (SpecialtySource.cpp:34-44, GeometricSource.cpp:31-41: no velocity in an oligochromatic simulation)
+            const pmc_source& src = scene->num_sources > 1 ? scene->sources[i] : scene->source;
+            if (src.lambda_mode == PMC_LAMBDA_OLIGO) velocity[i] = pmc_source_velocity{};
+            if (velocity[i].kind != PMC_VELOCITY_NONE) moving = true;
+        }
+    }
+    if (moving && scene->num_media > 1) return fail(PMC_ERR_UNSUPPORTED, "a moving source together with more than one medium component");
+    if (moving && scene->radiation_field.store) return fail(PMC_ERR_UNSUPPORTED, "a moving source together with a stored radiation field");
+    if (moving)
+        for (int i = 0; i < scene->num_instruments; ++i)
+            if (int64_t(scene->instruments[i].nxp) * scene->instruments[i].nyp >= (int64_t(1) << 28))
+                return fail(PMC_ERR_UNSUPPORTED, "a moving source together with an instrument of 2^28 pixels or more");
     if (pmcExperimentBuild())
     {
         static std::atomic<bool> said{false};
@@ -374,6 +400,16 @@ int pmc_create_ext(const pmc_scene* scene, const pmc_scene_ext* ext, int32_t dev
             return bail(fail(PMC_ERR_UNSUPPORTED, "unsupported wavelength sampling mode"));
     }
     D.src_first[numSources] = numSources > 1 ? scene->source_first[numSources] : ~0ull;
+    D.kin = moving ? 1 : 0;
+    for (int si = 0; si < PMC_MAX_SOURCES; ++si)
+    {
+        DevVelocity& V = D.vel[si];
+        V.kind = velocity[si].kind;
+        V.magnitude = velocity[si].magnitude;
+        std::memcpy(V.vec, velocity[si].vector, sizeof(V.vec));
+        V.unity_radius = velocity[si].unity_radius;
+        V.exponent = velocity[si].exponent;
+    }
     for (int si = 1; si < numSources; ++si)
         if (D.src[si].lambda_mode != D.src[0].lambda_mode) return bail(fail(PMC_ERR_INVALID, "sources with different wavelength regimes"));
     // one wavelength for every history: its dust properties are found here once, as launchHistory finds them (DustMix::indexForLambda:

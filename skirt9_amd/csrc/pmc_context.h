@@ -55,14 +55,15 @@ extern "C" hipError_t pmcLaunchPeelSortCounts(int slot, int slotBase, int numSlo
 extern "C" size_t pmcRfTempBytes(int numParts);
 extern "C" int pmcRfMaxParts();
 extern "C" hipError_t pmcLaunchDipoleCosines(const double* u, int64_t n, double* out, hipStream_t stream);
-extern "C" hipError_t pmcLaunchTransition(int slot, int dipole, int slotBase, int numSlots, int group, uint64_t seed, const int* list, int listLen, int maxBlocks,
+extern "C" hipError_t pmcLaunchSourceVelocities(int slot, int source, const double* r, int64_t n, double* out, hipStream_t stream);
+extern "C" hipError_t pmcLaunchTransition(int slot, int flavour, int slotBase, int numSlots, int group, uint64_t seed, const int* list, int listLen, int maxBlocks,
                                           size_t ldsBytes, const StatLogArgs* statLog, uint64_t count, hipStream_t stream);
-extern "C" hipError_t pmcLaunchLaunch(int slot, int slotBase, int numSlots, int group, uint64_t first, uint64_t count, uint64_t seed, int initial,
+extern "C" hipError_t pmcLaunchLaunch(int slot, int kin, int slotBase, int numSlots, int group, uint64_t first, uint64_t count, uint64_t seed, int initial,
                                       int maxBlocks, size_t ldsBytes, const StatLogArgs* statLog, hipStream_t stream);
 extern "C" hipError_t pmcLaunchStatFlush(int slot, const uint32_t* keys, const double* vals, uint32_t* sortedKeys, double* sortedVals, unsigned long long n,
                                          int numParts, void* temp, int numCU, const uint32_t* chunkFill, hipStream_t stream);
 extern "C" int pmcStatBucketBits();
-extern "C" hipError_t pmcLaunchCycleStart(int slot, int gridKind, int slotBase, int numSlots, int listCounter, int* listOut, const int* listIn,
+extern "C" hipError_t pmcLaunchCycleStart(int slot, int gridKind, int kin, int slotBase, int numSlots, int listCounter, int* listOut, const int* listIn,
                                           int listLen, int maxBlocks, size_t ldsBytes, const PeelSortArgs* sort, hipStream_t stream);
 extern "C" hipError_t pmcLaunchTrace(int slot, int gridKind, int wide, int uniform, const double r[3], const double k[3],
                                      const double* kdev, int32_t* m, double* ds, int32_t cap, int32_t* n, size_t ldsBytes,

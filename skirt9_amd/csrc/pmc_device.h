@@ -30,6 +30,8 @@
                             // (FluxRecorder statistics); a multiple of 4.  A history with more distinct pixels continues its list in
                             // chained blocks of PMC_STAT_CAP entries from the slot group's pool (DevScene::stat_pool_*): the
                             // reference's list is unbounded (FluxRecorder.hpp:327-338)
+#define PMC_STAT_EMISSION_BIN 0x20000000   // (a scene with a moving source) added to the pixel of a list entry: the contribution of the emission peel-off packet,
+                                           // in the wavelength bin of its own Doppler shift (SlotArrays::obsEll); pixels stay below 2^28 in such a scene
 #define PMC_STAT_POOL_EXHAUSTED 0x40000000  // flag in the length word of a list head: a contribution was lost because the pool had no block left
 
 // link word (uint32): bits 0-4 size exponent e of the target box (its edge spans 2^e finest cells), bits 5-29 index,
@@ -144,6 +146,13 @@ struct SlotArrays
     int32_t* statBin;
     double*  statW;
     int64_t  num_slots;
+    // a scene with a moving source (DevScene::kin; else null): the emission peel-off packet towards every observer has its own Doppler-shifted
+    // wavelength (PhotonPacket.cpp:66-85), so the EMISSION cycle of a history reads per instrument what every later cycle reads per slot
+    // (lambda, dustExt, ell hold the PACKET's values from the launch on).  [num_instruments][num_slots], written by the launch kernel whenever
+    // a slot takes up a history; lambda and cross section at the group leader's index only
+    double*  obsLambda;                     // wavelength of the emission peel-off packet towards the instrument's observer
+    double*  obsExt;                        // extinction cross section of the dust mix at that wavelength
+    int32_t* obsEll;                        // its wavelength bin in the instrument (at obsLambda (1 + z))
 };
 
 // Walk tasks: the transition and launch kernels start every walk of a cycle (PathSegmentGenerator::moveInside, location
@@ -208,6 +217,15 @@ struct DevSource
     int32_t angular_kind;        // PMC_ANGULAR_*: emission direction of a point source
     double  angular_axis[3];
     double  angular_cos_delta;
+};
+
+// the bulk velocity of a source at a launch position (pmc.h pmc_source_velocity): magnitude * field(r)
+struct DevVelocity
+{
+    int32_t kind;       // PMC_VELOCITY_*
+    double  magnitude;  // m/s
+    double  vec[3];     // CONSTANT: the field's vector; RADIAL, CYLINDRICAL: the field's centre
+    double  unity_radius, exponent;
 };
 
 // one medium component of a system of several (pmc.h pmc_scene::media): its cell densities in the DEVICE numbering of the cells and its
@@ -364,6 +382,10 @@ struct DevScene
     //      kernel, which runs when some component has the dipole (any_dipole)
     int32_t phase_kind[PMC_MAX_MEDIA];
     int32_t any_dipole;
+    // ---- velocity of every source (pmc.h pmc_source_velocity, pmc_scene_ext): read only by the kinematic flavours of the launch, transition and
+    //      cycle start kernels, which run when some source moves (kin); every other scene runs the kernels that hold no trace of it
+    int32_t kin;
+    DevVelocity vel[PMC_MAX_SOURCES];
 };
 
 // The radiation-field contributions of the propagation walks of one slot group and generation (octree): (key, value)

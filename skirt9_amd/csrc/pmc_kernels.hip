@@ -385,7 +385,13 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
                {reinterpret_cast<const void*>(&traceRayKernel<GRID_VORO>), walkMax},
                {reinterpret_cast<const void*>(&transitionKernel), transitionMax},
                {reinterpret_cast<const void*>(&transitionDipoleKernel), transitionMax},
+               {reinterpret_cast<const void*>(&transitionKinKernel), transitionMax},
+               {reinterpret_cast<const void*>(&transitionKinDipoleKernel), transitionMax},
                {reinterpret_cast<const void*>(&launchKernel), transitionMax},
+               {reinterpret_cast<const void*>(&launchKinKernel), transitionMax},
+               {reinterpret_cast<const void*>(&cycleStartKernel<GRID_TREE, true>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
+               {reinterpret_cast<const void*>(&cycleStartKernel<GRID_CART, true>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
+               {reinterpret_cast<const void*>(&cycleStartKernel<GRID_VORO, true>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_TREE>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_CART>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_VORO>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)}};
@@ -600,15 +606,17 @@ extern "C" hipError_t pmcLaunchStatMerge(int slot, int blocks, hipStream_t strea
 
 // transitions of the slots [slotBase, slotBase + numSlots) of slot group `group`, followed by the scan of the group's
 // ended-history counts (the launch kernel's history indices)
-// dipole: some medium component has the dipole phase function (DevScene::any_dipole): the kernel flavour that knows it
-extern "C" hipError_t pmcLaunchTransition(int slot, int dipole, int slotBase, int numSlots, int group, uint64_t seed, const int* list, int listLen, int maxBlocks,
+// flavour: bit 0 some medium component has the dipole phase function (DevScene::any_dipole), bit 1 some source moves (DevScene::kin): the kernel
+// flavour that knows them
+extern "C" hipError_t pmcLaunchTransition(int slot, int flavour, int slotBase, int numSlots, int group, uint64_t seed, const int* list, int listLen, int maxBlocks,
                                           size_t ldsBytes, const StatLogArgs* statLog, uint64_t count, hipStream_t stream)
 {
     const StatLogArgs none = {nullptr, nullptr, 0ull, 0, nullptr, nullptr, nullptr};
     const int block = PMC_TRANSITION_BLOCK;
     // (a sparse generation: one list entry per lane; otherwise persistent workgroups over runs of 256 slots per wave)
     const int grid = std::max(1, std::min(((list ? listLen : numSlots) + block - 1) / block, maxBlocks));
-    hipLaunchKernelGGL(dipole ? transitionDipoleKernel : transitionKernel, dim3(grid), dim3(block), ldsBytes, stream, slot, slotBase, numSlots, group, seed, list, listLen,
+    const auto kernel = (flavour & 2) ? ((flavour & 1) ? transitionKinDipoleKernel : transitionKinKernel) : ((flavour & 1) ? transitionDipoleKernel : transitionKernel);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), ldsBytes, stream, slot, slotBase, numSlots, group, seed, list, listLen,
                        statLog ? *statLog : none);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || list) return e;  // (a sparse generation retires its ended histories in the transition kernel)
@@ -616,18 +624,19 @@ extern "C" hipError_t pmcLaunchTransition(int slot, int dipole, int slotBase, in
     return hipGetLastError();
 }
 
-// launches of new histories into the slots of the group whose history ended (initial: into all slots of the group)
-extern "C" hipError_t pmcLaunchLaunch(int slot, int slotBase, int numSlots, int group, uint64_t first, uint64_t count, uint64_t seed, int initial,
+// launches of new histories into the slots of the group whose history ended (initial: into all slots of the group); kin: some source moves
+extern "C" hipError_t pmcLaunchLaunch(int slot, int kin, int slotBase, int numSlots, int group, uint64_t first, uint64_t count, uint64_t seed, int initial,
                                       int maxBlocks, size_t ldsBytes, const StatLogArgs* statLog, hipStream_t stream)
 {
     const StatLogArgs none = {nullptr, nullptr, 0ull, 0, nullptr, nullptr, nullptr};
     const int grid = std::max(1, std::min((numSlots + 255) / 256, maxBlocks));
-    hipLaunchKernelGGL(launchKernel, dim3(grid), dim3(256), ldsBytes, stream, slot, slotBase, numSlots, group, first, count, seed, initial, statLog ? *statLog : none);
+    hipLaunchKernelGGL(kin ? launchKinKernel : launchKernel, dim3(grid), dim3(256), ldsBytes, stream, slot, slotBase, numSlots, group, first, count, seed, initial,
+                       statLog ? *statLog : none);
     return hipGetLastError();
 }
 
-// the walks of the cycle that every live slot of the group is about to start (task records)
-extern "C" hipError_t pmcLaunchCycleStart(int slot, int gridKind, int slotBase, int numSlots, int listCounter, int* listOut, const int* listIn,
+// the walks of the cycle that every live slot of the group is about to start (task records); kin: some source moves
+extern "C" hipError_t pmcLaunchCycleStart(int slot, int gridKind, int kin, int slotBase, int numSlots, int listCounter, int* listOut, const int* listIn,
                                           int listLen, int maxBlocks, size_t ldsBytes, const PeelSortArgs* sort, hipStream_t stream)
 {
     PeelSortArgs ps;
@@ -640,7 +649,8 @@ extern "C" hipError_t pmcLaunchCycleStart(int slot, int gridKind, int slotBase, 
         ldsBytes = size_t(ps.ldsOffset) + size_t(ps.numObs + (ps.propIndex >= 0 ? 1 : 0)) * PEEL_SORT_PARTS * sizeof(uint32_t);
     }
     const int grid = std::max(1, std::min(((listIn ? listLen : numSlots) + 255) / 256, maxBlocks));
-    const auto kernel = gridKind == PMC_GRID_OCTREE ? cycleStartKernel<GRID_TREE> : gridKind == PMC_GRID_VORONOI ? cycleStartKernel<GRID_VORO> : cycleStartKernel<GRID_CART>;
+    const auto kernel = kin ? (gridKind == PMC_GRID_OCTREE ? cycleStartKernel<GRID_TREE, true> : gridKind == PMC_GRID_VORONOI ? cycleStartKernel<GRID_VORO, true> : cycleStartKernel<GRID_CART, true>)
+                            : (gridKind == PMC_GRID_OCTREE ? cycleStartKernel<GRID_TREE> : gridKind == PMC_GRID_VORONOI ? cycleStartKernel<GRID_VORO> : cycleStartKernel<GRID_CART>);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), ldsBytes, stream, slot, slotBase, numSlots, listCounter, listOut, listIn, listLen, ps);
     return hipGetLastError();
 }
@@ -659,6 +669,27 @@ extern "C" hipError_t pmcLaunchDipoleCosines(const double* u, int64_t n, double*
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(dipoleCosineKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, u, n, out);
+    return hipGetLastError();
+}
+
+// test aid (pmc_tuning.h pmc_tune_source_velocities): the launch kernel's own velocity function of source `source` over n positions [n][3] in
+// device memory
+namespace
+{
+    __global__ __launch_bounds__(256) void sourceVelocityKernel(const int sceneSlot, const int source, const double* __restrict__ r, const int64_t n,
+                                                                double* __restrict__ out)
+    {
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i >= n) return;
+        double vx, vy, vz;
+        sourceVelocity(c_scene[sceneSlot].vel[source], r[3 * i], r[3 * i + 1], r[3 * i + 2], vx, vy, vz);
+        out[3 * i] = vx, out[3 * i + 1] = vy, out[3 * i + 2] = vz;
+    }
+}
+extern "C" hipError_t pmcLaunchSourceVelocities(int slot, int source, const double* r, int64_t n, double* out, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sourceVelocityKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, slot, source, r, n, out);
     return hipGetLastError();
 }
 

@@ -87,6 +87,14 @@ namespace
         if ((rc = ctx->allocate<int32_t>(size_t(n) * size_t(ctx->dev.num_instruments), &A.ell, true, &own))) return rc;
         if (ctx->dev.any_stats && (rc = ctx->allocate<int32_t>(size_t(n) * size_t(ctx->dev.num_instruments) * 16, &A.statHead, true, &own))) return rc;
         if (ctx->dev.rf_store && (rc = ctx->allocate<int32_t>(n, &A.rfell, true, &own))) return rc;
+        if (ctx->dev.kin)
+        {
+            // (a moving source: the emission cycle's own wavelength, cross section and bin per instrument)
+            const size_t per = size_t(n) * size_t(ctx->dev.num_instruments);
+            if ((rc = ctx->allocate<double>(per, &A.obsLambda, false, &own))) return rc;
+            if ((rc = ctx->allocate<double>(per, &A.obsExt, false, &own))) return rc;
+            if ((rc = ctx->allocate<int32_t>(per, &A.obsEll, true, &own))) return rc;
+        }
         if (ctx->dev.any_stats)
         {
             size_t entries = size_t(ctx->dev.num_instruments) * PMC_STAT_CAP * size_t(n);
@@ -717,7 +725,7 @@ namespace
         if (sortNow)
             HIP_TRY(pmcLaunchPeelSortCounts(ctx->slot, P.base[g], P.size[g], &sortArgs, P.octree ? ctx->peelRec[g] : nullptr, P.octree ? nullptr : ctx->peelList[g],
                                             ctx->peelTemp[g], &sortGroups, sg));
-        HIP_TRY(pmcLaunchCycleStart(ctx->slot, D.grid_kind, P.base[g], P.size[g], buildList ? PMC_CTR_LIST(g) : -1, listOut, listIn, listLen,
+        HIP_TRY(pmcLaunchCycleStart(ctx->slot, D.grid_kind, D.kin, P.base[g], P.size[g], buildList ? PMC_CTR_LIST(g) : -1, listOut, listIn, listLen,
                                     sortNow ? sortGroups : P.cycleBlocks, ctx->walkLds, sortNow ? &sortArgs : nullptr, sg));
         S.peelSorted[g] = sortNow;
         S.listBuilt[g] = buildList;
@@ -746,7 +754,7 @@ namespace
         {
             if (g > 0) HIP_TRY(hipStreamWaitEvent(sg, ctx->evStart, 0));
             HIP_TRY(hipEventRecord(ctx->evB[g], sg));
-            HIP_TRY(pmcLaunchLaunch(ctx->slot, P.base[g], P.size[g], g, P.first, P.count, P.seed, 1, (P.size[g] + 255) / 256, ctx->launchLds, nullptr, sg));
+            HIP_TRY(pmcLaunchLaunch(ctx->slot, ctx->dev.kin, P.base[g], P.size[g], g, P.first, P.count, P.seed, 1, (P.size[g] + 255) / 256, ctx->launchLds, nullptr, sg));
             return enqueueCycleStart(ctx, P, S, g, initial, listIn, listLen);
         }
         if (P.poolGrows)
@@ -781,9 +789,9 @@ namespace
         HIP_TRY(hipEventRecord(ctx->evB[g], sg));
         HIP_TRY(hipMemsetAsync(ctr + PMC_CTR_LIVE(g), 0, sizeof(unsigned long long), sg));
         const StatLogArgs statLog = statLogOf(ctx, P, g);
-        HIP_TRY(pmcLaunchTransition(ctx->slot, ctx->dev.any_dipole, P.base[g], P.size[g], g, P.seed, listIn, listLen, P.transitionBlocks, ctx->transitionLds, &statLog, P.count, sg));
+        HIP_TRY(pmcLaunchTransition(ctx->slot, (ctx->dev.any_dipole ? 1 : 0) | (ctx->dev.kin ? 2 : 0), P.base[g], P.size[g], g, P.seed, listIn, listLen, P.transitionBlocks, ctx->transitionLds, &statLog, P.count, sg));
         if (!listIn)
-            HIP_TRY(pmcLaunchLaunch(ctx->slot, P.base[g], P.size[g], g, P.first, P.count, P.seed, 0, P.launchBlocks, ctx->launchLds, &statLog, sg));
+            HIP_TRY(pmcLaunchLaunch(ctx->slot, ctx->dev.kin, P.base[g], P.size[g], g, P.first, P.count, P.seed, 0, P.launchBlocks, ctx->launchLds, &statLog, sg));
         return enqueueCycleStart(ctx, P, S, g, initial, listIn, listLen);
     }
 

@@ -252,8 +252,12 @@
         S.stat_pool_free[S.stat_pool_first[group] + (int)pos] = block;
     }
 
+    // KIN (a scene with a moving source): `emission` = the packet is an emission peel-off packet, whose wavelength bin is the observer's own
+    // (SlotArrays::obsEll); a history can then contribute to TWO wavelength bins of an instrument, and the list entry of an emission
+    // contribution to another bin than the packet's carries PMC_STAT_EMISSION_BIN on top of its pixel (flushStatistics)
+    template<bool KIN = false>
     __device__ __forceinline__ void detect(const DevScene& S, const DustLds& L, Counters& cnt, int inst, int slot, double rx,
-                                           double ry, double rz, double Lum, double tau, int numScatt, int group)
+                                           double ry, double rz, double Lum, double tau, int numScatt, int group, bool emission = false)
     {
         const DevInstrument& I = S.inst[inst];
         const SlotArrays& A = S.slots;
@@ -276,11 +280,14 @@
             headN = *reinterpret_cast<const int2*>(head + 48);
         }
 #endif
-        const int l = pixelOnDetector(I, rx, ry, rz);
+        int l = pixelOnDetector(I, rx, ry, rz);
         if (!I.include_sed && l < 0) return;
         if (!insideAperture(I, rx, ry, rz)) return;
-        const int ell = S.mono ? I.mono_ell : A.ell[(int64_t)inst * A.num_slots + slot];
+        const int ell = (KIN && emission) ? A.obsEll[ni] : S.mono ? I.mono_ell : A.ell[(int64_t)inst * A.num_slots + slot];
         if (ell < 0) return;
+        const int pixel = l;
+        // (the key of the contribution in the history's list: the pixel, or for an emission contribution to a bin of its own the marked pixel)
+        if (KIN && emission && I.record_stats && ell != A.ell[ni]) l = pixel + PMC_STAT_EMISSION_BIN;
         const double Lext = Lum * exp(-tau);
         if (I.include_sed)
         {
@@ -299,10 +306,10 @@
                 if (numScatt <= I.num_levels) atomicAdd(&sed[(3 + numScatt - 1) * nl + ell], Lext);
             }
         }
-        if (I.include_ifu && l >= 0)
+        if (I.include_ifu && pixel >= 0)
         {
             const int64_t len = I.npix * I.num_lambda;
-            const int64_t at = I.ifu_offset + l + (int64_t)ell * I.npix;
+            const int64_t at = I.ifu_offset + pixel + (int64_t)ell * I.npix;
             if (!I.record_components)
             {
                 frameAdd(S, L, at, Lext);
@@ -509,6 +516,9 @@
         return true;
     }
 
+    // KIN: an entry marked PMC_STAT_EMISSION_BIN (detect) belongs to the wavelength bin of the emission peel-off packet (SlotArrays::obsEll); there is
+    // at most one, and it is a bin of its own (FluxRecorder sums the contributions of a history per (ell, pixel))
+    template<bool KIN = false>
     __device__ __forceinline__ void flushStatistics(const DevScene& S, const DustLds& L, Counters& cnt, int slot, bool flush,
                                                     int lane, int group, bool giveBack, const StatLogArgs& statLog, StatLogWave& logWave)
     {
@@ -519,6 +529,9 @@
             const DevInstrument& I = S.inst[inst];
             if (!I.record_stats) continue;
             int n = 0, ell = -1;
+            int ellEmission = -1;    // (KIN) the bin of a marked entry
+            double wsedEmission = 0.;
+            bool anyEmission = false, anyOther = false;
             // (the head record: length of the list, first chained block, and the first four entries -- a history has 3.7 entries
             // on average -- in one round trip)
             int block = -1;
@@ -532,6 +545,7 @@
                 w01 = *reinterpret_cast<const double2*>(head + 16);
                 w23 = *reinterpret_cast<const double2*>(head + 32);
                 ell = S.mono ? I.mono_ell : A.ell[(int64_t)inst * stride + slot];
+                if (KIN) ellEmission = A.obsEll[(int64_t)inst * stride + slot];
                 *reinterpret_cast<int2*>(head + 48) = make_int2(0, -1);
                 n = headN.x;
                 if (n & PMC_STAT_POOL_EXHAUSTED)
@@ -544,7 +558,7 @@
                 if (n > PMC_STAT_CAP) block = headN.y;
             }
             const int total = n;
-            if (ell < 0) n = 0;  // (no bin: nothing to add, but the blocks are returned below)
+            if (ell < 0 && !(KIN && ellEmission >= 0)) n = 0;  // (no bin: nothing to add, but the blocks are returned below)
             const int64_t base = ((int64_t)inst * stride + (flush ? slot : 0)) * PMC_STAT_CAP;
             double wsed = 0.;
             for (int e = 0; __ballot(e < n) != 0ull; ++e)
@@ -576,10 +590,22 @@
                         bin = S.stat_pool_bin[(int64_t)block * PMC_STAT_CAP + q];
                         w = S.stat_pool_w[(int64_t)block * PMC_STAT_CAP + q];
                     }
-                    wsed += w;
+                    int binEll = ell;
+                    if (KIN && bin >= PMC_STAT_EMISSION_BIN - 1)
+                    {
+                        bin -= PMC_STAT_EMISSION_BIN;
+                        binEll = ellEmission;
+                        wsedEmission += w;
+                        anyEmission = true;
+                    }
+                    else
+                    {
+                        wsed += w;
+                        anyOther = true;
+                    }
                     if (bin >= 0 && I.include_ifu)
                     {
-                        rec = I.stat_acc_offset + bin + (int64_t)ell * I.npix;
+                        rec = I.stat_acc_offset + bin + (int64_t)binEll * I.npix;
                         cnt.updates += 5;
                     }
                 }
@@ -610,7 +636,7 @@
                     block = S.stat_pool_next[block];
                     if (giveBack) statBlockReturn(S, group, done);
                 }
-            if (n > 0 && I.include_sed)
+            if (n > 0 && I.include_sed && (!KIN || anyOther))
             {
                 double* sed = L.sed + I.sed_lds_offset + I.num_components * I.num_lambda;
                 double wn = 1.;
@@ -618,6 +644,16 @@
                 {
                     atomicAdd(&sed[k * I.num_lambda + ell], wn);
                     wn *= wsed;
+                }
+            }
+            if (KIN && anyEmission && I.include_sed)
+            {
+                double* sed = L.sed + I.sed_lds_offset + I.num_components * I.num_lambda;
+                double wn = 1.;
+                for (int k = 0; k <= 4; ++k)
+                {
+                    atomicAdd(&sed[k * I.num_lambda + ellEmission], wn);
+                    wn *= wsedEmission;
                 }
             }
         }
@@ -693,6 +729,8 @@
     // for the optical depth: some instrument of the group records the packet (FluxRecorder.cpp:310-327: detect returns
     // before the optical depth is needed if the packet misses the frame of an instrument without SED, or if its
     // wavelength falls outside the instrument's grid).  Returns num_instruments if no observer is left.
+    // EMISSION (a scene with a moving source, emission cycle): the bins of the observers' own wavelengths (SlotArrays::obsEll)
+    template<bool EMISSION = false>
     __device__ __forceinline__ int nextObserver(const DevScene& S, int slot, double rx, double ry, double rz, int g)
     {
         const SlotArrays& A = S.slots;
@@ -704,7 +742,8 @@
             {
                 const DevInstrument& I = S.inst[j];
                 const bool seen = (I.include_sed && insideAperture(I, rx, ry, rz)) || (I.include_ifu && pixelOnDetector(I, rx, ry, rz) >= 0);
-                if (seen && (S.mono ? S.inst[j].mono_ell : A.ell[(int64_t)j * A.num_slots + slot]) >= 0) need = true;
+                if (seen && (EMISSION ? A.obsEll[(int64_t)j * A.num_slots + slot] : S.mono ? S.inst[j].mono_ell : A.ell[(int64_t)j * A.num_slots + slot]) >= 0)
+                    need = true;
                 ++j;
             } while (j < S.num_instruments && S.inst[j].same_observer);
             if (need) return g;
@@ -950,7 +989,7 @@
     // Several medium components: `shares` holds every component's share of the scattering opacity in the interaction cell and
     // `asyms` its asymmetry parameter; the peel-off weight is the sum of the components' phase functions weighted by the shares
     // (MediumSystem::peelOffScattering, consolidated form, MediumSystem.cpp:734-767; components with share 0 are skipped).
-    template<bool DIPOLE = false>
+    template<bool DIPOLE = false, bool EMISSION = false>
     __device__ __forceinline__ void announceCycle(const DevScene& S, int slot, uint64_t seed, Rng& rng, double rx, double ry, double rz, double kinx,
                                                   double kiny, double kinz, double W, double asym, int pscatt, const double* shares = nullptr,
                                                   const double* asyms = nullptr, const DevSource* emitter = nullptr)
@@ -958,7 +997,7 @@
         const SlotArrays& A = S.slots;
         const int64_t NS = A.num_slots;
         uint32_t pmask = 0;
-        int g = nextObserver(S, slot, rx, ry, rz, 0);
+        int g = nextObserver<EMISSION>(S, slot, rx, ry, rz, 0);
         for (int i = 0; i < S.num_instruments; ++i)
         {
             if (i != g) continue;
@@ -984,7 +1023,7 @@
             pmask |= 1u << i;
             int j = i + 1;
             while (j < S.num_instruments && S.inst[j].same_observer) ++j;
-            g = nextObserver(S, slot, rx, ry, rz, j);
+            g = nextObserver<EMISSION>(S, slot, rx, ry, rz, j);
         }
         if (!S.force_scattering)
             // the interaction optical depth is drawn now (Random::expon, MonteCarloSimulation.cpp:746-752); it travels in
@@ -1006,7 +1045,13 @@
     // Start of a cycle, second part: the walks.  All of them start at the slot's position; a peel-off walk needs the weight
     // of its packet (taumax of MediumSystem::getExtinctionOpticalDepth), the propagation walk the direction.
     // returns the walks that exist: bit 1 + i = the peel-off walk towards observer i, bit 0 = the propagation walk
-    template<int GRID>
+    // KIN (a scene with a moving source): in the emission cycle the packet towards observer i has its own wavelength -- its own taumax --
+    // and its own cross section sigma_i.  The peel-off walk kernels are the ones every scene runs: they sum the optical depth with the
+    // PACKET's cross section sigma (SlotArrays::dustExt).  With ONE medium component the two depths of a path differ by the factor
+    // sigma_i / sigma, so the walk gets the stop value taumax sigma / sigma_i, and onCycleDone multiplies the depth it finds by sigma_i / sigma
+    // (both exactly 1 where the cross sections agree; otherwise two roundings on a sum of thousands).  sigma = 0 < sigma_i leaves
+    // nothing to scale: counted as an internal error (DevScene::counters[7]), pmc_run_primary fails.
+    template<int GRID, bool KIN = false>
     __device__ __forceinline__ uint32_t startCycleWalks(const DevScene& S, const GridLds& G, Counters& cnt, int slot, int modeWord, const PeelSortArgs* ps = nullptr,
                                                         uint32_t* cursors = nullptr)
     {
@@ -1020,6 +1065,7 @@
         const int hint0 = A.mint[slot];
         const double drawn = S.force_scattering ? 0. : A.tausample[slot];
         const uint32_t pmask = ((uint32_t)modeWord >> 8) & 0xFFFFu;
+        const bool emission = KIN && A.nscatt[slot] == 0;
         int hint = hint0;
         uint32_t made = 0u;
         // Voronoi: all walks of the cycle start at this position: its cell (VoronoiMeshSnapshot::cellIndex) is found once
@@ -1038,7 +1084,16 @@
             const DevInstrument& I = S.inst[prop ? 0 : i];
             // peel-off walk: up to taumax of the packet's weight; propagation walk: forced scattering walks the whole path first
             // (pass 1), otherwise up to the drawn optical depth
-            const double target = prop ? drawn : peelTaumax(A.ppW[(int64_t)i * NS + slot], lambda);
+            double target = prop ? drawn : peelTaumax(A.ppW[(int64_t)i * NS + slot], (KIN && emission) ? A.obsLambda[(int64_t)i * NS + slot] : lambda);
+            if (KIN && emission && !prop && target != -INFINITY)
+            {
+                const double sobs = A.obsExt[(int64_t)i * NS + slot];
+                if (sobs != sext)
+                {
+                    if (sext == 0.) atomicAdd(S.counters + 7, 1ull);
+                    target = sobs > 0. ? target * (sext / sobs) : INFINITY;
+                }
+            }
             // (sorted peel-off records: the walk's place in the tile order of its observer -- every slot with this bit of the mode word set
             // takes one, as peelSortCountKernel counted)
             PeelRec* place = nullptr;
@@ -1082,7 +1137,7 @@
     //      then the interaction the propagation walk found (MonteCarloSimulation.cpp:724-741 / 746-780): albedo and
     //      escape weights, termination test, scattering (DustMix::performScattering, HG), and the next cycle.
     //      All slot loads are issued as one batch first.
-    template<bool DIPOLE>
+    template<bool DIPOLE, bool KIN = false>
     __device__ __forceinline__ int onCycleDone(const DevScene& S, const DustLds& L, Counters& cnt, int slot, int modeWord, uint64_t seed, int group)
     {
         const SlotArrays& A = S.slots;
@@ -1108,12 +1163,19 @@
         for (int g = 0; g < S.num_instruments; ++g)
         {
             if (!((pmask >> g) & 1u)) continue;
-            const double Lum = A.ppW[(int64_t)g * NS + slot] / lambda;
-            const double tau = A.ptau[(int64_t)g * NS + slot];
+            // (KIN, emission cycle: the packet towards this observer has its own wavelength and cross section -- startCycleWalks)
+            const bool emission = KIN && pscatt == 0;
+            const double Lum = A.ppW[(int64_t)g * NS + slot] / (emission ? A.obsLambda[(int64_t)g * NS + slot] : lambda);
+            double tau = A.ptau[(int64_t)g * NS + slot];
+            if (emission)
+            {
+                const double sobs = A.obsExt[(int64_t)g * NS + slot];
+                if (sobs != sext && tau != INFINITY) tau = tau * (sobs / sext);
+            }
             int inst = g;
             do
             {
-                detect(S, L, cnt, inst, slot, rx0, ry0, rz0, Lum, tau, pscatt, group);
+                detect<KIN>(S, L, cnt, inst, slot, rx0, ry0, rz0, Lum, tau, pscatt, group, emission);
                 ++inst;
             } while (inst < S.num_instruments && S.inst[inst].same_observer);
         }
@@ -1230,6 +1292,39 @@
     // ---- SourceSystem::launch ... PhotonPacket::launch (SourceSystem.cpp:101-112, NormalizedSource.cpp:73-110,
     //      PointSource.cpp:32-43, GeometricSource.cpp:66-82, SpheGeometry.cpp:25-32, SersicGeometry.cpp:41-45) followed
     //      by the first cycle (emission peel-offs and first propagation walk); returns false for a zero-luminosity packet
+    // the bulk velocity of a source at the launch position r (pmc.h pmc_source_velocity): magnitude * field(r), GeometricSource.cpp:66-82 with
+    // UnidirectionalVectorField.cpp:28-31, RadialVectorField.cpp:17-35, CylindricalVectorField.cpp:17-36, OffsetVectorFieldDecorator.cpp:16-21; a
+    // PointSource's velocity is magnitude 1 times the vector (SpecialtySource.cpp:48-51)
+    __device__ __forceinline__ void sourceVelocity(const DevVelocity& V, double rx, double ry, double rz, double& vx, double& vy, double& vz)
+    {
+        vx = 0., vy = 0., vz = 0.;
+        if (V.kind == PMC_VELOCITY_NONE) return;
+        double ux = V.vec[0], uy = V.vec[1], uz = V.vec[2];
+        if (V.kind != PMC_VELOCITY_CONSTANT)
+        {
+            const double x = rx - V.vec[0], y = ry - V.vec[1], z = rz - V.vec[2];
+            const bool radial = V.kind == PMC_VELOCITY_RADIAL;
+            ux = radial ? x : -y, uy = radial ? y : x, uz = radial ? z : 0.;
+            const double r = sqrt(ux * ux + uy * uy + uz * uz);
+            if (r == 0.) return;  // (the null vector at the centre resp. on the axis)
+            ux /= r, uy /= r, uz /= r;
+            double v = 1.;
+            if (V.unity_radius > 0. && ((V.exponent > 0. && r < V.unity_radius) || (V.exponent < 0. && r > V.unity_radius)))
+                v = pow(r / V.unity_radius, V.exponent);
+            ux = v * ux, uy = v * uy, uz = v * uz;
+        }
+        vx = V.magnitude * ux, vy = V.magnitude * uy, vz = V.magnitude * uz;
+    }
+    // PhotonPacket::shiftedEmissionWavelength (PhotonPacket.cpp:133-136)
+    __device__ __forceinline__ double shiftedEmissionWavelength(double lambda0, double kx, double ky, double kz, double vx, double vy, double vz)
+    {
+        return lambda0 * (1 - (kx * vx + ky * vy + kz * vz) / 2.99792458e8);
+    }
+
+    // KIN (a scene with a moving source): the packet's wavelength is Doppler-shifted by the source's velocity along the launch direction
+    // (PhotonPacket.cpp:18-40: the weight W = L lambda0 keeps the sampled wavelength), and so is, by the velocity along its line of sight,
+    // that of the emission peel-off packet towards every observer (:66-85): SlotArrays::obsLambda, obsExt, obsEll
+    template<bool KIN = false>
     __device__ __forceinline__ bool launchHistory(const DevScene& S, const DustLds& L, Counters& cnt, int slot, uint64_t history, uint64_t seed)
     {
         const SlotArrays& A = S.slots;
@@ -1405,6 +1500,13 @@
 #endif
         const double Lw = Q.packet_luminosity * w;
         const double W = Lw * lambda;
+        const double lambda0 = lambda;
+        double vx = 0., vy = 0., vz = 0.;
+        if (KIN)
+        {
+            sourceVelocity(S.vel[si], rx, ry, rz, vx, vy, vz);
+            lambda = shiftedEmissionWavelength(lambda0, kx, ky, kz, vx, vy, vz);
+        }
         if (!(W / lambda > 0)) return false;
         A.rx[slot] = rx, A.ry[slot] = ry, A.rz[slot] = rz;
         A.kx[slot] = kx, A.ky[slot] = ky, A.kz[slot] = kz;
@@ -1450,6 +1552,24 @@
                     lo = mid + 1;
             }
             if (!S.mono) A.ell[(int64_t)i * A.num_slots + slot] = I.ellv[lo];
+            if (KIN)
+            {
+                // the emission peel-off packet towards this instrument's observer: wavelength, cross section there, bin
+                const double lambdaPeel = shiftedEmissionWavelength(lambda0, I.kx, I.ky, I.kz, vx, vy, vz);
+                const double lambdaPeelObs = lambdaPeel * I.zp1;
+                int plo = 0, phi = I.num_border;
+                while (plo < phi)
+                {
+                    int mid = (plo + phi) >> 1;
+                    if (lambdaPeelObs < I.border[mid])
+                        phi = mid;
+                    else
+                        plo = mid + 1;
+                }
+                A.obsLambda[(int64_t)i * A.num_slots + slot] = lambdaPeel;
+                A.obsExt[(int64_t)i * A.num_slots + slot] = L.sext[locateClip(L.lamb, S.num_lambda, lambdaPeel)];
+                A.obsEll[(int64_t)i * A.num_slots + slot] = I.ellv[plo];
+            }
             if (S.any_stats) *reinterpret_cast<int2*>(reinterpret_cast<char*>(A.statHead) + ((int64_t)i * A.num_slots + slot) * 64 + 48) = make_int2(0, -1);
         }
         if (S.rf_store)
@@ -1469,7 +1589,7 @@
         // the photon cycle starts with the emission peel-offs and the first propagation walk
         A.Lthreshold[slot] = (W / lambda) / S.min_weight_reduction;  // MonteCarloSimulation.cpp:566
         PMC_T_STAMP(4);
-        announceCycle(S, slot, seed, rng, rx, ry, rz, kx, ky, kz, W, asym, 0, nullptr, nullptr, Q.angular_kind != PMC_ANGULAR_ISOTROPIC ? &Q : nullptr);
+        announceCycle<false, KIN>(S, slot, seed, rng, rx, ry, rz, kx, ky, kz, W, asym, 0, nullptr, nullptr, Q.angular_kind != PMC_ANGULAR_ISOTROPIC ? &Q : nullptr);
         storeRng(A, slot, rng);
         return true;
     }
@@ -1479,7 +1599,8 @@
     // ================================================================================================
     //  DIPOLE: the flavour of a scene in which some medium component has the dipole phase function (transitionDipoleKernel); every other
     //  scene runs transitionKernel, which holds no trace of it
-    template<bool DIPOLE>
+    //  KIN: the flavour of a scene with a moving source (transitionKinKernel, transitionKinDipoleKernel)
+    template<bool DIPOLE, bool KIN = false>
     __device__ __forceinline__ void transitionBody(const int sceneSlot, const int slotBase, const int numSlots, const int group, const uint64_t seed,
                                                    const int* const list, const int listLen, const StatLogArgs& statLog)
     {
@@ -1566,14 +1687,14 @@
                     const int entry = myList[c + lane];
                     slot = entry & 0x3FFFFFFF;
                     sub = (int)((unsigned)entry >> 30);
-                    event = onCycleDone<DIPOLE>(S, L, cnt, slot, myMode[c + lane], seed, group);
+                    event = onCycleDone<DIPOLE, KIN>(S, L, cnt, slot, myMode[c + lane], seed, group);
                 }
                 PMC_T_STAMP(2);
                 if (list)
                 {
                     // the history has ended and none is left to take its slot (SourceSystem has handed out all indices): its statistics
                     // are flushed here and the slot dies
-                    if (S.any_stats) flushStatistics(S, L, cnt, slot, event == EV_LAUNCH, lane, group, false, statLog, logWave);
+                    if (S.any_stats) flushStatistics<KIN>(S, L, cnt, slot, event == EV_LAUNCH, lane, group, false, statLog, logWave);
                     if (event == EV_LAUNCH)
                     {
                         A.mode[slot] = MODE_NONE;
@@ -1617,6 +1738,18 @@
                                                             const int listLen, const StatLogArgs statLog)
     {
         transitionBody<true>(sceneSlot, slotBase, numSlots, group, seed, list, listLen, statLog);
+    }
+    __global__ __launch_bounds__(PMC_TRANSITION_BLOCK, PMC_TRANSITION_MIN_WAVES) void transitionKinKernel(const int sceneSlot, const int slotBase, const int numSlots,
+                                                            const int group, const uint64_t seed, const int* const list, const int listLen,
+                                                            const StatLogArgs statLog)
+    {
+        transitionBody<false, true>(sceneSlot, slotBase, numSlots, group, seed, list, listLen, statLog);
+    }
+    __global__ __launch_bounds__(PMC_TRANSITION_BLOCK, PMC_TRANSITION_MIN_WAVES) void transitionKinDipoleKernel(const int sceneSlot, const int slotBase,
+                                                            const int numSlots, const int group, const uint64_t seed, const int* const list,
+                                                            const int listLen, const StatLogArgs statLog)
+    {
+        transitionBody<true, true>(sceneSlot, slotBase, numSlots, group, seed, list, listLen, statLog);
     }
 
     // ================================================================================================
@@ -1708,9 +1841,10 @@
     //  lanes whose history has ended (first generation: all) flush the per-history statistics, take up the next history --
     //  its index follows from the scanned counts -- launch it and start its first cycle
     // ================================================================================================
-    __global__ __launch_bounds__(256, PMC_LAUNCH_MIN_WAVES) void launchKernel(const int sceneSlot, const int slotBase, const int numSlots, const int group,
-                                                        const uint64_t first, const uint64_t count, const uint64_t seed, const int initial,
-                                                        const StatLogArgs statLog)
+    //  KIN: the flavour of a scene with a moving source (launchKinKernel)
+    template<bool KIN>
+    __device__ __forceinline__ void launchBody(const int sceneSlot, const int slotBase, const int numSlots, const int group, const uint64_t first,
+                                               const uint64_t count, const uint64_t seed, const int initial, const StatLogArgs& statLog)
     {
         const DevScene& S = c_scene[sceneSlot];
         extern __shared__ double lds[];
@@ -1781,7 +1915,7 @@
                 }
                 const bool ended = slot >= 0;
 #ifndef PMC_ABLATE_LAUNCH_FLUSH
-                if (!initial && S.any_stats) flushStatistics(S, L, cnt, slot, ended, lane, group, true, statLog, logWave);
+                if (!initial && S.any_stats) flushStatistics<KIN>(S, L, cnt, slot, ended, lane, group, true, statLog, logWave);
 #endif
                 PMC_T_STAMP(2);
                 int event = ended ? EV_LAUNCH : EV_NONE;
@@ -1813,7 +1947,7 @@
                         else
                         {
                             cnt.histories += 1;
-                            if (launchHistory(S, L, cnt, slot, first + h, seed)) event = EV_TASK;
+                            if (launchHistory<KIN>(S, L, cnt, slot, first + h, seed)) event = EV_TASK;
                         }
                     }
                 }
@@ -1833,6 +1967,18 @@
         PMC_T_PROF_END(200);
         addCounters(S, cnt, lane);
     }
+    __global__ __launch_bounds__(256, PMC_LAUNCH_MIN_WAVES) void launchKernel(const int sceneSlot, const int slotBase, const int numSlots, const int group,
+                                                        const uint64_t first, const uint64_t count, const uint64_t seed, const int initial,
+                                                        const StatLogArgs statLog)
+    {
+        launchBody<false>(sceneSlot, slotBase, numSlots, group, first, count, seed, initial, statLog);
+    }
+    __global__ __launch_bounds__(256, PMC_LAUNCH_MIN_WAVES) void launchKinKernel(const int sceneSlot, const int slotBase, const int numSlots, const int group,
+                                                        const uint64_t first, const uint64_t count, const uint64_t seed, const int initial,
+                                                        const StatLogArgs statLog)
+    {
+        launchBody<true>(sceneSlot, slotBase, numSlots, group, first, count, seed, initial, statLog);
+    }
 
     // ================================================================================================
     //  cycle start kernel: one lane per slot of the group, in slot order; every live slot is at the start of a cycle here (its
@@ -1843,7 +1989,8 @@
     //  TaskArrays::liveList; counter S.counters[listCounter]): the kernels of a sparse generation run over that list -- this one
     //  too (listIn, listLen: the list the generation started with).
     // ================================================================================================
-    template<int GRID>
+    //  KIN: the flavour of a scene with a moving source
+    template<int GRID, bool KIN = false>
     __global__ __launch_bounds__(256, PMC_CYCLE_MIN_WAVES) void cycleStartKernel(const int sceneSlot, const int slotBase, const int numSlots,
                                                                                  const int listCounter, int* const listOut,
                                                                                  const int* const listIn, const int listLen, const PeelSortArgs ps)
@@ -1877,7 +2024,7 @@
                 {
                     const int slot = slotBase + i;
                     const int md = A.mode[slot];
-                    if (md & MODE_ALIVE) startCycleWalks<GRID>(S, G, cnt, slot, md, &ps, cur);
+                    if (md & MODE_ALIVE) startCycleWalks<GRID, KIN>(S, G, cnt, slot, md, &ps, cur);
                 }
         }
         else
@@ -1888,7 +2035,7 @@
                 const int i = i0 + tid;
                 const int slot = sparse ? (i < listLen ? listIn[i] : -1) : slotBase + i;
                 const int md = (slot >= 0 && slot < slotEnd) ? A.mode[slot] : 0;
-                if (md & MODE_ALIVE) startCycleWalks<GRID>(S, G, cnt, slot, md);
+                if (md & MODE_ALIVE) startCycleWalks<GRID, KIN>(S, G, cnt, slot, md);
                 if (GRID == GRID_TREE && listCounter >= 0)
                 {
                     // a sparse generation follows: the live slots go to the group's list, in any order (one atomic per wave)

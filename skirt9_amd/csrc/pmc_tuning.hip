@@ -63,3 +63,28 @@ extern "C" int pmc_tune_dipole_cosines(pmc_ctx* ctx, const double* u, int64_t n,
     if (e != hipSuccess) return hipFail(e, "pmc_tune_dipole_cosines");
     return PMC_OK;
 }
+
+extern "C" int pmc_tune_source_velocities(pmc_ctx* ctx, int32_t source, const double* r, int64_t n, double* v_out)
+{
+    if (!ctx || n < 0 || (n > 0 && (!r || !v_out))) return fail(PMC_ERR_INVALID, "pmc_tune_source_velocities: invalid argument");
+    if (source < 0 || source >= ctx->dev.num_sources) return fail(PMC_ERR_INVALID, "pmc_tune_source_velocities: no such source");
+    if (n == 0) return PMC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    double* d = nullptr;
+    HIP_TRY(hipMalloc(&d, sizeof(double) * size_t(6 * n)));
+    hipError_t e = hipSuccess;
+    if (ctx->sceneDirty)
+    {
+        // (the scene in constant memory, as pmc_trace_ray brings it up to date)
+        e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = pmcUploadScene(ctx->slot, &ctx->dev, ctx->stream);
+        if (e == hipSuccess) ctx->sceneDirty = false;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(d, r, sizeof(double) * size_t(3 * n), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = pmcLaunchSourceVelocities(ctx->slot, source, d, n, d + 3 * n, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(v_out, d + 3 * n, sizeof(double) * size_t(3 * n), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    hipFree(d);
+    if (e != hipSuccess) return hipFail(e, "pmc_tune_source_velocities");
+    return PMC_OK;
+}

@@ -22,7 +22,7 @@ SYMBOLS = ["pmc_abi_version", "pmc_build_info", "pmc_last_error", "pmc_frame_lay
            "pmc_download_radiation_field", "pmc_clear_radiation_field", "pmc_bind_radiation_field", "pmc_sampler_create",
            "pmc_sampler_density", "pmc_sampler_destroy", "pmc_history_range", "pmc_comm_init_all", "pmc_comm_unique_id",
            "pmc_comm_init_rank", "pmc_comm_size", "pmc_comm_destroy", "pmc_reduce_frames", "pmc_allreduce_radiation_field",
-           "pmc_debug_tables", "pmc_tuning_set", "pmc_tuning_clear", "pmc_tune_dipole_cosines"]
+           "pmc_debug_tables", "pmc_tuning_set", "pmc_tuning_clear", "pmc_tune_dipole_cosines", "pmc_tune_source_velocities"]
 
 _lib = None
 
@@ -55,6 +55,8 @@ def lib():
         if hasattr(L, "pmc_create_ext"):  # (absent from engines built from an older commit and loaded through PMC_LIBRARY)
             L.pmc_create_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
             L.pmc_tune_dipole_cosines.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        if hasattr(L, "pmc_tune_source_velocities"):  # (likewise)
+            L.pmc_tune_source_velocities.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         L.pmc_destroy.argtypes = [C.c_void_p]
         L.pmc_bind_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.pmc_clear_frames.argtypes = [C.c_void_p]
@@ -200,6 +202,8 @@ class Engine:
             # (an engine from before the extension knows Henyey-Greenstein only: another phase function must not run as that)
             if ext and any(SceneExt.from_address(ext).phase_function):
                 raise RuntimeError("this libpmc.so has no pmc_create_ext: it cannot run a scene with a dipole component")
+            if ext and any(v.kind for v in SceneExt.from_address(ext).source_velocity):
+                raise RuntimeError("this libpmc.so has no pmc_create_ext: it cannot run a scene with a moving source")
             _check(L.pmc_create(int(scene_ptr), device, C.byref(self._h)))
         self.device = device
 
@@ -330,6 +334,14 @@ class Engine:
         u = np.ascontiguousarray(u, dtype=np.float64)
         out = np.empty_like(u)
         _check(lib().pmc_tune_dipole_cosines(self._h, u.ctypes.data_as(C.c_void_p), u.size, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def source_velocities(self, source, positions):
+        """test aid (pmc_tune_source_velocities): the velocity (m/s) that the launch kernel's velocity function gives source `source` at
+        the positions [n][3] (m)"""
+        r = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        out = np.empty_like(r)
+        _check(lib().pmc_tune_source_velocities(self._h, int(source), r.ctypes.data_as(C.c_void_p), r.shape[0], out.ctypes.data_as(C.c_void_p)))
         return out
 
     def trace_ray(self, r, k, cap=4096):

@@ -618,6 +618,9 @@ namespace skh
         double normWavelength{0}, specificLuminosity{0};
         std::string normRange{"Source"};
         double normMinWavelength{0.09e-6}, normMaxWavelength{100e-6}, integratedLuminosity{0};
+        // bulk velocity of the source in a panchromatic simulation (pmc.h pmc_source_velocity; kind PMC_VELOCITY_NONE: at rest): a PointSource's
+        // velocityX/Y/Z (SpecialtySource.cpp:34-50), a GeometricSource's velocityMagnitude times its velocityDistribution (GeometricSource.cpp:66-82)
+        pmc_source_velocity velocity{};
     };
 
     // ---------------------------------------------------------------- wavelength grid (disjoint bins)

@@ -1,5 +1,5 @@
 // scenefile.cpp -- a set-up scene as ONE file: everything pmc_create_ext reads (include/pmc.h pmc_scene: grid, densities, dust tables,
-// sources, instruments; pmc_scene_ext: the components' phase functions) plus the few numbers a driver of the photon loop needs (seed, packets of the segment, frame layout).
+// sources, instruments; pmc_scene_ext: the components' phase functions, the sources' velocities) plus the few numbers a driver of the photon loop needs (seed, packets of the segment, frame layout).
 //
 // In a job of one process per GPU every process needs the same scene.  The reference repeats the whole setup in every MPI
 // process (Simulation::setupSimulation runs everywhere; only the photon packets are distributed, SKIRT/mpi/ProcessManager.cpp).
@@ -35,6 +35,16 @@ namespace
         uint64_t scene_offset, layout_offset, total_bytes;
         uint32_t sizeof_scene, sizeof_instrument, sizeof_source, sizeof_layout;
         uint64_t checksum;  // FNV-1a (64 bit) of the bytes behind the header
+    };
+
+    // The velocities of the sources (pmc_scene_ext::source_velocity) follow the frame layouts as a block of their own, written only for a
+    // scene with a moving source: a file without it -- every file written before sources could move -- describes sources at rest.
+    constexpr uint64_t VELOCITY_TAG = 0x31304c4556534b48ull;  // "HKSVEL01"
+    struct VelocityBlock
+    {
+        uint64_t tag;
+        uint32_t count, sizeof_velocity;
+        pmc_source_velocity velocity[PMC_EXT_MAX_SOURCES];
     };
 
     uint64_t fnv1a(const char* data, size_t bytes)
@@ -187,6 +197,17 @@ int skh_scene_save(const skh_simulation* h, const char* path)
         std::vector<pmc_frame_layout> layouts(size_t(live.num_instruments));
         for (int i = 0; i < live.num_instruments; ++i) skh_frame_layout(h, i, &layouts[size_t(i)]);
         const size_t layoutAt = S.append(layouts.data(), layouts.size() * sizeof(pmc_frame_layout));
+        const pmc_scene_ext& ext = *skh_scene_ext(h);
+        bool moving = false;
+        for (const pmc_source_velocity& v : ext.source_velocity) moving = moving || v.kind != PMC_VELOCITY_NONE;
+        if (moving)
+        {
+            VelocityBlock block{};
+            block.tag = VELOCITY_TAG;
+            block.count = PMC_EXT_MAX_SOURCES, block.sizeof_velocity = sizeof(pmc_source_velocity);
+            std::memcpy(block.velocity, ext.source_velocity, sizeof(block.velocity));
+            S.append(&block, sizeof(block));
+        }
         Header head{};
         head.magic = MAGIC;
         head.abi = PMC_ABI_VERSION;
@@ -197,7 +218,6 @@ int skh_scene_save(const skh_simulation* h, const char* path)
         head.rf_size = skh_radiation_field_size(h);
         head.num_instruments = live.num_instruments;
         static_assert(PMC_MAX_MEDIA <= 4, "one byte per component in Header::phase_kinds");
-        const pmc_scene_ext& ext = *skh_scene_ext(h);
         for (int c = 0; c < PMC_MAX_MEDIA; ++c)
         {
             if (ext.phase_function[c] < 0 || ext.phase_function[c] > 255) throw std::runtime_error("skh_scene_save: phase function kind out of range");
@@ -274,6 +294,17 @@ skh_scene_file* skh_scene_load(const char* path)
         file->header = head;
         file->ext.struct_size = int32_t(sizeof(pmc_scene_ext));
         for (int c = 0; c < PMC_MAX_MEDIA; ++c) file->ext.phase_function[c] = int32_t((head->phase_kinds >> (8 * c)) & 0xFFu);
+        // (the velocity block, if any, starts at the first 16-byte boundary behind the layouts)
+        const uint64_t blockAt = (head->layout_offset + uint64_t(head->num_instruments) * sizeof(pmc_frame_layout) + 15) & ~uint64_t(15);
+        if (blockAt < total)
+        {
+            VelocityBlock block;
+            if (!inside(blockAt, 1, sizeof(VelocityBlock))) throw std::runtime_error(std::string(path) + ": unknown data behind the frame layouts");
+            std::memcpy(&block, base + blockAt, sizeof(block));
+            if (block.tag != VELOCITY_TAG || block.count != PMC_EXT_MAX_SOURCES || block.sizeof_velocity != sizeof(pmc_source_velocity))
+                throw std::runtime_error(std::string(path) + " was written for another version of pmc_scene_ext");
+            std::memcpy(file->ext.source_velocity, block.velocity, sizeof(block.velocity));
+        }
         file->scene = &scene;
         file->layouts = reinterpret_cast<const pmc_frame_layout*>(base + head->layout_offset);
         return file.release();

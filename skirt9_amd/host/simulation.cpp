@@ -260,9 +260,15 @@ namespace skh
         {
             _source.position = Vec3{rd.quantity(src, "positionX", "length", "0"), rd.quantity(src, "positionY", "length", "0"),
                                     rd.quantity(src, "positionZ", "length", "0")};
-            bool moving = rd.quantity(src, "velocityX", "velocity", "0") || rd.quantity(src, "velocityY", "velocity", "0")
-                          || rd.quantity(src, "velocityZ", "velocity", "0");
-            if (moving && !_oligo) unsupported("a source with a bulk velocity");
+            // SpecialtySource.cpp:31-50: the bulk velocity; none in an oligochromatic simulation
+            const double vx = rd.quantity(src, "velocityX", "velocity", "0"), vy = rd.quantity(src, "velocityY", "velocity", "0"),
+                         vz = rd.quantity(src, "velocityZ", "velocity", "0");
+            if ((vx || vy || vz) && !_oligo)
+            {
+                _source.velocity.kind = PMC_VELOCITY_CONSTANT;
+                _source.velocity.magnitude = 1.;
+                _source.velocity.vector[0] = vx, _source.velocity.vector[1] = vy, _source.velocity.vector[2] = vz;
+            }
             if (const XmlElement* ad = src.item("angularDistribution"))
             {
                 if (ad->name == "IsotropicAngularDistribution")
@@ -304,8 +310,40 @@ namespace skh
             if (auto sph = dynamic_cast<const SpheroidalGeometry*>(undecorated))
                 if (sph->inner()->type() != "SersicGeometry" && sph->inner()->type() != "PlummerGeometry")
                     unsupported("source geometry SpheroidalGeometryDecorator of " + sph->inner()->type());
-            if (src.item("velocityDistribution") && rd.quantity(src, "velocityMagnitude", "velocity", "0") && !_oligo)
-                unsupported("a source with a velocity field");
+            // GeometricSource.cpp:31-41: the velocity field; none in an oligochromatic simulation
+            if (const XmlElement* vd = src.item("velocityDistribution"))
+                if (const double magnitude = rd.quantity(src, "velocityMagnitude", "velocity", "0"); magnitude && !_oligo)
+                {
+                    pmc_source_velocity& v = _source.velocity;
+                    v.magnitude = magnitude;
+                    const XmlElement* field = vd;
+                    if (field->name == "OffsetVectorFieldDecorator")
+                    {
+                        // OffsetVectorFieldDecorator.cpp:16-21: the field about another centre
+                        v.vector[0] = rd.quantity(*field, "offsetX", "length", "0"), v.vector[1] = rd.quantity(*field, "offsetY", "length", "0"),
+                        v.vector[2] = rd.quantity(*field, "offsetZ", "length", "0");
+                        field = field->item("vectorField");
+                        if (!field) throw std::runtime_error("ski: OffsetVectorFieldDecorator lacks a vectorField");
+                    }
+                    if (field->name == "UnidirectionalVectorField")
+                    {
+                        // UnidirectionalVectorField.cpp:11-17: the same unit vector everywhere (an offset changes nothing)
+                        double x = rd.number(*field, "fieldX", "0"), y = rd.number(*field, "fieldY", "0"), z = rd.number(*field, "fieldZ", "1");
+                        const double norm = std::sqrt(x * x + y * y + z * z);
+                        if (norm == 0.) throw std::runtime_error("Field direction cannot be null vector");
+                        x /= norm, y /= norm, z /= norm;
+                        v.kind = PMC_VELOCITY_CONSTANT;
+                        v.vector[0] = x, v.vector[1] = y, v.vector[2] = z;
+                    }
+                    else if (field->name == "RadialVectorField" || field->name == "CylindricalVectorField")
+                    {
+                        v.kind = field->name == "RadialVectorField" ? PMC_VELOCITY_RADIAL : PMC_VELOCITY_CYLINDRICAL;
+                        v.unity_radius = rd.quantity(*field, "unityRadius", "length", "0");
+                        v.exponent = rd.number(*field, "exponent", "1");
+                    }
+                    else
+                        unsupported("vector field " + field->name);
+                }
         }
         else
             unsupported("source " + src.name);
@@ -447,6 +485,10 @@ namespace skh
         auto media = ms->items("media");
         if (media.empty()) unsupported("a medium system without media");
         if (media.size() > PMC_MAX_MEDIA) unsupported("a medium system with more than " + std::to_string(PMC_MAX_MEDIA) + " media");
+        // (a moving source: every emission peel-off packet has its own wavelength -- the engine keeps one cross section per observer, for one
+        // component; and the radiation field would need the packet's wavelength per path, which its log does not take)
+        if (hasMovingSources() && media.size() > 1) unsupported("a moving source together with more than one medium component");
+        if (hasMovingSources() && _storeRadiationField) unsupported("a moving source together with storeRadiationField");
         // (several components: every one a dust medium with spatially constant cross sections --
         // Configuration::hasMultipleConstantSectionMedia, MediumSystem.cpp:874-887)
         for (const XmlElement* mediumElement : media)
@@ -761,6 +803,12 @@ namespace skh
             if (lo < rangeMin) rangeMin = lo;
             if (hi > rangeMax) rangeMax = hi;
         };
+        // (a wide margin for kinematics, Configuration.cpp:573, before the grids are added)
+        if (hasMovingSources())
+        {
+            rangeMin /= (1. + 1. / 3.);
+            rangeMax *= (1. + 1. / 3.);
+        }
         std::set<double> simWavelengths;
         auto addGrid = [&](const WavelengthGrid* g) {
             extend(g->rangeMin(), g->rangeMax());
@@ -1109,6 +1157,8 @@ namespace skh
         _sceneExt = pmc_scene_ext{};
         _sceneExt.struct_size = static_cast<int32_t>(sizeof(pmc_scene_ext));
         for (size_t h = 0; h != _media.size(); ++h) _sceneExt.phase_function[h] = _media[h]->mix->phaseFunction();
+        static_assert(PMC_EXT_MAX_SOURCES >= 16, "one velocity per source of the largest source system");
+        for (size_t i = 0; i != _sources.size(); ++i) _sceneExt.source_velocity[i] = _sources[i].velocity;
 
         _scene.options = _options;
 

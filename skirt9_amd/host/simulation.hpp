@@ -25,7 +25,7 @@ namespace skh
         void setup();
 
         const pmc_scene& scene() const { return _scene; }
-        // what the scene's layout has no room for (pmc_create_ext): the phase function of every medium component
+        // what the scene's layout has no room for (pmc_create_ext): the phase function of every medium component, the velocity of every source
         const pmc_scene_ext& sceneExt() const { return _sceneExt; }
         uint64_t numPackets() const { return _numPackets; }
         int seed() const { return _seed; }
@@ -59,6 +59,13 @@ namespace skh
         const Array& numberDensity(size_t h = 0) const { return _density[h]; }
         const SourceModel& source(int h = 0) const { return _sources[h]; }
         int numSources() const { return static_cast<int>(_sources.size()); }
+        // Configuration::hasMovingSources (Configuration.cpp:79-81): some source has a velocity (never in an oligochromatic simulation)
+        bool hasMovingSources() const
+        {
+            for (const SourceModel& source : _sources)
+                if (source.velocity.kind != PMC_VELOCITY_NONE) return true;
+            return false;
+        }
 
         // optional overrides applied before setup()
         void setNumPackets(uint64_t n) { _numPackets = n; }
