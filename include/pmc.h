@@ -49,7 +49,9 @@ enum { PMC_OK = 0, PMC_ERR_INVALID = -1, PMC_ERR_UNSUPPORTED = -2, PMC_ERR_DEVIC
 
 /* ---------------------------------------------------------------- spatial grid ---- */
 
-enum { PMC_GRID_CARTESIAN = 1, PMC_GRID_OCTREE = 2, PMC_GRID_VORONOI = 3 };
+/* PMC_GRID_BINTREE (PolicyTreeSpatialGrid with treeType BinTree, BinTreeNode.cpp) uses the octree's node arrays: the
+   children of a node are 2 consecutive ids, and it splits along the axis node_level % 3 (x, y, z in turn) */
+enum { PMC_GRID_CARTESIAN = 1, PMC_GRID_OCTREE = 2, PMC_GRID_VORONOI = 3, PMC_GRID_BINTREE = 4 };
 
 /* walls in the reference's order (SKIRT/core/TreeNode.hpp enum Wall): BACK=-x, FRONT=+x, LEFT=-y, RIGHT=+y,
    BOTTOM=-z, TOP=+z */
@@ -71,7 +73,8 @@ typedef struct pmc_grid
 
     /* --- Octree: the reference's node list in node-id order (TreeSpatialGrid.cpp:38-49), flattened.
        node_box[6*id + {0..5}] = xmin,ymin,zmin,xmax,ymax,zmax exactly as the reference's TreeNode holds them;
-       node_first_child[id] = id of child 0 (children are 8 consecutive ids, OctTreeNode.cpp:22-33) or -1;
+       node_first_child[id] = id of child 0 (children are 8 consecutive ids, OctTreeNode.cpp:22-33; PMC_GRID_BINTREE: 2 consecutive
+       ids, BinTreeNode.cpp:23-49, the lower half first) or -1;
        node_cell[id] = cell index m of a leaf or -1 (TreeSpatialGrid::_cellindexv);
        neighbours of node id through wall w, in the reference's (sorted) list order (TreeNode.cpp:200-207):
        nbr_list[ nbr_start[6*id+w] .. nbr_start[6*id+w+1] )  -- a CSR over 6*num_nodes rows. */

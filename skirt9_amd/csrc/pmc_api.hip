@@ -174,7 +174,8 @@ int pmc_create_ext(const pmc_scene* scene, const pmc_scene_ext* ext, int32_t dev
     if (scene->num_media > 1 && !scene->media) return fail(PMC_ERR_INVALID, "num_media > 1 without pmc_scene::media");
     if (scene->num_instruments < 1 || scene->num_instruments > PMC_MAX_INSTRUMENTS)
         return fail(PMC_ERR_UNSUPPORTED, "between 1 and " + std::to_string(PMC_MAX_INSTRUMENTS) + " instruments are supported");
-    if (scene->grid.kind != PMC_GRID_CARTESIAN && scene->grid.kind != PMC_GRID_OCTREE && scene->grid.kind != PMC_GRID_VORONOI)
+    if (scene->grid.kind != PMC_GRID_CARTESIAN && scene->grid.kind != PMC_GRID_OCTREE && scene->grid.kind != PMC_GRID_VORONOI
+        && scene->grid.kind != PMC_GRID_BINTREE)
         return fail(PMC_ERR_UNSUPPORTED, "unsupported grid kind");
     if (scene->instruments[0].same_observer_as_preceding) return fail(PMC_ERR_INVALID, "first instrument cannot share an observer");
 
@@ -254,6 +255,11 @@ int pmc_create_ext(const pmc_scene* scene, const pmc_scene_ext* ext, int32_t dev
     else if (g.kind == PMC_GRID_VORONOI)
     {
         if ((rc = pmcUploadVoronoiGrid(ctx, scene, med))) return bail(rc);
+    }
+    else if (g.kind == PMC_GRID_BINTREE || pmcTune("PMC_TREE_AS_BINTREE") != nullptr)
+    {
+        // (an octree under the verification switch runs through the binary tree's tables and kernels: D.grid_kind becomes PMC_GRID_BINTREE)
+        if ((rc = pmcUploadBinTreeGrid(ctx, scene, med, devToCell))) return bail(rc);
     }
     else
     {

@@ -229,6 +229,8 @@ struct pmc_ctx
 // and of a Voronoi grid (cell records, neighbour entries, cone masks, tables of runs per cone and per observer)
 int pmcUploadOctreeGrid(pmc_ctx* ctx, const pmc_scene* scene, const pmc_medium& med, std::vector<int32_t>& devToCell);
 int pmcUploadVoronoiGrid(pmc_ctx* ctx, const pmc_scene* scene, const pmc_medium& med);
+// ... and of a binary tree, or of an octree that is to run through the binary tree's tables and kernels (sets DevScene::grid_kind to PMC_GRID_BINTREE)
+int pmcUploadBinTreeGrid(pmc_ctx* ctx, const pmc_scene* scene, const pmc_medium& med, std::vector<int32_t>& devToCell);
 // pmc_run.hip: the pool of packet slots
 int pmcAllocateSlots(pmc_ctx* ctx, int64_t n);
 

@@ -80,6 +80,34 @@ struct NodeRec
 };
 static_assert(sizeof(NodeRec) == 64, "NodeRec must be one 64-byte record");
 
+// Binary-tree cells (PMC_GRID_BINTREE, and an octree scene under the switch PMC_TREE_AS_BINTREE).  ONE self-contained, 128-byte-aligned
+// record per cell, cells in depth-first order of the tree: the six box doubles exactly as pmc_grid::node_box gives them, the density of
+// component 0, and one link per wall.  The record carries its own box: the step needs no coordinate table, no LDS staging and no size
+// exponents, so the depth of the tree is not limited by a packed index.
+// link (int32): >= 0 a leaf (device cell index) whose box covers the whole wall; PMC_BIN_OUTSIDE: the wall lies on the grid boundary;
+// otherwise PMC_BIN_NODE(index): the deepest internal node whose box covers the whole wall -- the walk descends below it with the child
+// rule (BinTreeNode.cpp:53-62), one BinNodeRec per level.  A link only proposes a candidate: the step accepts it when the position lies
+// strictly inside its box (leaves tile the domain, so no other leaf's closed box holds the position), else the reference's own search runs.
+#define PMC_BIN_OUTSIDE (-1)
+#define PMC_BIN_NODE(index) (-2 - (index))
+struct BinCellRec
+{
+    double  box[6];     // xmin, ymin, zmin, xmax, ymax, zmax
+    double  density;    // number density n[m] of component 0
+    int32_t link[6];    // through wall 2 * axis + side (side 0: lower wall, 1: upper wall)
+    int32_t pad[12];
+};
+static_assert(sizeof(BinCellRec) == 128, "BinCellRec must be 128 bytes");
+// one binary split: the position goes to child[0] if r[axis] < split, else to child[1] (links as in BinCellRec, never PMC_BIN_OUTSIDE)
+struct BinNodeRec
+{
+    double  split;      // CHILD_0's upper wall on the split axis
+    int32_t axis;
+    int32_t child[2];
+    int32_t pad[3];
+};
+static_assert(sizeof(BinNodeRec) == 32, "BinNodeRec must be 32 bytes");
+
 struct DevInstrument
 {
     double kx, ky, kz;
@@ -386,6 +414,12 @@ struct DevScene
     //      cycle start kernels, which run when some source moves (kin); every other scene runs the kernels that hold no trace of it
     int32_t kin;
     DevVelocity vel[PMC_MAX_SOURCES];
+    // ---- binary tree (grid_kind PMC_GRID_BINTREE; behind everything else, so that no member the other grids' kernels read moves): cell and
+    //      node records, the link of the root.  nbr_start / nbr_list (the reference's lists by device cell), cell_ext and cell_density (device
+    //      numbering) are the members above
+    const BinCellRec* bin_cells;  // [num_cells]
+    const BinNodeRec* bin_nodes;
+    int32_t bin_root;
 };
 
 // The radiation-field contributions of the propagation walks of one slot group and generation (octree): (key, value)

@@ -195,7 +195,7 @@ __constant__ DevScene c_scene[PMC_MAX_CONTEXTS];
 namespace
 {
     enum Mode : int { MODE_PASS1 = 0, MODE_PASS2 = 1, MODE_PEEL = 2, MODE_NONE = 3 };
-    enum Grid : int { GRID_CART = PMC_GRID_CARTESIAN, GRID_TREE = PMC_GRID_OCTREE, GRID_VORO = PMC_GRID_VORONOI };
+    enum Grid : int { GRID_CART = PMC_GRID_CARTESIAN, GRID_TREE = PMC_GRID_OCTREE, GRID_VORO = PMC_GRID_VORONOI, GRID_BIN = PMC_GRID_BINTREE };
     constexpr int MODE_ALIVE = 1 << 5;
     constexpr int MODE_ENDED = 1 << 6;  // the history of the slot has ended: the launch kernel takes up the next one
 
@@ -316,6 +316,11 @@ static const auto walkKernels = flavourTable<16>([](auto f) {
     constexpr int F = decltype(f)::value;
     return KernelFlavour<WalkKernel>{walkKernel<(F & 8) ? GRID_VORO : GRID_CART, (F & 1) != 0, (F & 2) != 0, (F & 4) != 0>, 0};
 });
+// generic walks on a binary tree (a table of its own: the entries of the table above stay what they were)
+static const auto binWalkKernels = flavourTable<8>([](auto f) {
+    constexpr int F = decltype(f)::value;
+    return KernelFlavour<WalkKernel>{walkKernel<GRID_BIN, (F & 1) != 0, (F & 2) != 0, (F & 4) != 0>, 0};
+});
 // Voronoi propagation on the table of runs: static LDS only (launched without dynamic LDS; its limit is never raised)
 typedef void (*VoroPropKernel)(int, const int32_t*, const unsigned long long*, unsigned long long*, int, uint64_t);
 static const auto voroPropKernels = flavourTable<8>([](auto f) {
@@ -371,7 +376,7 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
         if (e != hipSuccess) return e;
     }
     for (hipError_t e : {raiseLdsLimits(peelKernels, walkMax), raiseLdsLimits(peel2Kernels, walkMax), raiseLdsLimits(propKernels, walkMax),
-                         raiseLdsLimits(walkKernels, walkMax)})
+                         raiseLdsLimits(walkKernels, walkMax), raiseLdsLimits(binWalkKernels, walkMax)})
         if (e != hipSuccess) return e;
     const struct
     {
@@ -383,6 +388,7 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
                {reinterpret_cast<const void*>(&traceTreeKernel<true, true>), walkMax},
                {reinterpret_cast<const void*>(&traceRayKernel<GRID_CART>), walkMax},
                {reinterpret_cast<const void*>(&traceRayKernel<GRID_VORO>), walkMax},
+               {reinterpret_cast<const void*>(&traceRayKernel<GRID_BIN>), walkMax},
                {reinterpret_cast<const void*>(&transitionKernel), transitionMax},
                {reinterpret_cast<const void*>(&transitionDipoleKernel), transitionMax},
                {reinterpret_cast<const void*>(&transitionKinKernel), transitionMax},
@@ -394,7 +400,9 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_VORO, true>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_TREE>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_CART>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
-               {reinterpret_cast<const void*>(&cycleStartKernel<GRID_VORO>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)}};
+               {reinterpret_cast<const void*>(&cycleStartKernel<GRID_VORO>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
+               {reinterpret_cast<const void*>(&cycleStartKernel<GRID_BIN, true>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
+               {reinterpret_cast<const void*>(&cycleStartKernel<GRID_BIN>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)}};
     for (const auto& k : all)
     {
         hipError_t e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
@@ -429,6 +437,8 @@ extern "C" int pmcWalkBlocksPerCU(int gridKind, int kind, int wide, int block, s
         if (pmcPropHasCheckpoints(0, ldsBytes)) ldsBytes = ((ldsBytes + 15) & ~size_t(15)) + PROP_CKPT_BYTES;
         kernel = reinterpret_cast<const void*>(propKernels[wide ? 8 : 0].kernel);
     }
+    else if (gridKind == PMC_GRID_BINTREE)
+        kernel = reinterpret_cast<const void*>(binWalkKernels[0].kernel);
     else
         kernel = reinterpret_cast<const void*>(walkKernels[gridKind == PMC_GRID_VORONOI ? 8 : 0].kernel);
     int n = 0;
@@ -453,7 +463,7 @@ extern "C" hipError_t pmcLaunchWalk(int slot, int gridKind, int flavour, int tas
     WalkStreamArgs ws;
     std::memset(&ws, 0, sizeof(ws));
     if (tasks) ws = *tasks;
-    const WalkKernel kernel = walkKernels[(flavour & 7) | (gridKind == PMC_GRID_VORONOI ? 8 : 0)].kernel;
+    const WalkKernel kernel = gridKind == PMC_GRID_BINTREE ? binWalkKernels[flavour & 7].kernel : walkKernels[(flavour & 7) | (gridKind == PMC_GRID_VORONOI ? 8 : 0)].kernel;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), ldsBytes, stream, slot, taskBase, numTaskRecords, taskCounter, seed, ws);
     return hipGetLastError();
 }
@@ -649,8 +659,10 @@ extern "C" hipError_t pmcLaunchCycleStart(int slot, int gridKind, int kin, int s
         ldsBytes = size_t(ps.ldsOffset) + size_t(ps.numObs + (ps.propIndex >= 0 ? 1 : 0)) * PEEL_SORT_PARTS * sizeof(uint32_t);
     }
     const int grid = std::max(1, std::min(((listIn ? listLen : numSlots) + 255) / 256, maxBlocks));
-    const auto kernel = kin ? (gridKind == PMC_GRID_OCTREE ? cycleStartKernel<GRID_TREE, true> : gridKind == PMC_GRID_VORONOI ? cycleStartKernel<GRID_VORO, true> : cycleStartKernel<GRID_CART, true>)
-                            : (gridKind == PMC_GRID_OCTREE ? cycleStartKernel<GRID_TREE> : gridKind == PMC_GRID_VORONOI ? cycleStartKernel<GRID_VORO> : cycleStartKernel<GRID_CART>);
+    const auto kernel = kin ? (gridKind == PMC_GRID_OCTREE ? cycleStartKernel<GRID_TREE, true> : gridKind == PMC_GRID_VORONOI ? cycleStartKernel<GRID_VORO, true>
+                               : gridKind == PMC_GRID_BINTREE ? cycleStartKernel<GRID_BIN, true> : cycleStartKernel<GRID_CART, true>)
+                            : (gridKind == PMC_GRID_OCTREE ? cycleStartKernel<GRID_TREE> : gridKind == PMC_GRID_VORONOI ? cycleStartKernel<GRID_VORO>
+                               : gridKind == PMC_GRID_BINTREE ? cycleStartKernel<GRID_BIN> : cycleStartKernel<GRID_CART>);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), ldsBytes, stream, slot, slotBase, numSlots, listCounter, listOut, listIn, listLen, ps);
     return hipGetLastError();
 }
@@ -707,7 +719,7 @@ extern "C" hipError_t pmcLaunchTrace(int slot, int gridKind, int wide, int unifo
         hipLaunchKernelGGL(kernel, dim3(1), dim3(64), ldsBytes, stream, slot, r[0], r[1], r[2], k[0], k[1], k[2], kdev, m, ds, cap, n);
     }
     else
-        hipLaunchKernelGGL(gridKind == PMC_GRID_VORONOI ? traceRayKernel<GRID_VORO> : traceRayKernel<GRID_CART>, dim3(1), dim3(64), ldsBytes, stream, slot, r[0],
+        hipLaunchKernelGGL(gridKind == PMC_GRID_VORONOI ? traceRayKernel<GRID_VORO> : gridKind == PMC_GRID_BINTREE ? traceRayKernel<GRID_BIN> : traceRayKernel<GRID_CART>, dim3(1), dim3(64), ldsBytes, stream, slot, r[0],
                            r[1], r[2], k[0], k[1], k[2], m, ds, cap, n);
     return hipGetLastError();
 }

@@ -4,6 +4,7 @@
 // subdivision, OctTreeNode.cpp:22-33), build that table from the reference's own doubles, and replace the per-wall neighbour lists by links
 // (per wall: the neighbour leaf covering it, or the internal node below which finer neighbours are found).  The reference lists themselves
 // are uploaded too, re-indexed by cell, for the exact fallback path.
+// Binary tree: self-contained cell records with one link per wall, and the table of binary splits (pmcUploadBinTreeGrid).
 // Voronoi: cell records, neighbour entries, cone masks, and the tables of runs that the walk kernels read (per direction cone, per observer).
 #include "pmc_context.h"
 
@@ -306,6 +307,154 @@ int pmcUploadOctreeGrid(pmc_ctx* ctx, const pmc_scene* scene, const pmc_medium& 
         // (levels 13-20: 0.2 ... 25 MB: not in LDS; the walk reads the six walls of a step from global memory)
         D.tab_in_lds = T.lmax <= 12 ? 1 : 0;
         D.lds_grid_len = D.tab_in_lds ? 3 * T.tabn : 0;
+    return rc;
+}
+
+// Binary tree (PMC_GRID_BINTREE), or -- under the switch PMC_TREE_AS_BINTREE -- an octree whose every node enters the table of binary nodes
+// as its three levels of splits (x, then y, then z, at CHILD_0's upper corner: the doubles and the `<` decisions of OctTreeNode::child,
+// OctTreeNode.cpp:37-42).  Cell records: the node boxes as they come, one link per wall; the reference's neighbour lists re-indexed by
+// cell for the exact fallback path (pmc_device.h BinCellRec, BinNodeRec; pmc_walk_bin.inc).
+int pmcUploadBinTreeGrid(pmc_ctx* ctx, const pmc_scene* scene, const pmc_medium& med, std::vector<int32_t>& devToCell)
+{
+    DevScene& D = ctx->dev;
+    const pmc_grid& g = scene->grid;
+    const int fan = g.kind == PMC_GRID_BINTREE ? 2 : 8;  // children of a subdivided node (consecutive ids)
+    const int numNodes = g.num_nodes, numCells = g.num_cells;
+    if (numNodes < 1 || numCells < 1 || !g.node_box || !g.node_level || !g.node_first_child || !g.node_cell || !g.nbr_start || !g.nbr_list)
+        return fail(PMC_ERR_INVALID, "tree grid tables are missing");
+    if (size_t(numCells) > PMC_LINK_MAX_INDEX) return fail(PMC_ERR_UNSUPPORTED, "tree with 2^25 cells or more");
+    if (g.node_level[0] != 0) return fail(PMC_ERR_INVALID, "tree root is not at level 0");
+    // device numbering of the cells: depth-first order of the tree, children in child order (siblings are neighbours in the table)
+    std::vector<int32_t> perm(numCells, -1), internalIndex(numNodes, -1), nodeOfCell(numCells, -1);
+    int numInternal = 0;
+    {
+        int next = 0;
+        size_t visited = 0;
+        std::vector<int> stack{0};
+        while (!stack.empty())
+        {
+            const int id = stack.back();
+            stack.pop_back();
+            if (++visited > size_t(numNodes)) return fail(PMC_ERR_INVALID, "tree child links form no tree");
+            const int first = g.node_first_child[id];
+            if (first < 0)
+            {
+                const int m = g.node_cell[id];
+                if (m < 0 || m >= numCells || perm[m] >= 0) return fail(PMC_ERR_INVALID, "tree leaf without a valid cell index");
+                perm[m] = next++;
+                nodeOfCell[m] = id;
+                continue;
+            }
+            if (first < 1 || first + fan > numNodes) return fail(PMC_ERR_INVALID, "tree child index out of range");
+            internalIndex[id] = numInternal++;
+            for (int l = fan - 1; l >= 0; --l)
+            {
+                if (g.node_level[first + l] != g.node_level[id] + 1) return fail(PMC_ERR_INVALID, "tree child level mismatch");
+                stack.push_back(first + l);
+            }
+        }
+        if (next != numCells || visited != size_t(numNodes)) return fail(PMC_ERR_INVALID, "tree leaves and cells do not match");
+    }
+    const int perNode = fan == 2 ? 1 : 7;  // binary node records per subdivided node
+    if (size_t(numInternal) * perNode > size_t(0x7FFFFFF0)) return fail(PMC_ERR_UNSUPPORTED, "tree with too many nodes");
+    auto linkOf = [&](int id) -> int32_t {
+        return g.node_first_child[id] < 0 ? perm[g.node_cell[id]] : PMC_BIN_NODE(internalIndex[id] * perNode);
+    };
+    std::vector<BinNodeRec> nodes(size_t(numInternal) * perNode, BinNodeRec{});
+    for (int id = 0; id < numNodes; ++id)
+    {
+        const int first = g.node_first_child[id];
+        if (first < 0) continue;
+        const double* c0 = g.node_box + 6 * size_t(first);  // CHILD_0
+        BinNodeRec* rec = &nodes[size_t(internalIndex[id]) * perNode];
+        if (fan == 2)
+        {
+            const int axis = g.node_level[id] % 3;
+            rec[0].split = c0[3 + axis];
+            rec[0].axis = axis;
+            rec[0].child[0] = linkOf(first), rec[0].child[1] = linkOf(first + 1);
+            continue;
+        }
+        // octree: record 0 decides x, records 1 + ix decide y, records 3 + ix + 2 iy decide z and name the child ix + 2 iy + 4 iz
+        const int32_t base = internalIndex[id] * perNode;
+        rec[0].split = c0[3], rec[0].axis = 0;
+        rec[0].child[0] = PMC_BIN_NODE(base + 1), rec[0].child[1] = PMC_BIN_NODE(base + 2);
+        for (int ix = 0; ix < 2; ++ix)
+        {
+            BinNodeRec& y = rec[1 + ix];
+            y.split = c0[4], y.axis = 1;
+            for (int iy = 0; iy < 2; ++iy)
+            {
+                y.child[iy] = PMC_BIN_NODE(base + 3 + ix + 2 * iy);
+                BinNodeRec& z = rec[3 + ix + 2 * iy];
+                z.split = c0[5], z.axis = 2;
+                for (int iz = 0; iz < 2; ++iz) z.child[iz] = linkOf(first + ix + 2 * iy + 4 * iz);
+            }
+        }
+    }
+    const int32_t rootLink = linkOf(0);
+    // the link through a wall of a leaf: the deepest node whose box covers the whole wall from the other side -- a leaf, or the internal node
+    // whose split cuts the wall (finer neighbours: the walk descends with its position).  Descent by the split records alone: along the wall's
+    // axis the side just beyond the wall decides, across it the wall's extent
+    auto wallLink = [&](const double* box, int wall) -> int32_t {
+        const int axis = wall >> 1, side = wall & 1;
+        const double c = box[3 * side + axis];
+        const double bound = side ? (axis == 0 ? g.xmax : axis == 1 ? g.ymax : g.zmax) : (axis == 0 ? g.xmin : axis == 1 ? g.ymin : g.zmin);
+        if (c == bound) return PMC_BIN_OUTSIDE;
+        int32_t link = rootLink;
+        while (link < PMC_BIN_OUTSIDE)
+        {
+            const BinNodeRec& n = nodes[size_t(-2 - link)];
+            if (n.axis == axis)
+                link = n.child[side ? (c < n.split ? 0 : 1) : (c <= n.split ? 0 : 1)];
+            else if (box[3 + n.axis] <= n.split)
+                link = n.child[0];
+            else if (box[n.axis] >= n.split)
+                link = n.child[1];
+            else
+                break;
+        }
+        return link;
+    };
+    std::vector<BinCellRec> cells(size_t(numCells), BinCellRec{});
+    std::vector<double> density(size_t(numCells), 0.);
+    std::vector<int32_t> nbrStart(6 * size_t(numCells) + 1, 0), nbrList;
+    std::vector<int32_t> cellExt(numCells, -1);
+    for (int m = 0; m < numCells; ++m) cellExt[perm[m]] = m;
+    for (int dev = 0; dev < numCells; ++dev)
+    {
+        const int m = cellExt[dev];
+        const int id = nodeOfCell[m];
+        BinCellRec& rec = cells[dev];
+        std::memcpy(rec.box, g.node_box + 6 * size_t(id), sizeof(rec.box));
+        rec.density = density[dev] = med.number_density[m];
+        for (int wall = 0; wall < 6; ++wall)
+        {
+            rec.link[wall] = wallLink(rec.box, wall);
+            nbrStart[6 * size_t(dev) + wall] = (int32_t)nbrList.size();
+            for (int q = g.nbr_start[6 * size_t(id) + wall]; q < g.nbr_start[6 * size_t(id) + wall + 1]; ++q)
+            {
+                const int nb = g.nbr_list[q];
+                if (nb < 0 || nb >= numNodes || g.node_first_child[nb] >= 0)
+                    return fail(PMC_ERR_INVALID, "neighbour list of a leaf contains a non-leaf node");
+                nbrList.push_back(perm[g.node_cell[nb]]);
+            }
+        }
+    }
+    nbrStart[6 * size_t(numCells)] = (int32_t)nbrList.size();
+    int rc = PMC_OK;
+    if ((rc = ctx->upload(cells.data(), cells.size(), &D.bin_cells))) return rc;
+    if ((rc = ctx->upload(nodes.data(), nodes.size(), &D.bin_nodes))) return rc;
+    if ((rc = ctx->upload(density.data(), density.size(), &D.cell_density))) return rc;
+    if ((rc = ctx->upload(nbrStart.data(), nbrStart.size(), &D.nbr_start))) return rc;
+    if ((rc = ctx->upload(nbrList.data(), nbrList.size(), &D.nbr_list))) return rc;
+    if ((rc = ctx->upload(cellExt.data(), cellExt.size(), &D.cell_ext))) return rc;
+    D.bin_root = rootLink;
+    D.cell_slots = numCells;
+    D.grid_kind = PMC_GRID_BINTREE;  // (also for an octree scene under the switch: every kernel and the run loop see a binary tree)
+    D.lds_grid_len = 0;
+    D.lmax = 0;
+    devToCell = cellExt;
     return rc;
 }
 

@@ -934,7 +934,7 @@
         cnt.paths += 1;
         int located;
         const bool ok = startWalk<GRID>(S, G, w, (GRID == GRID_CART) ? -1 : hint, located, GRID == GRID_VORO && deferScan);
-        if (GRID == GRID_TREE && located >= 0) hint = located;
+        if ((GRID == GRID_TREE || GRID == GRID_BIN) && located >= 0) hint = located;
         if (zeroPeel || !ok)
         {
             if (record == 0)

@@ -706,6 +706,8 @@
         return voroLocateAndEnter(S, w);
     }
 
+#include "pmc_walk_bin.inc"
+
     // ------------------------------------------------------------------------------------------------
     // PathSegmentGenerator::moveInside (PathSegmentGenerator.cpp:11-112); returns false if the path misses the grid;
     // cumds receives the length of the initial segment outside the grid
@@ -808,6 +810,13 @@
             }
             return voroLocateAndEnter(S, w, (hint >= 0 && cumds == 0.) ? hint : -2);
         }
+        else if (GRID == GRID_BIN)
+        {
+            // (moveInside guarantees that r is inside the closed root box: the search finds a leaf)
+            binStart(S, w, hint);
+            if (cumds == 0.) located = w.cell;
+            return true;
+        }
         else
         {
             const char* leaves = reinterpret_cast<const char*>(S.leaves);
@@ -877,6 +886,13 @@
             w.dens = S.vsite[4 * (int64_t)w.cell + 3];
         }
         w.axis = (bits >> 2) & 3u;
+        if (GRID == GRID_BIN)
+        {
+            // the cell's density and its link through the exit wall of the first segment (the sign bit of the exit axis is in the record)
+            const BinCellRec* rec = S.bin_cells + w.cell;
+            w.dens = rec->density;
+            w.ci = rec->link[2 * w.axis + (((bits >> (4 + w.axis)) & 1u) ? 0 : 1)];
+        }
         w.sgn = (bits >> 4) & 7u;
         w.tau = 0.;
         w.lastm = -1;
@@ -1154,7 +1170,7 @@
         if (lane == 0 && v) atomicAdd(S.counters + 6, v);
     }
 
-    // Generic walk kernel of the Cartesian and Voronoi grids (the octree has its own kernels, pmc_walk_tree.inc): persistent
+    // Generic walk kernel of the Cartesian, Voronoi and binary-tree grids (the octree has its own kernels, pmc_walk_tree.inc): persistent
     // wavefronts, one walk per lane; a lane runs the task records of a slot one after the other (record 0: propagation
     // walk, continued from pass 1 into pass 2; record 1 + g: peel-off walk towards observer g).
     // RF: the forced-scattering path walk (pass 1) also stores the radiation field (MonteCarloSimulation.cpp:638-662)
@@ -1226,6 +1242,7 @@
             if (service)
             {
                 if (GRID == GRID_VORO && st == ST_SLOW) st = voroStepSlow(S, w) ? ST_ACTIVE : ST_EXIT;
+                if (GRID == GRID_BIN && st == ST_SLOW) st = binStepSlow(S, w) ? ST_ACTIVE : ST_EXIT;
                 // ---- finished walks: results (stores only), and what the lane does next:
                 //      again: pass 1 ended with tau_path > 0 -> pass 2 over the same path (record 0 again)
                 //      chain: the slot has another record of this cycle -> that walk
@@ -1392,7 +1409,8 @@
                         {
                             double extEnd;
                             const double rfValue = rfSegment<EA>(rfL, rfExtBeg, tau0, tabs0, tau1, tabs1, ds, extEnd);
-                            if (rfEll >= 0) unsafeAtomicAdd(S.rf + ((int64_t)w.cell * S.rf_num_lambda + rfEll), rfValue);
+                            // (binary tree: the table counts cells in the caller's numbering)
+                            if (rfEll >= 0) unsafeAtomicAdd(S.rf + ((int64_t)(GRID == GRID_BIN ? S.cell_ext[w.cell] : w.cell) * S.rf_num_lambda + rfEll), rfValue);
                             rfExtBeg = extEnd;
                         }
                         if (GRID == GRID_VORO)
@@ -1401,6 +1419,8 @@
                             enter = w.ci;
                             if (enter < 0) st = ST_EXIT;
                         }
+                        else if (GRID == GRID_BIN)
+                            st = binAdvance(S, w);
                         else
                         {
                             if (!cartAdvance(S, L, w)) st = ST_EXIT;
@@ -2165,7 +2185,7 @@
     }
 
     // ================================================================================================
-    //  single-ray tracer (Cartesian and Voronoi grids; the octree's is in pmc_walk_tree.inc): the same traversal code,
+    //  single-ray tracer (Cartesian, Voronoi and binary-tree grids; the octree's is in pmc_walk_tree.inc): the same traversal code,
     //  one lane, (m, ds) written out
     // ================================================================================================
     template<int GRID> __global__ void traceRayKernel(const int sceneSlot, double rx, double ry, double rz, double kx, double ky,
@@ -2204,6 +2224,8 @@
                 w.ck = locateClip(L.grid + (S.nx + 1) + (S.ny + 1), S.nz + 1, w.rz);
                 cartEnter(S, L, w);
             }
+            else if (GRID == GRID_BIN)
+                binStart(S, w, -1);
             else
                 ok = voroLocateAndEnter(S, w);
             bool inside = ok;
@@ -2212,11 +2234,17 @@
             {
                 if (n < cap)
                 {
-                    mOut[n] = w.cell;
+                    mOut[n] = GRID == GRID_BIN ? S.cell_ext[w.cell] : w.cell;
                     dsOut[n] = w.ds;
                 }
                 ++n;
-                if (GRID == GRID_VORO)
+                if (GRID == GRID_BIN)
+                {
+                    // (the step of the walk kernel, and its service round for an undecided one)
+                    const int r = binAdvance(S, w);
+                    inside = r == ST_ACTIVE || (r == ST_SLOW && binStepSlow(S, w));
+                }
+                else if (GRID == GRID_VORO)
                 {
                     const int r = voroAdvance(S, w);
                     if (r == ST_SLOW)

@@ -771,6 +771,7 @@ namespace skh
     //                                           + OctTreeNode::addNeighbors (OctTreeNode.cpp:45-138)
     void OctreeSpatialGrid::subdivide(int id)
     {
+        if (binary) return subdivideBinary(id);
         int first = static_cast<int>(nodes.size());
         {
             const Box b = nodes[id].box;
@@ -813,6 +814,61 @@ namespace skh
                     bool ok1 = ((l >> a1) & 1) ? (hi(nb, a1) >= split[a1]) : (lo(nb, a1) <= split[a1]);
                     bool ok2 = ((l >> a2) & 1) ? (hi(nb, a2) >= split[a2]) : (lo(nb, a2) <= split[a2]);
                     if (ok1 && ok2) makeNeighbors(nodes, complementWall[wall], neighbor, first + l);
+                }
+            }
+        }
+    }
+
+    // TreeNode::subdivide (TreeNode.cpp:78-83) = BinTreeNode::createChildren (BinTreeNode.cpp:23-49)
+    //                                           + BinTreeNode::addNeighbors (BinTreeNode.cpp:66-263)
+    void OctreeSpatialGrid::subdivideBinary(int id)
+    {
+        const int child0 = static_cast<int>(nodes.size()), child1 = child0 + 1;
+        const int dir = nodes[id].level % 3;  // XDIR, YDIR, ZDIR
+        {
+            const Box b = nodes[id].box;
+            const Vec3 rc = b.center();
+            Box lower = b, upper = b;
+            if (dir == 0) lower.xmax = upper.xmin = rc.x;
+            if (dir == 1) lower.ymax = upper.ymin = rc.y;
+            if (dir == 2) lower.zmax = upper.zmin = rc.z;
+            for (const Box& box : {lower, upper})
+            {
+                Node child;
+                child.box = box;
+                child.level = nodes[id].level + 1;
+                child.parent = id;
+                nodes.push_back(std::move(child));
+            }
+            nodes[id].firstChild = child0;
+        }
+        const double split = hi(nodes[child0].box, dir);
+        const int lowerWall = 2 * dir, upperWall = 2 * dir + 1;  // BACK/FRONT, LEFT/RIGHT, BOTTOM/TOP
+
+        // internal neighbours
+        makeNeighbors(nodes, upperWall, child0, child1);
+
+        // the outer neighbours of this node, wall by wall in the order BACK, FRONT, LEFT, RIGHT, BOTTOM, TOP
+        for (int wall = 0; wall < 6; ++wall)
+        {
+            const std::vector<int> list = nodes[id].neighbors[wall];
+            for (int neighbor : list)
+            {
+                // (the ZDIR branch first deletes this node from the neighbour's BOTTOM list as well -- for the TOP wall twice, and
+                //  instead of the BOTTOM wall's complement: BinTreeNode.cpp:204-259, kept as it stands)
+                if (dir == 2) deleteNeighbor(nodes, neighbor, PMC_WALL_BOTTOM, id);
+                if (dir == 2 && wall == PMC_WALL_TOP)
+                    deleteNeighbor(nodes, neighbor, PMC_WALL_BOTTOM, id);
+                else
+                    deleteNeighbor(nodes, neighbor, complementWall[wall], id);
+                if (wall == lowerWall)
+                    makeNeighbors(nodes, complementWall[wall], neighbor, child0);
+                else if (wall == upperWall)
+                    makeNeighbors(nodes, complementWall[wall], neighbor, child1);
+                else
+                {
+                    if (lo(nodes[neighbor].box, dir) <= split) makeNeighbors(nodes, complementWall[wall], neighbor, child0);
+                    if (hi(nodes[neighbor].box, dir) >= split) makeNeighbors(nodes, complementWall[wall], neighbor, child1);
                 }
             }
         }
@@ -1004,6 +1060,7 @@ namespace skh
 
     void OctreeSpatialGrid::setupFromTopology(const std::vector<char>& topology)
     {
+        if (binary) throw std::runtime_error("a tree topology file is not supported with treeType BinTree");
         // first pass: depth-first reconstruction of parent/child relations on temporary ids
         struct Tmp
         {
@@ -1103,7 +1160,7 @@ namespace skh
 
     void OctreeSpatialGrid::fill(pmc_grid& g) const
     {
-        g.kind = PMC_GRID_OCTREE;
+        g.kind = binary ? PMC_GRID_BINTREE : PMC_GRID_OCTREE;
         g.num_nodes = static_cast<int32_t>(nodes.size());
         g.node_box = flatBox.data();
         g.node_level = flatLevel.data();

@@ -532,8 +532,8 @@ namespace skh
         void fill(pmc_grid& g) const override;
     };
 
-    // PolicyTreeSpatialGrid (treeType OctTree) with DensityTreePolicy
-    // TreeSpatialGrid.cpp:23-78, TreeNode.cpp, OctTreeNode.cpp:22-138, DensityTreePolicy.cpp:117-309
+    // PolicyTreeSpatialGrid (treeType OctTree or BinTree) with DensityTreePolicy
+    // TreeSpatialGrid.cpp:23-78, TreeNode.cpp, OctTreeNode.cpp:22-138, BinTreeNode.cpp:23-263, DensityTreePolicy.cpp:117-309
     class OctreeSpatialGrid : public SpatialGrid
     {
     public:
@@ -541,6 +541,8 @@ namespace skh
         int minLevel{3}, maxLevel{7};
         double maxDustFraction{1e-6}, maxDustOpticalDepth{0}, policyWavelength{0.55e-6}, maxDustDensityDispersion{0};
         double maxElectronFraction{1e-6};
+        // treeType BinTree: a node splits in two along x, y, z in turn (level % 3); levels then count binary splits
+        bool binary{false};
 
         struct Node
         {
@@ -568,6 +570,7 @@ namespace skh
 
     private:
         void subdivide(int id);
+        void subdivideBinary(int id);
         void finish();
     };
 

@@ -83,7 +83,7 @@ namespace
     template<typename F> void visitScene(pmc_scene& s, F&& f)
     {
         pmc_grid& g = s.grid;
-        const bool cart = g.kind == PMC_GRID_CARTESIAN, tree = g.kind == PMC_GRID_OCTREE, voro = g.kind == PMC_GRID_VORONOI;
+        const bool cart = g.kind == PMC_GRID_CARTESIAN, tree = g.kind == PMC_GRID_OCTREE || g.kind == PMC_GRID_BINTREE, voro = g.kind == PMC_GRID_VORONOI;
         f(g.xv, cart ? size_t(g.nx) + 1 : 0);
         f(g.yv, cart ? size_t(g.ny) + 1 : 0);
         f(g.zv, cart ? size_t(g.nz) + 1 : 0);

@@ -656,8 +656,10 @@ namespace skh
         }
         else if (ge->name == "PolicyTreeSpatialGrid")
         {
-            if (ge->attr("treeType", "OctTree") != "OctTree") unsupported("treeType " + ge->attr("treeType"));
+            const std::string treeType = ge->attr("treeType", "OctTree");
+            if (treeType != "OctTree" && treeType != "BinTree") unsupported("treeType " + treeType);
             auto grid = std::make_unique<OctreeSpatialGrid>();
+            grid->binary = treeType == "BinTree";
             grid->extent = extent;
             if (const XmlElement* pol = ge->item("policy"))
             {
@@ -1239,9 +1241,9 @@ namespace skh
         std::ostringstream s;
         s << "simulation " << _prefix << ": " << (_oligo ? "oligochromatic" : "panchromatic") << ", " << _numPackets
           << " packets, seed " << _seed << "\n";
-        s << "  grid: " << (_scene.grid.kind == PMC_GRID_CARTESIAN ? "Cartesian" : _scene.grid.kind == PMC_GRID_VORONOI ? "Voronoi" : "octree") << " with " << _scene.grid.num_cells
+        s << "  grid: " << (_scene.grid.kind == PMC_GRID_CARTESIAN ? "Cartesian" : _scene.grid.kind == PMC_GRID_VORONOI ? "Voronoi" : _scene.grid.kind == PMC_GRID_BINTREE ? "binary tree" : "octree") << " with " << _scene.grid.num_cells
           << " cells";
-        if (_scene.grid.kind == PMC_GRID_OCTREE) s << " (" << _scene.grid.num_nodes << " nodes)";
+        if (_scene.grid.kind == PMC_GRID_OCTREE || _scene.grid.kind == PMC_GRID_BINTREE) s << " (" << _scene.grid.num_nodes << " nodes)";
         s << "\n  dust table: " << _scene.medium.num_lambda << " wavelengths; setup draws: " << _random.draws() << "\n";
         s << "  instruments: " << _instruments.size() << "; frame buffer: " << _frameSize << " doubles\n";
         return s.str();
