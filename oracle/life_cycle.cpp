@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <limits>
 #include <memory>
@@ -519,15 +520,25 @@ namespace
             const double* b = g.node_box + 6 * size_t(id);
             return BoxD{b[0], b[1], b[2], b[3], b[4], b[5]};
         }
-        // TreeNode::leafChild (TreeNode.cpp:66-76) with OctTreeNode::child (OctTreeNode.cpp:36-41)
+        // TreeNode::leafChild (TreeNode.cpp:66-76) with OctTreeNode::child (OctTreeNode.cpp:36-41) or, for PMC_GRID_BINTREE,
+        // BinTreeNode::child (BinTreeNode.cpp:53-62): two children, split along the axis level % 3
         int leafChild(int id, double x, double y, double z) const
         {
             if (!box(id).contains(x, y, z)) return -1;
+            const bool binary = g.kind == PMC_GRID_BINTREE;
             while (g.node_first_child[id] >= 0)
             {
                 int first = g.node_first_child[id];
                 const double* c0 = g.node_box + 6 * size_t(first);  // child 0: its rmax is the split point
-                int l = (x < c0[3] ? 0 : 1) + (y < c0[4] ? 0 : 2) + (z < c0[5] ? 0 : 4);
+                int l;
+                if (binary)
+                {
+                    const int axis = g.node_level[id] % 3;
+                    const double v = axis == 0 ? x : axis == 1 ? y : z;
+                    l = v < c0[3 + axis] ? 0 : 1;
+                }
+                else
+                    l = (x < c0[3] ? 0 : 1) + (y < c0[4] ? 0 : 2) + (z < c0[5] ? 0 : 4);
                 id = first + l;
             }
             return id;
@@ -614,6 +625,9 @@ namespace
     {
         V3 r{0, 0, 0}, k{0, 0, 1};
         double lambda{0}, W{0}, D{0};
+        double lambda0{0};                   // the wavelength as sampled from the source, before its Doppler shift (PhotonPacket::_lambda0)
+        bool moving{false};                  // launched by a source with a bulk velocity (PhotonPacket::_bvi)
+        V3 velocity{0, 0, 0};                //   that velocity at the launch position
         int nscatt{0};
         uint64_t historyIndex{0};
         bool hasObservedOpticalDepth{false};
@@ -683,9 +697,42 @@ namespace
             std::vector<Contribution> contributions;
         };
         std::vector<ContributionList> lists;
+        // the scene's extension (pmc.h pmc_scene_ext); without one every component is Henyey-Greenstein and every source at rest
+        int32_t phaseKind[PMC_MAX_MEDIA];
+        pmc_source_velocity sourceVelocity[PMC_EXT_MAX_SOURCES];
+
+        // reads the extension as pmc_create_ext does: members beyond struct_size do not exist; PMC_OK, or the status pmc_create_ext returns
+        int readExtension(const pmc_scene_ext* ext)
+        {
+            if (!ext) return PMC_OK;
+            if (ext->struct_size < int32_t(sizeof(int32_t))) return PMC_ERR_INVALID;
+            const int components = sc.num_media > 1 ? sc.num_media : 1;
+            for (int h = 0; h < components && h < PMC_MAX_MEDIA; ++h)
+            {
+                if (size_t(ext->struct_size) < offsetof(pmc_scene_ext, phase_function) + sizeof(int32_t) * size_t(h + 1)) break;
+                phaseKind[h] = ext->phase_function[h];
+                if (phaseKind[h] != PMC_PHASE_HG && phaseKind[h] != PMC_PHASE_DIPOLE) return PMC_ERR_UNSUPPORTED;
+            }
+            bool moving = false;
+            const int sources = sc.num_sources > 1 ? sc.num_sources : 1;
+            for (int i = 0; i < sources && i < PMC_EXT_MAX_SOURCES; ++i)
+            {
+                if (size_t(ext->struct_size) < offsetof(pmc_scene_ext, source_velocity) + sizeof(pmc_source_velocity) * size_t(i + 1)) break;
+                sourceVelocity[i] = ext->source_velocity[i];
+                if (sourceVelocity[i].kind < PMC_VELOCITY_NONE || sourceVelocity[i].kind > PMC_VELOCITY_CYLINDRICAL) return PMC_ERR_UNSUPPORTED;
+                // (SpecialtySource.cpp:34-44, GeometricSource.cpp:31-41: no velocity in an oligochromatic simulation)
+                const pmc_source& src = sc.num_sources > 1 ? sc.sources[i] : sc.source;
+                if (src.lambda_mode == PMC_LAMBDA_OLIGO) sourceVelocity[i] = pmc_source_velocity{};
+                if (sourceVelocity[i].kind != PMC_VELOCITY_NONE) moving = true;
+            }
+            if (moving && (sc.num_media > 1 || sc.radiation_field.store)) return PMC_ERR_UNSUPPORTED;
+            return PMC_OK;
+        }
 
         LifeCycle(const pmc_scene& scene, Rng& r, double* f) : sc(scene), rng(r), frames(f)
         {
+            for (int h = 0; h != PMC_MAX_MEDIA; ++h) phaseKind[h] = PMC_PHASE_HG;
+            std::memset(sourceVelocity, 0, sizeof(sourceVelocity));
             if (sc.grid.kind == PMC_GRID_CARTESIAN)
                 generator.reset(new CartesianGenerator(sc.grid));
             else if (sc.grid.kind == PMC_GRID_VORONOI)
@@ -714,6 +761,35 @@ namespace
         {
             double n = sc.medium.number_density[m];
             return n > 0. ? n * sigma[indexForLambda(lambda)] : 0.;
+        }
+
+        // ---- the bulk velocity of a source at the launch position: magnitude * field(r) (GeometricSource.cpp:66-82 with
+        //      UnidirectionalVectorField.cpp:28-31, RadialVectorField.cpp:17-35, CylindricalVectorField.cpp:17-36,
+        //      OffsetVectorFieldDecorator.cpp:16-21; a PointSource's own velocity is magnitude 1 times the vector, SpecialtySource.cpp:48-51)
+        static V3 velocityAt(const pmc_source_velocity& V, V3 r)
+        {
+            V3 u{V.vector[0], V.vector[1], V.vector[2]};
+            if (V.kind != PMC_VELOCITY_CONSTANT)
+            {
+                const double x = r.x - V.vector[0], y = r.y - V.vector[1], z = r.z - V.vector[2];
+                u = V.kind == PMC_VELOCITY_RADIAL ? V3{x, y, z} : V3{-y, x, 0.};
+                const double norm = sqrt(u.x * u.x + u.y * u.y + u.z * u.z);
+                if (norm == 0) return V3{0, 0, 0};
+                u = V3{u.x / norm, u.y / norm, u.z / norm};
+                double v = 1.;
+                if (V.unity_radius > 0.)
+                {
+                    if ((V.exponent > 0. && norm < V.unity_radius) || (V.exponent < 0. && norm > V.unity_radius))
+                        v = pow(norm / V.unity_radius, V.exponent);
+                }
+                u = V3{v * u.x, v * u.y, v * u.z};
+            }
+            return V3{V.magnitude * u.x, V.magnitude * u.y, V.magnitude * u.z};
+        }
+        // PhotonPacket::shiftedEmissionWavelength (PhotonPacket.cpp:133-136)
+        static double shiftedEmissionWavelength(double sourceWavelength, V3 k, V3 v)
+        {
+            return sourceWavelength * (1 - (k.x * v.x + k.y * v.y + k.z * v.z) / 2.99792458e8);
         }
 
         // ---- SourceSystem::launch -> NormalizedSource::launch -> Point/GeometricSource (SourceSystem.cpp:101-112,
@@ -873,6 +949,14 @@ namespace
             double Lw = L * w;
             pp.lambda = lambda;
             pp.W = Lw * lambda;
+            // PhotonPacket::launch (PhotonPacket.cpp:18-40) for a source with a bulk velocity: the weight keeps the sampled wavelength
+            pp.lambda0 = lambda;
+            pp.moving = sourceVelocity[si].kind != PMC_VELOCITY_NONE;
+            if (pp.moving)
+            {
+                pp.velocity = velocityAt(sourceVelocity[si], r);
+                pp.lambda = shiftedEmissionWavelength(lambda, k, pp.velocity);
+            }
             pp.D = 0;
             pp.historyIndex = historyIndex;
             pp.nscatt = 0;
@@ -1387,6 +1471,8 @@ namespace
                     V3 k{ins.kobs[0], ins.kobs[1], ins.kobs[2]};
                     ppp.lambda = pp.lambda;
                     ppp.W = pp.W;
+                    // (PhotonPacket.cpp:77: towards the observer the moving source's light has its own wavelength)
+                    if (pp.moving) ppp.lambda = shiftedEmissionWavelength(pp.lambda0, k, pp.velocity);
                     // PhotonPacket::launchEmissionPeelOff (PhotonPacket.cpp:66-85): the bias of an anisotropic emitter
                     if (pp.source && pp.source->kind == PMC_SOURCE_POINT && pp.source->angular_kind != PMC_ANGULAR_ISOTROPIC)
                         ppp.W *= angularProbability(*pp.source, k);
@@ -1427,6 +1513,14 @@ namespace
             return integralHG(g, cosalpha, cosbeta) / (cosalpha - cosbeta);
         }
 
+        // ---- dipole phase function of unpolarized Thomson scattering (DipolePhaseFunction.cpp:47-59)
+        static double valueDipole(double costheta) { return 0.75 * (costheta * costheta + 1.); }
+        static double cosineDipole(double X)
+        {
+            double p = cbrt(4. * X - 2. + sqrt(16. * X * (X - 1.) + 5.));
+            return p - 1. / p;
+        }
+
         // ---- MonteCarloSimulation::peelOffScattering, consolidated branch (MonteCarloSimulation.cpp:784-842;
         //      MediumSystem.cpp:697-767; DustMix.cpp:430-445; PhotonPacket.cpp:89-103)
         void peelOffScattering(const Packet& pp, Packet& ppp)
@@ -1460,8 +1554,14 @@ namespace
                         // (MediumSystem.cpp:745-757: components that do not scatter the packet are skipped)
                         if (wv[h] > 0.)
                         {
-                            double g = med(h).asymmpar[indexForLambda(h, lambda)];
-                            double value = std::abs(g) > 0.95 ? meanHG(g, costheta) : valueHG(g, costheta);
+                            double value;
+                            if (phaseKind[h] == PMC_PHASE_DIPOLE)
+                                value = valueDipole(costheta);
+                            else
+                            {
+                                double g = med(h).asymmpar[indexForLambda(h, lambda)];
+                                value = std::abs(g) > 0.95 ? meanHG(g, costheta) : valueHG(g, costheta);
+                            }
                             I += value * wv[h];
                         }
                     }
@@ -1497,7 +1597,14 @@ namespace
             }
             double g = med(hpick).asymmpar[indexForLambda(hpick, pp.lambda)];
             V3 knew;
-            if (fabs(g) < 1e-6)
+            if (phaseKind[hpick] == PMC_PHASE_DIPOLE)
+            {
+                // DipolePhaseFunction::performScattering (DipolePhaseFunction.cpp:164-172): one deviate for the cosine, then
+                // Random::direction(bfk, costheta)
+                double costheta = cosineDipole(rng.uniform());
+                knew = randomDirectionAbout(rng, pp.k, costheta);
+            }
+            else if (fabs(g) < 1e-6)
                 knew = randomDirection(rng);
             else
             {
@@ -1571,16 +1678,22 @@ extern "C" {
 // rng_kind 1: per-history Philox streams keyed by `seed` (the engine's streams).
 // frames: caller-allocated, accumulated into.  The per-history statistics lists are flushed before returning, so a
 // history range must not be split across calls with rng_kind 0 if bit-exact statistics are wanted.
-int oracle_run_primary(const pmc_scene* scene, uint64_t first, uint64_t count, int rng_kind, uint64_t seed,
-                       uint64_t skip_draws, double* frames, pmc_counter_values* counters)
+// ext: the scene's extension, read as pmc_create_ext reads it (struct_size; the kinds and combinations that function refuses return
+// PMC_ERR_UNSUPPORTED here too); NULL: every component Henyey-Greenstein, every source at rest.
+// rf: the radiation field table rf[m * num_lambda + ell] (scene->radiation_field.store must be set), or NULL: not stored.
+int oracle_run_primary_ext(const pmc_scene* scene, const pmc_scene_ext* ext, uint64_t first, uint64_t count, int rng_kind, uint64_t seed,
+                           uint64_t skip_draws, double* frames, double* rf, pmc_counter_values* counters)
 {
     if (!scene || !frames) return PMC_ERR_INVALID;
+    if (rf && !scene->radiation_field.store) return PMC_ERR_INVALID;
     std::unique_ptr<Rng> rng;
     if (rng_kind == 0)
         rng.reset(new MtRng(static_cast<int>(seed), skip_draws));
     else
         rng.reset(new PhiloxRng(seed));
     LifeCycle cycle(*scene, *rng, frames);
+    if (int rc = cycle.readExtension(ext)) return rc;
+    cycle.radiationField = rf;
     // the reference's contribution list starts with history index 0 and an empty list (FluxRecorder.hpp:335)
     cycle.run(first, count);
     cycle.flush();
@@ -1588,22 +1701,19 @@ int oracle_run_primary(const pmc_scene* scene, uint64_t first, uint64_t count, i
     return PMC_OK;
 }
 
+// without the extension: Henyey-Greenstein components, sources at rest
+int oracle_run_primary(const pmc_scene* scene, uint64_t first, uint64_t count, int rng_kind, uint64_t seed,
+                       uint64_t skip_draws, double* frames, pmc_counter_values* counters)
+{
+    return oracle_run_primary_ext(scene, nullptr, first, count, rng_kind, seed, skip_draws, frames, nullptr, counters);
+}
+
 // the same with the radiation field table rf[m * num_lambda + ell] (scene->radiation_field.store must be set)
 int oracle_run_primary_rf(const pmc_scene* scene, uint64_t first, uint64_t count, int rng_kind, uint64_t seed,
                           uint64_t skip_draws, double* frames, double* rf, pmc_counter_values* counters)
 {
-    if (!scene || !frames || !rf || !scene->radiation_field.store) return PMC_ERR_INVALID;
-    std::unique_ptr<Rng> rng;
-    if (rng_kind == 0)
-        rng.reset(new MtRng(static_cast<int>(seed), skip_draws));
-    else
-        rng.reset(new PhiloxRng(seed));
-    LifeCycle cycle(*scene, *rng, frames);
-    cycle.radiationField = rf;
-    cycle.run(first, count);
-    cycle.flush();
-    if (counters) *counters = cycle.counters;
-    return PMC_OK;
+    if (!rf) return PMC_ERR_INVALID;
+    return oracle_run_primary_ext(scene, nullptr, first, count, rng_kind, seed, skip_draws, frames, rf, counters);
 }
 
 int oracle_trace_ray(const pmc_scene* scene, const double r[3], const double k[3], int32_t* m, double* ds, int32_t cap,

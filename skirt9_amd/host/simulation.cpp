@@ -946,7 +946,17 @@ namespace skh
             for (size_t i = 0; i <= n; ++i) pv[i] = planck(lambdav[i]);
             return tab::cumulative(true, lambdav, pv, Pv);
         };
-        double Ltot = planckCdf(_sedLambda, _sedp, _sedP, sourceMin, sourceMax);
+        // SED::normalizationWavelengthRange (SED.cpp:22-28): the source range intersected with the range on which the SED is tabulated
+        // (a black body is defined everywhere); it is also the range NormalizedSource hands to its wavelength bias distribution
+        // (NormalizedSource.cpp:50-53, DefaultWavelengthDistribution.cpp:13-22, RangeWavelengthDistribution.cpp:12-19)
+        double normMin = sourceMin, normMax = sourceMax;
+        if (tabulated)
+        {
+            normMin = std::max(normMin, _source.sedInLambda.front());
+            normMax = std::min(normMax, _source.sedInLambda.back());
+            if (!(normMin < normMax)) throw std::runtime_error("Intrinsic SED wavelength range does not overlap source wavelength range");
+        }
+        double Ltot = planckCdf(_sedLambda, _sedp, _sedP, normMin, normMax);
         if (tabulated)
             for (double& v : _source.sedInP) v /= Ltot;  // TabulatedSED.cpp:20-21 (the later integrals use the normalised table)
         auto specificLuminosity = [&](double lambda) {
@@ -1013,8 +1023,9 @@ namespace skh
             flat.sed_f1 = f1;
             flat.sed_f2 = f2;
             flat.sed_ltot = Ltot;
-            // bias distribution range: Default = source range; Log/Lin = configured range intersected with source range
-            double lo = sourceMin, hi = sourceMax;
+            // bias distribution range: Default = the source's wavelength range, which is the normalization range of its SED; Log/Lin =
+            // the configured range intersected with it
+            double lo = normMin, hi = normMax;
             if (_source.biasDistType != "DefaultWavelengthDistribution")
             {
                 lo = std::max(lo, _source.biasMin);

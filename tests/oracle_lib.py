@@ -20,6 +20,8 @@ def lib():
                                          C.c_void_p, C.c_void_p]
         L.oracle_run_primary_rf.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64,
                                             C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_run_primary_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_trace_ray.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p]
         _lib = L
@@ -30,8 +32,17 @@ RNG_MT19937 = 0   # the reference's single-thread stream, continued after setup
 RNG_PHILOX = 1    # the engine's per-history streams
 
 
-def run_primary(sim, first, count, rng_kind, seed=None, skip_draws=None, frames=None):
-    """runs histories [first, first+count) of a set-up skirt9_amd.host.Simulation; returns (frames, counters)"""
+def _extension(sim):
+    """address of the pmc_scene_ext of a set-up Simulation (or SceneFile)"""
+    ext = getattr(sim.scene, "ext", None)
+    assert ext, "the scene carries no extension"
+    return ext
+
+
+def run_primary(sim, first, count, rng_kind, seed=None, skip_draws=None, frames=None, ext=False):
+    """runs histories [first, first+count) of a set-up skirt9_amd.host.Simulation; returns (frames, counters).
+    ext=False: every medium component scatters by Henyey-Greenstein and every source is at rest, whatever the scene's extension says;
+    ext=True: the oracle follows sim.scene.ext (dipole phase function, moving sources) as pmc_create_ext does"""
     from skirt9_amd.host import CounterValues
     if frames is None:
         frames = np.zeros(sim.frame_size, dtype=np.float64)
@@ -40,13 +51,17 @@ def run_primary(sim, first, count, rng_kind, seed=None, skip_draws=None, frames=
     if skip_draws is None:
         skip_draws = sim.setup_draws if rng_kind == RNG_MT19937 else 0
     counters = CounterValues()
-    rc = lib().oracle_run_primary(sim.scene, first, count, rng_kind, seed, skip_draws,
-                                  frames.ctypes.data_as(C.c_void_p), C.byref(counters))
-    assert rc == 0
+    if ext:
+        rc = lib().oracle_run_primary_ext(int(sim.scene), _extension(sim), first, count, rng_kind, seed, skip_draws,
+                                          frames.ctypes.data_as(C.c_void_p), None, C.byref(counters))
+    else:
+        rc = lib().oracle_run_primary(sim.scene, first, count, rng_kind, seed, skip_draws,
+                                      frames.ctypes.data_as(C.c_void_p), C.byref(counters))
+    assert rc == 0, rc
     return frames, counters
 
 
-def run_primary_rf(sim, first, count, rng_kind, seed=None, skip_draws=None):
+def run_primary_rf(sim, first, count, rng_kind, seed=None, skip_draws=None, ext=False):
     """like run_primary for a simulation that stores the radiation field; returns (frames, rf, counters)"""
     from skirt9_amd.host import CounterValues
     frames = np.zeros(sim.frame_size, dtype=np.float64)
@@ -56,9 +71,13 @@ def run_primary_rf(sim, first, count, rng_kind, seed=None, skip_draws=None):
     if skip_draws is None:
         skip_draws = sim.setup_draws if rng_kind == RNG_MT19937 else 0
     counters = CounterValues()
-    rc = lib().oracle_run_primary_rf(sim.scene, first, count, rng_kind, seed, skip_draws, frames.ctypes.data_as(C.c_void_p),
-                                     rf.ctypes.data_as(C.c_void_p), C.byref(counters))
-    assert rc == 0
+    if ext:
+        rc = lib().oracle_run_primary_ext(int(sim.scene), _extension(sim), first, count, rng_kind, seed, skip_draws,
+                                          frames.ctypes.data_as(C.c_void_p), rf.ctypes.data_as(C.c_void_p), C.byref(counters))
+    else:
+        rc = lib().oracle_run_primary_rf(sim.scene, first, count, rng_kind, seed, skip_draws, frames.ctypes.data_as(C.c_void_p),
+                                         rf.ctypes.data_as(C.c_void_p), C.byref(counters))
+    assert rc == 0, rc
     return frames, rf, counters
 
 

@@ -41,9 +41,10 @@ def test_byte_identical_to_reference(name, nfiles, tmp_path):
         assert _same_file(golden(f), str(tmp_path / f)), f"{f} differs from the reference output"
 
 
-@pytest.mark.parametrize("name", ["cfg1", "cfg1mesh", "cfg1mesh2", "cfg2small", "cfg2deep", "cfg2deeper", "cfg4small", "cfg4deepest", "cfg5small", "cfg5peak", "cfg5imp"])
+@pytest.mark.parametrize("name", ["cfg1", "cfg1mesh", "cfg1mesh2", "cfg2small", "cfg2deep", "cfg2deeper", "cfg4small", "cfg4deepest", "cfg5small", "cfg5peak", "cfg5imp", "cfg2bin", "cfg2bindeep"])
 def test_ray_segments_bit_exact(name):
-    """PathSegmentGenerator (m, ds) sequences dumped from the reference (skirt_ref rays) vs the oracle's generators"""
+    """PathSegmentGenerator (m, ds) sequences dumped from the reference (skirt_ref rays) vs the oracle's generators (cfg2bin, cfg2bindeep:
+    binary trees, BinTreeNode::child in the descent)"""
     sim = Simulation(ski(name + ".ski")).setup()
     rays = [[float.fromhex(t) for t in line.split()] for line in open(golden(name + "_rays.txt"))]
     ref = open(golden(name + "_rays_ref.txt")).read().split("\n")
