@@ -386,6 +386,18 @@ int pmc_reset_counters(pmc_ctx* ctx);
 /* Walk one ray on the device with the same traversal code the photon loop uses; k is normalised by the caller.
    Writes up to cap segments (cell index m or -1, length ds) and the number found to *n. */
 int pmc_trace_ray(pmc_ctx* ctx, const double r[3], const double k[3], int32_t* m, double* ds, int32_t cap, int32_t* n);
+/* Integrals along many rays at once (the probe maps: ProbeFormBridge::valuesAlongPath for accumulated quantities):
+   sums[i * num_values + v] = sum over the path of ray i of ds * cell_values[v * num_cells + m], over the segments with m >= 0 in path order,
+   without fused multiply-add -- the (m, ds) of pmc_trace_ray for the same ray, added up in double bit for bit.  origins and directions are
+   [num_rays][3] (an origin may lie outside the grid; directions normalised by the caller), cell_values is [num_values][num_cells] in the cell
+   numbering pmc_trace_ray reports; all host pointers; num_rays may be 0.  The device keeps PMC_INTEGRATE_PASS_VALUES sums per ray in registers:
+   more values take several passes over the rays.  A ray that is still inside the grid after 100000 cells fails the call with PMC_ERR_DEVICE. */
+#define PMC_INTEGRATE_PASS_VALUES 4
+int pmc_integrate_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, const double* directions, int32_t num_values,
+                       const double* cell_values, double* sums);
+/* work of the most recent pmc_integrate_rays on this context: milliseconds in its kernels (HIP events), cell segments added (lane steps), and
+   wave iterations that added them (64 lanes each: lanes in use = lane_steps / (64 wave_steps)) */
+int pmc_last_integrate_work(pmc_ctx* ctx, float* kernel_ms, uint64_t* lane_steps, uint64_t* wave_steps);
 /* number of photon histories kept in flight on the device (default 24 Mi, fewer where the device memory is short; environment PMC_NUM_SLOTS).  The slots are
    divided into slot groups (default 3; environment PMC_NUM_GROUPS) whose generations run on separate streams */
 int pmc_set_num_slots(pmc_ctx* ctx, int64_t num_slots);

@@ -54,6 +54,33 @@ int64_t  skh_radiation_field_size(const skh_simulation* sim);
 int skh_write_radiation_field(const skh_simulation* sim, const double* rf, const char* outdir);
 int skh_summary(const skh_simulation* sim, char* buffer, int32_t capacity);
 
+/* Probes of the spatial grid: DensityProbe and OpacityProbe with a PerCellForm (<prefix>_<probe>_<fileid>.dat) or a ParallelProjectionForm
+   (<prefix>_<probe>_<projectedFileid>.fits: one "projected map" per quantity, e.g. dust_Sigma, elec_N, tau).  The pixels of a map are sums
+   over sub-sample rays of line integrals through the grid; the integrator is handed over at run time -- libpmc.so's pmc_integrate_rays
+   with user = the pmc_ctx -- so that this library does not link against the HIP engine. */
+typedef int (*skh_integrate_fn)(void* user, int64_t num_rays, const double* origins, const double* directions, int32_t num_values,
+                                const double* cell_values, double* sums);
+typedef struct
+{
+    char file_name[256];    /* name of the FITS file, without directory */
+    int32_t nx, ny;         /* pixels */
+    int32_t sampling;       /* sub-samples per pixel and axis (numSampling) */
+    int32_t num_values;     /* values per ray: 1, or the wavelengths of an opacity probe */
+    int32_t after_setup;    /* probeAfter: 1 Setup, 0 Run */
+    int64_t num_rays;       /* nx * ny * sampling^2 */
+} skh_probe_map;
+/* projected maps, in file order (valid after skh_setup; 0 for a simulation without a medium) */
+int32_t skh_num_probe_maps(const skh_simulation* sim);
+int skh_probe_map_info(const skh_simulation* sim, int32_t map, skh_probe_map* out);
+/* the rays [num_rays][3] of a map, ordered by pixel (j, i) and sub-sample (is, js), and its cell values [num_values][num_cells] in
+   internal units (the unit factor of the projected quantity is applied to the integrals) */
+int skh_probe_map_rays(const skh_simulation* sim, int32_t map, double* origins, double* directions);
+int skh_probe_map_values(const skh_simulation* sim, int32_t map, double* cell_values);
+/* writes every probe file into outdir; the per-cell files are written without calling `integrate`, which may be NULL when the ski file
+   has no projected map.  skh_write_probes_when: only the probes with probeAfter Setup (when = 0) or Run (when = 1); -1: all */
+int skh_write_probes(const skh_simulation* sim, skh_integrate_fn integrate, void* user, const char* outdir);
+int skh_write_probes_when(const skh_simulation* sim, skh_integrate_fn integrate, void* user, const char* outdir, int32_t when);
+
 /* A set-up scene as ONE file: everything pmc_create reads plus the numbers a driver of the photon loop needs.  In a job of
    one process per GPU, one process sets the simulation up (all host cores) and saves it, the others load it instead of
    repeating the setup -- the reference repeats Simulation::setupSimulation in every MPI process.  A loaded scene serves

@@ -20,6 +20,31 @@ void pmcSetError(const std::string& message)
     t_error = message;
 }
 
+// device buffers of one pmc_integrate_rays call: freed when the call returns, whichever way
+namespace
+{
+    struct ScratchBuffers
+    {
+        std::vector<void*> owned;
+        ~ScratchBuffers()
+        {
+            for (void* d : owned) hipFree(d);
+        }
+        template<typename T> hipError_t get(size_t count, T** out)
+        {
+            void* d = nullptr;
+            hipError_t e = hipMalloc(&d, std::max(count, size_t(1)) * sizeof(T));
+            if (e != hipSuccess) return e;
+            owned.push_back(d);
+            // (test aid, as in pmc_ctx::allocate: what the call does not write shows)
+            if (pmcTune("PMC_POISON_ALLOCATIONS")) e = hipMemset(d, 0xA5, std::max(count, size_t(1)) * sizeof(T));
+            *out = static_cast<T*>(d);
+            return e;
+        }
+    };
+}
+
+
 extern "C" {
 
 int pmc_abi_version(void)
@@ -899,6 +924,113 @@ int pmc_trace_ray(pmc_ctx* ctx, const double r[3], const double k[3], int32_t* m
     hipFree(dn);
     hipFree(dk);
     return rc;
+}
+
+int pmc_integrate_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, const double* directions, int32_t num_values, const double* cell_values,
+                       double* sums)
+{
+    if (!ctx) return fail(PMC_ERR_INVALID, "null context");
+    if (num_rays < 0) return fail(PMC_ERR_INVALID, "pmc_integrate_rays: negative number of rays");
+    if (num_values < 0) return fail(PMC_ERR_INVALID, "pmc_integrate_rays: negative number of values");
+    if (num_rays > 0 && (!origins || !directions)) return fail(PMC_ERR_INVALID, "pmc_integrate_rays: null ray arrays");
+    if (num_values > 0 && !cell_values) return fail(PMC_ERR_INVALID, "pmc_integrate_rays: null cell values");
+    if (num_rays > 0 && num_values > 0 && !sums) return fail(PMC_ERR_INVALID, "pmc_integrate_rays: null result array");
+    ctx->integrateMs = 0.f;
+    ctx->integrateLaneSteps = ctx->integrateWaveSteps = 0;
+    if (num_rays == 0 || num_values == 0) return PMC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->sceneDirty)
+    {
+        HIP_TRY(pmcUploadScene(ctx->slot, &ctx->dev, ctx->stream));
+        ctx->sceneDirty = false;
+    }
+    const DevScene& D = ctx->dev;
+    constexpr int W = PMC_INTEGRATE_PASS_VALUES;
+    const size_t numCells = size_t(D.num_cells);
+    // the numbering the kernel walks in: device cells of a tree (cell_ext[device cell] = the caller's m, -1: none), else the caller's
+    const bool renumbered = D.grid_kind == PMC_GRID_OCTREE || D.grid_kind == PMC_GRID_BINTREE;
+    const size_t slots = renumbered ? size_t(D.cell_slots) : numCells;
+    std::vector<int32_t> ext;
+    if (renumbered)
+    {
+        ext.resize(slots);
+        HIP_TRY(hipMemcpy(ext.data(), D.cell_ext, slots * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int32_t m : ext)
+            if (m >= D.num_cells) return fail(PMC_ERR_DEVICE, "pmc_integrate_rays: cell numbering table out of range");
+    }
+    const int64_t batchMax = int64_t(1) << 22;  // rays per launch (device memory: 10 doubles per ray)
+    const size_t batchRoom = size_t(std::min(num_rays, batchMax));
+    ScratchBuffers scratch;
+    double *dOrigins = nullptr, *dDirections = nullptr, *dQ = nullptr, *dSums = nullptr;
+    unsigned long long* dWork = nullptr;
+    const int workWords = pmcProbeWorkWords();
+    HIP_TRY(scratch.get(3 * batchRoom, &dOrigins));
+    HIP_TRY(scratch.get(3 * batchRoom, &dDirections));
+    HIP_TRY(scratch.get(slots * W, &dQ));
+    HIP_TRY(scratch.get(W * batchRoom, &dSums));
+    HIP_TRY(scratch.get(size_t(workWords), &dWork));
+    hipEvent_t evA = nullptr, evB = nullptr;
+    HIP_TRY(hipEventCreate(&evA));
+    if (hipError_t e = hipEventCreate(&evB); e != hipSuccess)
+    {
+        hipEventDestroy(evA);
+        return hipFail(e, "hipEventCreate");
+    }
+    std::vector<double> q(slots * W), part(W * batchRoom);
+    std::vector<unsigned long long> work(workWords);
+    unsigned long long capped = 0;
+    hipError_t e = hipSuccess;
+    const int numPasses = (num_values + W - 1) / W;
+    for (int64_t first = 0; first < num_rays && e == hipSuccess; first += batchMax)
+    {
+        const size_t n = size_t(std::min(batchMax, num_rays - first));
+        e = hipMemcpy(dOrigins, origins + 3 * first, 3 * n * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dDirections, directions + 3 * first, 3 * n * sizeof(double), hipMemcpyHostToDevice);
+        // persistent waves: enough workgroups of four for every CU's share, no more than the rays fill
+        const int grid = int(std::max<size_t>(1, std::min<size_t>((n + 255) / 256, size_t(ctx->numCU) * 4)));
+        for (int pass = 0; pass < numPasses && e == hipSuccess; ++pass)
+        {
+            const int v0 = pass * W, nv = std::min(W, num_values - v0);
+            for (size_t c = 0; c < slots; ++c)
+            {
+                const int64_t m = renumbered ? int64_t(ext[c]) : int64_t(c);
+                for (int j = 0; j < W; ++j) q[c * W + j] = (j < nv && m >= 0) ? cell_values[size_t(v0 + j) * numCells + size_t(m)] : 0.;
+            }
+            e = hipMemcpy(dQ, q.data(), q.size() * sizeof(double), hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemsetAsync(dWork, 0, workWords * sizeof(unsigned long long), ctx->stream);
+            if (e == hipSuccess) e = hipEventRecord(evA, ctx->stream);
+            if (e == hipSuccess)
+                e = pmcLaunchIntegrate(ctx->slot, D.grid_kind, ctx->wide, dOrigins, dDirections, dQ, dSums, n, dWork, grid, ctx->walkLds, ctx->stream);
+            if (e == hipSuccess) e = hipEventRecord(evB, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            if (e == hipSuccess) e = hipMemcpy(part.data(), dSums, W * n * sizeof(double), hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(work.data(), dWork, workWords * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) break;
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, evA, evB) == hipSuccess) ctx->integrateMs += ms;
+            capped += work[1];
+            ctx->integrateLaneSteps += work[2];
+            ctx->integrateWaveSteps += work[3];
+            for (size_t i = 0; i < n; ++i)
+                for (int j = 0; j < nv; ++j) sums[(size_t(first) + i) * size_t(num_values) + size_t(v0 + j)] = part[i * W + j];
+        }
+    }
+    hipEventDestroy(evA);
+    hipEventDestroy(evB);
+    if (e != hipSuccess) return hipFail(e, "pmc_integrate_rays");
+    if (capped)
+        return fail(PMC_ERR_DEVICE, "pmc_integrate_rays: " + std::to_string(capped) + " ray walk(s) were still inside the grid after 100000 cells (traversal error)");
+    return PMC_OK;
+}
+
+int pmc_last_integrate_work(pmc_ctx* ctx, float* kernel_ms, uint64_t* lane_steps, uint64_t* wave_steps)
+{
+    if (!ctx) return fail(PMC_ERR_INVALID, "null context");
+    if (kernel_ms) *kernel_ms = ctx->integrateMs;
+    if (lane_steps) *lane_steps = ctx->integrateLaneSteps;
+    if (wave_steps) *wave_steps = ctx->integrateWaveSteps;
+    return PMC_OK;
 }
 
 }  // extern "C"

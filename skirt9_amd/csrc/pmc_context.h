@@ -68,6 +68,9 @@ extern "C" hipError_t pmcLaunchCycleStart(int slot, int gridKind, int kin, int s
 extern "C" hipError_t pmcLaunchTrace(int slot, int gridKind, int wide, int uniform, const double r[3], const double k[3],
                                      const double* kdev, int32_t* m, double* ds, int32_t cap, int32_t* n, size_t ldsBytes,
                                      hipStream_t stream);
+extern "C" int pmcProbeWorkWords(void);
+extern "C" hipError_t pmcLaunchIntegrate(int slot, int gridKind, int wide, const double* origins, const double* directions, const double* q, double* sums,
+                                         unsigned long long numRays, unsigned long long* work, int grid, size_t ldsBytes, hipStream_t stream);
 
 // error text of the calling thread (pmc_last_error); defined in pmc_api.hip
 void pmcSetError(const std::string& message);
@@ -118,6 +121,9 @@ struct pmc_ctx
     float totalMs{0}, walkMs{0}, transitionMs{0};
     float peelMs{0}, propMs{0};  // octree: the spans of the peel-off kernels and of the propagation kernel, summed over the generations
     int generations{0};
+    // work of the most recent pmc_integrate_rays (pmc_last_integrate_work)
+    float integrateMs{0};
+    unsigned long long integrateLaneSteps{0}, integrateWaveSteps{0};
     DevScene dev{};
     std::vector<void*> allocations;
     std::vector<void*> slotAllocations;

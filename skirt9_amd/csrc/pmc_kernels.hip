@@ -270,6 +270,7 @@ namespace
 #include "pmc_walk.inc"
 #include "pmc_walk_tree.inc"
 #include "pmc_transition.inc"
+#include "pmc_probe.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -389,6 +390,11 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
                {reinterpret_cast<const void*>(&traceRayKernel<GRID_CART>), walkMax},
                {reinterpret_cast<const void*>(&traceRayKernel<GRID_VORO>), walkMax},
                {reinterpret_cast<const void*>(&traceRayKernel<GRID_BIN>), walkMax},
+               {reinterpret_cast<const void*>(&integrateRaysKernel<GRID_TREE, false>), walkMax},
+               {reinterpret_cast<const void*>(&integrateRaysKernel<GRID_TREE, true>), walkMax},
+               {reinterpret_cast<const void*>(&integrateRaysKernel<GRID_CART, false>), walkMax},
+               {reinterpret_cast<const void*>(&integrateRaysKernel<GRID_VORO, false>), walkMax},
+               {reinterpret_cast<const void*>(&integrateRaysKernel<GRID_BIN, false>), walkMax},
                {reinterpret_cast<const void*>(&transitionKernel), transitionMax},
                {reinterpret_cast<const void*>(&transitionDipoleKernel), transitionMax},
                {reinterpret_cast<const void*>(&transitionKinKernel), transitionMax},
@@ -721,5 +727,20 @@ extern "C" hipError_t pmcLaunchTrace(int slot, int gridKind, int wide, int unifo
     else
         hipLaunchKernelGGL(gridKind == PMC_GRID_VORONOI ? traceRayKernel<GRID_VORO> : gridKind == PMC_GRID_BINTREE ? traceRayKernel<GRID_BIN> : traceRayKernel<GRID_CART>, dim3(1), dim3(64), ldsBytes, stream, slot, r[0],
                            r[1], r[2], k[0], k[1], k[2], m, ds, cap, n);
+    return hipGetLastError();
+}
+
+// batched ray integrals (pmc_probe.inc): one pass of PMC_INTEGRATE_PASS_VALUES values over numRays rays; `work` = the kernel's cursor and counters,
+// zeroed by the caller (pmcProbeWorkWords words)
+extern "C" int pmcProbeWorkWords(void) { return PROBE_WORK_WORDS; }
+extern "C" hipError_t pmcLaunchIntegrate(int slot, int gridKind, int wide, const double* origins, const double* directions, const double* q, double* sums,
+                                         unsigned long long numRays, unsigned long long* work, int grid, size_t ldsBytes, hipStream_t stream)
+{
+    const ProbeArgs A = {origins, directions, q, sums, numRays, work};
+    const auto kernel = gridKind == PMC_GRID_OCTREE    ? (wide ? integrateRaysKernel<GRID_TREE, true> : integrateRaysKernel<GRID_TREE, false>)
+                        : gridKind == PMC_GRID_VORONOI ? integrateRaysKernel<GRID_VORO, false>
+                        : gridKind == PMC_GRID_BINTREE ? integrateRaysKernel<GRID_BIN, false>
+                                                       : integrateRaysKernel<GRID_CART, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), ldsBytes, stream, slot, A);
     return hipGetLastError();
 }

@@ -10,14 +10,15 @@ import os
 
 import numpy as np
 
-from .host import CounterValues, FrameLayout, SceneExt
+from .host import CounterValues, FrameLayout, SceneExt, SceneHead
 
 _LIBDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 
 # every symbol include/pmc.h and include/pmc_tuning.h declare
 SYMBOLS = ["pmc_abi_version", "pmc_build_info", "pmc_last_error", "pmc_frame_layout_of", "pmc_create", "pmc_create_ext", "pmc_destroy", "pmc_bind_frames",
            "pmc_clear_frames", "pmc_run_primary", "pmc_set_progress", "pmc_sync", "pmc_download", "pmc_frames_device", "pmc_frames_size",
-           "pmc_last_kernel_ms", "pmc_counters", "pmc_reset_counters", "pmc_trace_ray", "pmc_set_launch",
+           "pmc_last_kernel_ms", "pmc_counters", "pmc_reset_counters", "pmc_trace_ray", "pmc_integrate_rays",
+           "pmc_last_integrate_work", "pmc_set_launch",
            "pmc_set_num_slots", "pmc_last_timing", "pmc_last_walk_timing", "pmc_walk_work", "pmc_radiation_field_size", "pmc_radiation_field_device",
            "pmc_download_radiation_field", "pmc_clear_radiation_field", "pmc_bind_radiation_field", "pmc_sampler_create",
            "pmc_sampler_density", "pmc_sampler_destroy", "pmc_history_range", "pmc_comm_init_all", "pmc_comm_unique_id",
@@ -71,6 +72,9 @@ def lib():
         L.pmc_counters.argtypes = [C.c_void_p, C.POINTER(CounterValues)]
         L.pmc_reset_counters.argtypes = [C.c_void_p]
         L.pmc_trace_ray.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        if hasattr(L, "pmc_integrate_rays"):  # (absent from engines built from an older commit and loaded through PMC_LIBRARY)
+            L.pmc_integrate_rays.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+            L.pmc_last_integrate_work.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.pmc_set_launch.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.pmc_set_num_slots.argtypes = [C.c_void_p, C.c_int64]
         L.pmc_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -105,6 +109,9 @@ def lib():
 
 
 # settings the library itself reads from the environment (include/pmc.h); every other PMC_* name is a tuning switch
+# values whose sums pmc_integrate_rays keeps in registers per pass over the rays (include/pmc.h PMC_INTEGRATE_PASS_VALUES)
+INTEGRATE_PASS_VALUES = 4
+
 ENVIRONMENT_SETTINGS = ("PMC_NUM_SLOTS", "PMC_NUM_GROUPS", "PMC_STAT_POOL_BLOCKS")
 
 
@@ -206,6 +213,7 @@ class Engine:
                 raise RuntimeError("this libpmc.so has no pmc_create_ext: it cannot run a scene with a moving source")
             _check(L.pmc_create(int(scene_ptr), device, C.byref(self._h)))
         self.device = device
+        self.num_cells = int(SceneHead.from_address(int(scene_ptr)).grid.num_cells)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -353,3 +361,33 @@ class Engine:
         _check(lib().pmc_trace_ray(self._h, r.ctypes.data_as(C.c_void_p), k.ctypes.data_as(C.c_void_p),
                                    m.ctypes.data_as(C.c_void_p), ds.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         return m[:n.value].copy(), ds[:n.value].copy()
+
+    def integrate_rays(self, origins, directions, cell_values):
+        """sums[i, v] = sum over the path of ray i of ds * cell_values[v, m] (pmc_integrate_rays: the probe maps' line integrals, the segments of
+        ``trace_ray`` added up in path order on the device).  origins, directions: [n][3]; cell_values: [V][num_cells] or [num_cells]
+        (then the result is [n]); cells in the numbering ``trace_ray`` reports"""
+        r = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        k = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        if r.shape != k.shape:
+            raise ValueError("origins and directions differ in shape")
+        q = np.ascontiguousarray(cell_values, dtype=np.float64)
+        single = q.ndim == 1
+        q = q.reshape(1, -1) if single else q
+        if q.ndim != 2:
+            raise ValueError("cell_values must be [V][num_cells]")
+        out = np.zeros((r.shape[0], q.shape[0]), dtype=np.float64)
+        if q.shape[1] != self.num_cells:
+            raise ValueError(f"cell_values has {q.shape[1]} cells per value, the grid has {self.num_cells}")
+        _check(lib().pmc_integrate_rays(self._h, r.shape[0], r.ctypes.data_as(C.c_void_p), k.ctypes.data_as(C.c_void_p), q.shape[0],
+                                        q.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out[:, 0].copy() if single else out
+
+    def integrate_callback(self):
+        """``integrate_rays`` as the C callback of skh_write_probes (include/skirt_host.h skh_integrate_fn): (function address, user pointer)"""
+        return C.cast(lib().pmc_integrate_rays, C.c_void_p).value, self._h
+
+    def last_integrate_work(self):
+        """the most recent integrate_rays: dict(kernel_ms, lane_steps, wave_steps); lanes in use = lane_steps / (64 wave_steps)"""
+        ms, a, b = C.c_float(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().pmc_last_integrate_work(self._h, C.byref(ms), C.byref(a), C.byref(b)))
+        return {"kernel_ms": float(ms.value), "lane_steps": int(a.value), "wave_steps": int(b.value)}

@@ -84,6 +84,17 @@ class SceneHead(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("grid", Grid), ("medium", Medium)]
 
 
+class ProbeMapInfo(C.Structure):
+    """skh_probe_map (include/skirt_host.h)"""
+    _fields_ = [("file_name", C.c_char * 256), ("nx", C.c_int32), ("ny", C.c_int32), ("sampling", C.c_int32), ("num_values", C.c_int32),
+                ("after_setup", C.c_int32), ("num_rays", C.c_int64)]
+
+
+# skh_integrate_fn (include/skirt_host.h)
+INTEGRATE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
+                           C.POINTER(C.c_double))
+
+
 def scene_head(sim):
     """the leading members (grid, medium) of the pmc_scene of a set-up Simulation, for inspection"""
     return SceneHead.from_address(sim.scene)
@@ -124,6 +135,13 @@ def lib():
         L.skh_radiation_field_size.restype = C.c_int64
         L.skh_radiation_field_size.argtypes = [C.c_void_p]
         L.skh_write_radiation_field.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
+        L.skh_num_probe_maps.restype = C.c_int32
+        L.skh_num_probe_maps.argtypes = [C.c_void_p]
+        L.skh_probe_map_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ProbeMapInfo)]
+        L.skh_probe_map_rays.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.skh_probe_map_values.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.skh_write_probes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
+        L.skh_write_probes_when.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32]
         L.skh_scene_save.argtypes = [C.c_void_p, C.c_char_p]
         L.skh_scene_load.restype = C.c_void_p
         L.skh_scene_load.argtypes = [C.c_char_p]
@@ -242,6 +260,65 @@ class Simulation:
         assert data.size == self.radiation_field_size
         os.makedirs(outdir, exist_ok=True)
         if lib().skh_write_radiation_field(self._h, data.ctypes.data_as(C.c_void_p), os.fsencode(outdir)) != 0:
+            raise RuntimeError(lib().skh_last_error().decode())
+
+    def probe_maps(self):
+        """the projected maps (DensityProbe / OpacityProbe with a ParallelProjectionForm) in file order, one dict each: file_name, nx, ny,
+        sampling, num_values, num_rays, after_setup, and the arrays origins [num_rays][3], directions [num_rays][3] (ordered by pixel
+        (j, i) and sub-sample (is, js)) and cell_values [num_values][num_cells] (internal units)"""
+        import numpy as np
+        assert self._setup, "call setup() first"
+        L = lib()
+        num_cells = int(scene_head(self).grid.num_cells)
+        maps = []
+        for index in range(L.skh_num_probe_maps(self._h)):
+            info = ProbeMapInfo()
+            if L.skh_probe_map_info(self._h, index, C.byref(info)) != 0:
+                raise RuntimeError(L.skh_last_error().decode())
+            origins = np.empty((info.num_rays, 3), dtype=np.float64)
+            directions = np.empty((info.num_rays, 3), dtype=np.float64)
+            values = np.empty((info.num_values, num_cells), dtype=np.float64)
+            if (L.skh_probe_map_rays(self._h, index, origins.ctypes.data_as(C.c_void_p), directions.ctypes.data_as(C.c_void_p)) != 0
+                    or L.skh_probe_map_values(self._h, index, values.ctypes.data_as(C.c_void_p)) != 0):
+                raise RuntimeError(L.skh_last_error().decode())
+            maps.append({"file_name": info.file_name.decode(), "nx": int(info.nx), "ny": int(info.ny), "sampling": int(info.sampling),
+                         "num_values": int(info.num_values), "num_rays": int(info.num_rays), "after_setup": bool(info.after_setup),
+                         "origins": origins, "directions": directions, "cell_values": values})
+        return maps
+
+    def write_probes(self, outdir, integrator=None, when=None):
+        """write the DensityProbe / OpacityProbe files into outdir.  integrator: an ``Engine`` (its pmc_integrate_rays is handed to the host
+        library as a C function: the rays never pass through Python), or a callable (origins [n][3], directions [n][3], cell_values
+        [V][num_cells]) -> sums [n][V]; None serves a ski file without projected maps.  when: "Setup" or "Run" for the probes with that
+        probeAfter only, None for all"""
+        import numpy as np
+        assert self._setup, "call setup() first"
+        os.makedirs(outdir, exist_ok=True)
+        code = {None: -1, "Setup": 0, "Run": 1}[when]
+        failure = []
+        if integrator is None:
+            function, user = None, None
+        elif hasattr(integrator, "integrate_callback"):
+            function, user = integrator.integrate_callback()
+        else:
+            num_cells = int(scene_head(self).grid.num_cells)
+
+            def call(_, n, origins, directions, num_values, values, sums):
+                try:
+                    r = np.ctypeslib.as_array(origins, shape=(n, 3))
+                    k = np.ctypeslib.as_array(directions, shape=(n, 3))
+                    q = np.ctypeslib.as_array(values, shape=(num_values, num_cells))
+                    np.ctypeslib.as_array(sums, shape=(n, num_values))[:] = np.asarray(integrator(r, k, q), dtype=np.float64).reshape(n, num_values)
+                    return 0
+                except Exception as error:  # (an exception must not cross the C frames: reported below)
+                    failure.append(error)
+                    return 1
+
+            keep = INTEGRATE_FN(call)
+            function, user = C.cast(keep, C.c_void_p), None
+        if lib().skh_write_probes_when(self._h, function, user, os.fsencode(outdir), code) != 0:
+            if failure:
+                raise failure[0]
             raise RuntimeError(lib().skh_last_error().decode())
 
     def save_scene(self, path):

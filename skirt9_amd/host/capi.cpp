@@ -218,6 +218,87 @@ int skh_write_radiation_field(const skh_simulation* h, const double* rf, const c
     }
 }
 
+int32_t skh_num_probe_maps(const skh_simulation* h)
+{
+    try
+    {
+        return h && h->sim ? h->sim->numProbeMaps() : 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int skh_probe_map_info(const skh_simulation* h, int32_t map, skh_probe_map* out)
+{
+    try
+    {
+        if (!h || !h->sim || !out) throw std::runtime_error("invalid argument");
+        const skh::Simulation::ProbeMapInfo info = h->sim->probeMapInfo(map);
+        std::memset(out, 0, sizeof(*out));
+        if (info.fileName.size() >= sizeof(out->file_name)) throw std::runtime_error("probe file name too long");
+        std::strcpy(out->file_name, info.fileName.c_str());
+        out->nx = info.nx, out->ny = info.ny;
+        out->sampling = info.sampling;
+        out->num_values = info.numValues;
+        out->after_setup = info.afterSetup ? 1 : 0;
+        out->num_rays = info.numRays;
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int skh_probe_map_rays(const skh_simulation* h, int32_t map, double* origins, double* directions)
+{
+    try
+    {
+        if (!h || !h->sim || !origins || !directions) throw std::runtime_error("invalid argument");
+        h->sim->probeMapRays(map, origins, directions);
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int skh_probe_map_values(const skh_simulation* h, int32_t map, double* cell_values)
+{
+    try
+    {
+        if (!h || !h->sim || !cell_values) throw std::runtime_error("invalid argument");
+        h->sim->probeMapValues(map, cell_values);
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int skh_write_probes_when(const skh_simulation* h, skh_integrate_fn integrate, void* user, const char* outdir, int32_t when)
+{
+    try
+    {
+        if (!h || !h->sim || !outdir) throw std::runtime_error("invalid argument");
+        h->sim->writeProbes(integrate, user, outdir, when);
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int skh_write_probes(const skh_simulation* h, skh_integrate_fn integrate, void* user, const char* outdir)
+{
+    return skh_write_probes_when(h, integrate, user, outdir, -1);
+}
+
 int skh_summary(const skh_simulation* h, char* buffer, int32_t capacity)
 {
     std::string s = h->sim->summary();

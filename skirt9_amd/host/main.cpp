@@ -9,7 +9,9 @@
 //
 // Counterpart of SKIRT/main (SkirtCommandLineHandler.cpp:295-372 doSimulation): construct the simulation from the
 // ski file, set it up, run the primary emission segment (here: on the GPU through the C ABI of include/pmc.h),
-// write the instrument output.  There is no CPU fallback: without a HIP device pmc_create fails and so does the run.
+// write the instrument output.  The density and opacity probes of the ski file are written with the line integrals of their projected
+// maps computed on the first device (pmc_integrate_rays): those with probeAfter="Setup" before the photon loop, the others after it
+// (ProbeSystem::probeSetup / probeRun).  There is no CPU fallback: without a HIP device pmc_create fails and so does the run.
 
 #include "../../include/pmc.h"
 #include "../../include/skirt_host.h"
@@ -137,9 +139,23 @@ int main(int argc, char** argv)
             meetCv.wait(lock, [&] { return arrived == G; });
         return failures == 0;
     };
+    // the integrator of the probe maps: the engine context of the first device
+    const skh_integrate_fn integrate = [](void* user, int64_t numRays, const double* origins, const double* directions, int32_t numValues,
+                                          const double* cellValues, double* sums) {
+        return pmc_integrate_rays(static_cast<pmc_ctx*>(user), numRays, origins, directions, numValues, cellValues, sums);
+    };
+    auto writeProbes = [&](int when) {
+        if (skh_write_probes_when(sim, integrate, ctxs[0], outdir.c_str(), when) == 0) return true;
+        // (the host layer reports that the integrator failed; the engine says why)
+        errors[0] = std::string(skh_last_error()) + (*pmc_last_error() ? std::string(": ") + pmc_last_error() : std::string());
+        return false;
+    };
     auto work = [&](int g) {
         auto failed = [&]() { errors[g] = pmc_last_error(); };
         bool ok = pmc_create_ext(skh_scene(sim), skh_scene_ext(sim), devices[g], &ctxs[g]) == PMC_OK;
+        if (!ok) failed();
+        // (probes after setup: before any photon packet is launched)
+        if (ok && g == 0) ok = writeProbes(0);
         if (ok)
         {
             // (the first device reports for all: MonteCarloSimulation::logProgress / Log::infoIfElapsed, every 3 s)
@@ -156,7 +172,7 @@ int main(int argc, char** argv)
             if (rc == PMC_ERR_OVERFLOW) statisticsLost[g] = pmc_last_error();
             ok = rc == PMC_OK || rc == PMC_ERR_OVERFLOW;
         }
-        if (!ok) failed();
+        if (!ok && errors[g].empty()) failed();
         if (ok) pmc_counters(ctxs[g], &counts[g]);
         if (!meet(ok) || !ok) return;
         if (useComm && pmc_reduce_frames(ctxs[g], comms[g], 0) != PMC_OK) return failed();
@@ -209,6 +225,12 @@ int main(int argc, char** argv)
     if (!rf.empty() && skh_write_radiation_field(sim, rf.data(), outdir.c_str()) != 0)
     {
         fprintf(stderr, "Fatal error: %s\n", skh_last_error());
+        return 1;
+    }
+    // the probes after the run
+    if (!writeProbes(1))
+    {
+        fprintf(stderr, "Fatal error: %s\n", errors[0].c_str());
         return 1;
     }
     printf("Finished final output in %.1f s.\n", seconds(t3, clock::now()));

@@ -1,0 +1,336 @@
+// probes.cpp -- the density and opacity probes of the spatial grid, per cell and in parallel projection:
+//   <prefix>_<probe>_<fileid>.dat            PerCellForm (PerCellForm.cpp:14-38)
+//   <prefix>_<probe>_<projectedFileid>.fits  ParallelProjectionForm (ParallelProjectionForm.cpp:18-116)
+// restating DensityProbe::probe (DensityProbe.cpp:14-100), OpacityProbe::probe (OpacityProbe.cpp:37-168) and the ProbeFormBridge between a
+// probe and its form (ProbeFormBridge.cpp:37-57, 114-136, 548-584, 628-650, 707-725) for the aggregations System, Type and Component.
+// The line integrals of a projected map -- ProbeFormBridge::valuesAlongPath -- are not computed here: the caller's integrator walks the
+// rays (the engine's pmc_integrate_rays); this file makes the rays and the cell values, averages the sub-samples and writes the files.
+
+#include "simulation.hpp"
+#include "units.hpp"
+#include <algorithm>
+#include <cctype>
+#include <cmath>
+#include <cstdio>
+#include <fstream>
+
+namespace skh
+{
+    // one ProbeFormBridge::writeQuantity call: a scalar (density) or compound (opacity per wavelength) quantity accumulated along paths
+    struct Simulation::ProbeQuantity
+    {
+        enum Kind { MassDensity, NumberDensity, Opacity } kind{MassDensity};
+        std::string fileid, projectedFileid, quantity, projectedQuantity, description, projectedDescription;
+        std::vector<int> components;  // the medium components summed, in order
+        bool compound{false};
+        Array wave;  // opacity: wavelengths in internal units, in output order
+        Array axis;  // ... in output units (the third axis of the FITS file)
+        int numValues() const { return compound ? static_cast<int>(axis.size()) : 1; }
+    };
+
+    std::vector<Simulation::ProbeQuantity> Simulation::probeQuantities(const ProbeModel& probe) const
+    {
+        std::vector<ProbeQuantity> result;
+        if (!_hasMedium) return result;  // DensityProbe.cpp:16, OpacityProbe.cpp:39
+        const int numMedia = static_cast<int>(_media.size());
+        std::vector<int> dust, electrons, all;
+        for (int h = 0; h != numMedia; ++h)
+        {
+            (_media[h]->mix->isElectrons() ? electrons : dust).push_back(h);
+            all.push_back(h);
+        }
+        if (probe.type == "DensityProbe")
+        {
+            auto add = [&](const std::string& id, bool mass, const std::vector<int>& components) {
+                ProbeQuantity q;
+                q.kind = mass ? ProbeQuantity::MassDensity : ProbeQuantity::NumberDensity;
+                q.fileid = id + (mass ? "_rho" : "_n");
+                q.projectedFileid = id + (mass ? "_Sigma" : "_N");
+                q.quantity = mass ? "massvolumedensity" : "numbervolumedensity";
+                q.projectedQuantity = mass ? "masssurfacedensity" : "numbersurfacedensity";
+                q.description = mass ? "mass density" : "number density";
+                q.projectedDescription = mass ? "mass surface density" : "column density";
+                q.components = components;
+                result.push_back(q);
+            };
+            if (probe.aggregation == "Type")
+            {
+                if (!dust.empty()) add("dust", true, dust);
+                if (!electrons.empty()) add("elec", false, electrons);
+            }
+            else
+                for (int h = 0; h != numMedia; ++h) add(std::to_string(h), !_media[h]->mix->isElectrons(), {h});
+        }
+        else
+        {
+            // the wavelengths in output order (OpacityProbe.cpp:44-54; Units::rwavelength, Units.cpp:124-133)
+            const WavelengthGrid& wlg = *probe.grid;
+            const int numWaves = wlg.numBins();
+            const bool reverse = _units.wavelengthStyle != "Wavelength";
+            Array wave(numWaves), axis(numWaves);
+            for (int i = 0; i != numWaves; ++i)
+            {
+                const int ell = reverse ? numWaves - 1 - i : i;
+                wave[i] = wlg.wavelength(ell);
+                axis[i] = _units.owavelength(wlg.wavelength(ell));
+            }
+            auto add = [&](const std::string& id, const std::vector<int>& components) {
+                ProbeQuantity q;
+                q.kind = ProbeQuantity::Opacity;
+                q.fileid = id + "k";
+                q.projectedFileid = id + "tau";
+                q.quantity = "opacity";
+                q.projectedQuantity = "dimensionless";
+                q.description = "opacity";
+                q.projectedDescription = "optical depth";
+                q.components = components;
+                q.compound = true;
+                q.wave = wave;
+                q.axis = axis;
+                result.push_back(q);
+            };
+            if (probe.aggregation == "System")
+                add("", all);
+            else if (probe.aggregation == "Type")
+            {
+                if (!dust.empty()) add("dust_", dust);
+                if (!electrons.empty()) add("elec_", electrons);
+            }
+            else
+                for (int h = 0; h != numMedia; ++h) add(std::to_string(h) + "_", {h});
+        }
+        return result;
+    }
+
+    // the value of cell m in internal units: MediumSystem::dustMassDensity / electronNumberDensity / massDensity / numberDensity
+    // (MediumSystem.cpp:513-550) and opacityExt over a set of components (:591-624; DustMix.cpp:363-367, ElectronMix.cpp:143-146)
+    double Simulation::probeCellValue(const ProbeQuantity& q, int value, int m) const
+    {
+        double result = 0.;
+        for (int h : q.components)
+        {
+            const double n = _density[h][m];
+            const MaterialMix& mix = *_media[h]->mix;
+            if (q.kind == ProbeQuantity::MassDensity)
+                result += n * mix.mass();
+            else if (q.kind == ProbeQuantity::NumberDensity)
+                result += n;
+            else if (mix.isElectrons())
+                result += n * mix.sectionSca(q.wave[value]);
+            else
+                result += n > 0. ? n * mix.sectionExt(q.wave[value]) : 0.;
+        }
+        return result;
+    }
+
+    int Simulation::numProbeMaps() const
+    {
+        int count = 0;
+        for (const ProbeModel& probe : _probes)
+            if (probe.projected) count += static_cast<int>(probeQuantities(probe).size());
+        return count;
+    }
+
+    namespace
+    {
+        [[noreturn]] void noSuchMap(int map) { throw std::runtime_error("probe map index " + std::to_string(map) + " out of range"); }
+    }
+
+    Simulation::ProbeMapInfo Simulation::probeMapInfo(int map) const
+    {
+        int at = 0;
+        for (const ProbeModel& probe : _probes)
+        {
+            if (!probe.projected) continue;
+            for (const ProbeQuantity& q : probeQuantities(probe))
+                if (at++ == map)
+                {
+                    ProbeMapInfo info;
+                    info.fileName = _prefix + "_" + probe.name + (q.projectedFileid.empty() ? "" : "_" + q.projectedFileid) + ".fits";
+                    info.nx = probe.numPixelsX;
+                    info.ny = probe.numPixelsY;
+                    info.sampling = probe.numSampling;
+                    info.numValues = q.numValues();
+                    info.numRays = int64_t(info.nx) * info.ny * info.sampling * info.sampling;
+                    info.afterSetup = probe.afterSetup;
+                    return info;
+                }
+        }
+        noSuchMap(map);
+    }
+
+    namespace
+    {
+        // the rays of the rows [j0, j1) of a projection, ordered by pixel (j, i) and sub-sample (is, js): ParallelProjectionForm.cpp:22-51, 67-88
+        // with the reference's expressions in their order
+        template<typename Probe> void projectionRays(const Probe& form, int j0, int j1, double* origins, double* directions)
+        {
+            const int Nxp = form.numPixelsX;
+            const double xpmin = form.centerX - 0.5 * form.fieldOfViewX;
+            const double xpsiz = form.fieldOfViewX / form.numPixelsX;
+            const double ypmin = form.centerY - 0.5 * form.fieldOfViewY;
+            const double ypsiz = form.fieldOfViewY / form.numPixelsY;
+            const int Nsampling = form.numSampling;
+            const double costheta = cos(form.inclination);
+            const double sintheta = sin(form.inclination);
+            const double cosphi = cos(form.azimuth);
+            const double sinphi = sin(form.azimuth);
+            const double cosomega = cos(form.roll);
+            const double sinomega = sin(form.roll);
+            // k_z: the direction from observer to model, not normalised again (Direction(..., false))
+            const double kzx = -cosphi * sintheta, kzy = -sinphi * sintheta, kzz = -costheta;
+            const double zp = 10. * (form.fieldOfViewX + form.fieldOfViewY);
+            size_t at = 0;
+            for (int j = j0; j != j1; ++j)
+                for (int i = 0; i != Nxp; ++i)
+                    for (int is = 0; is < Nsampling; ++is)
+                        for (int js = 0; js < Nsampling; ++js)
+                        {
+                            double xp = xpmin + (i + (is + 1.0) / (Nsampling + 1.0)) * xpsiz;
+                            double yp = ypmin + (j + (js + 1.0) / (Nsampling + 1.0)) * ypsiz;
+                            double xpp = sinomega * xp - cosomega * yp;
+                            double ypp = cosomega * xp + sinomega * yp;
+                            double zpp = zp;
+                            double x = cosphi * costheta * xpp - sinphi * ypp + cosphi * sintheta * zpp;
+                            double y = sinphi * costheta * xpp + cosphi * ypp + sinphi * sintheta * zpp;
+                            double z = -sintheta * xpp + costheta * zpp;
+                            origins[at] = x, origins[at + 1] = y, origins[at + 2] = z;
+                            directions[at] = kzx, directions[at + 1] = kzy, directions[at + 2] = kzz;
+                            at += 3;
+                        }
+        }
+    }
+
+    void Simulation::probeMapRays(int map, double* origins, double* directions) const
+    {
+        int at = 0;
+        for (const ProbeModel& probe : _probes)
+        {
+            if (!probe.projected) continue;
+            const int count = static_cast<int>(probeQuantities(probe).size());
+            if (map < at + count)
+            {
+                projectionRays(probe, 0, probe.numPixelsY, origins, directions);
+                return;
+            }
+            at += count;
+        }
+        noSuchMap(map);
+    }
+
+    void Simulation::probeMapValues(int map, double* cellValues) const
+    {
+        int at = 0;
+        for (const ProbeModel& probe : _probes)
+        {
+            if (!probe.projected) continue;
+            for (const ProbeQuantity& q : probeQuantities(probe))
+                if (at++ == map)
+                {
+                    const int numCells = _grid->numCells();
+                    for (int v = 0; v != q.numValues(); ++v)
+                        for (int m = 0; m != numCells; ++m) cellValues[size_t(v) * numCells + m] = probeCellValue(q, v, m);
+                    return;
+                }
+        }
+        noSuchMap(map);
+    }
+
+    std::vector<std::string> Simulation::writeProbes(IntegrateFn integrate, void* user, const std::string& outdir, int when) const
+    {
+        std::vector<std::string> files;
+        std::string base = outdir;
+        if (!base.empty() && base.back() != '/') base += '/';
+        base += _prefix + "_";
+        const int numCells = _grid->numCells();
+        for (const ProbeModel& probe : _probes)
+        {
+            if (when >= 0 && (when == 0) != probe.afterSetup) continue;
+            for (const ProbeQuantity& q : probeQuantities(probe))
+            {
+                const int numValues = q.numValues();
+                if (!probe.projected)
+                {
+                    // PerCellForm.cpp:14-38 through TextOutFile (TextOutFile.cpp:61-103): the cell index as 'd', the values as 'e' with 9 digits
+                    const double unitFactor = _units.out(q.quantity, 1.);
+                    const std::string unit = _units.unit(q.quantity);
+                    const std::string path = base + probe.name + (q.fileid.empty() ? "" : "_" + q.fileid) + ".dat";
+                    std::ofstream out(path);
+                    if (!out) throw std::runtime_error("Could not open output file " + path);
+                    std::string title = q.description + " per spatial cell";
+                    title[0] = static_cast<char>(std::toupper(static_cast<unsigned char>(title[0])));
+                    out << "# " << title << std::endl;
+                    out << "# column 1: spatial cell index (1)" << std::endl;
+                    if (!q.compound)
+                        out << "# column 2: " << q.description << " (" << unit << ")" << std::endl;
+                    else
+                        for (int v = 0; v != numValues; ++v)
+                        {
+                            // (StringUtils::toString(outwave, 'g'): six significant digits)
+                            char buf[40];
+                            snprintf(buf, sizeof(buf), "%1.6g", q.axis[v]);
+                            out << "# column " << (v + 2) << ": opacity at " << _units.swavelength() << " = " << buf << " " << _units.uwavelength()
+                                << " (" << unit << ")" << std::endl;
+                        }
+                    for (int m = 0; m != numCells; ++m)
+                    {
+                        char buf[40];
+                        snprintf(buf, sizeof(buf), "%1.0f", double(m));
+                        std::string line = buf;
+                        for (int v = 0; v != numValues; ++v)
+                        {
+                            // ProbeFormBridge::valuesInCell: the value times the unit factor
+                            snprintf(buf, sizeof(buf), " %1.9e", probeCellValue(q, v, m) * unitFactor);
+                            line += buf;
+                        }
+                        out << line << std::endl;
+                    }
+                    files.push_back(path);
+                    continue;
+                }
+
+                // ParallelProjectionForm.cpp:18-116
+                if (!integrate) throw std::runtime_error("probe " + probe.name + " is a projected map: it needs an integrator");
+                const int Nxp = probe.numPixelsX, Nyp = probe.numPixelsY, Ns = probe.numSampling;
+                const int Nsampling2 = Ns * Ns;
+                const double projectedUnitFactor = _units.out(q.projectedQuantity, 1.);
+                std::vector<double> cellValues(size_t(numValues) * numCells);
+                for (int v = 0; v != numValues; ++v)
+                    for (int m = 0; m != numCells; ++m) cellValues[size_t(v) * numCells + m] = probeCellValue(q, v, m);
+                Array vvv(size_t(numValues) * Nyp * Nxp, 0.);
+                // (rows in batches of about a million rays: the rays of a 10000 x 10000 map with 81 samples would not fit in memory at once)
+                const int raysPerRow = Nxp * Nsampling2;
+                const int rowsPerBatch = std::max(1, (1 << 20) / raysPerRow);
+                std::vector<double> origins, directions, sums;
+                for (int j0 = 0; j0 < Nyp; j0 += rowsPerBatch)
+                {
+                    const int j1 = std::min(Nyp, j0 + rowsPerBatch);
+                    const size_t numRays = size_t(j1 - j0) * raysPerRow;
+                    origins.resize(3 * numRays);
+                    directions.resize(3 * numRays);
+                    sums.assign(numRays * numValues, 0.);
+                    projectionRays(probe, j0, j1, origins.data(), directions.data());
+                    if (integrate(user, static_cast<int64_t>(numRays), origins.data(), directions.data(), numValues, cellValues.data(), sums.data()) != 0)
+                        throw std::runtime_error("probe " + probe.name + ": the ray integrator failed");
+                    size_t ray = 0;
+                    for (int j = j0; j != j1; ++j)
+                        for (int i = 0; i != Nxp; ++i)
+                            for (int s = 0; s != Nsampling2; ++s, ++ray)
+                                for (int p = 0; p != numValues; ++p)
+                                {
+                                    // valuesAlongPath: the sum times the projected unit factor; then the share of the sub-sample
+                                    const double value = sums[ray * numValues + p] * projectedUnitFactor;
+                                    vvv[(size_t(p) * Nyp + j) * Nxp + i] += value / Nsampling2;
+                                }
+                }
+                const double xpsiz = probe.fieldOfViewX / probe.numPixelsX, ypsiz = probe.fieldOfViewY / probe.numPixelsY;
+                const std::string path = base + probe.name + (q.projectedFileid.empty() ? "" : "_" + q.projectedFileid) + ".fits";
+                writeFitsCube(path, vvv.data(), _units.unit(q.projectedQuantity), Nxp, Nyp, _units.out("length", xpsiz), _units.out("length", ypsiz),
+                              _units.out("length", probe.centerX), _units.out("length", probe.centerY), _units.unit("length"),
+                              q.compound ? q.axis : Array(), q.compound ? _units.uwavelength() : std::string("1"), nullptr);
+                files.push_back(path);
+            }
+        }
+        return files;
+    }
+}

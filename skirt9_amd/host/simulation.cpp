@@ -746,10 +746,55 @@ namespace skh
         }
         if (_instruments.empty()) unsupported("a simulation without instruments");
 
-        // ---- probes: the radiation field per cell (RadiationFieldProbe + PerCellForm); nothing else is on this path
+        // ---- probes: the radiation field per cell (RadiationFieldProbe + PerCellForm); densities and opacities per cell and in parallel
+        //      projection (DensityProbe, OpacityProbe + PerCellForm, ParallelProjectionForm: probes.cpp); nothing else is on this path
         if (const XmlElement* ps = sim.item("probeSystem"))
             for (const XmlElement* pe : ps->items("probes"))
             {
+                if (pe->name == "DensityProbe" || pe->name == "OpacityProbe")
+                {
+                    ProbeModel probe;
+                    probe.type = pe->name;
+                    probe.name = pe->attr("probeName", "");
+                    // (SpatialGridFormProbe.hpp:23: the default form is DefaultCutsForm)
+                    const XmlElement* form = pe->item("form");
+                    const std::string formName = form ? form->name : std::string("DefaultCutsForm");
+                    if (formName != "PerCellForm" && formName != "ParallelProjectionForm") unsupported("probe form " + formName);
+                    // (SpatialGridWhenFormProbe.hpp:31: Setup unless the probe is a temperature probe)
+                    const std::string after = pe->attr("probeAfter", "Setup");
+                    if (after != "Setup" && after != "Run") unsupported(pe->name + " probeAfter " + after);
+                    probe.afterSetup = after == "Setup";
+                    probe.aggregation = pe->attr("aggregation", "Type");
+                    if (probe.aggregation == "Fragment") unsupported(pe->name + " aggregation Fragment");
+                    if (probe.aggregation != "Type" && probe.aggregation != "Component" && !(probe.aggregation == "System" && pe->name == "OpacityProbe"))
+                        throw std::runtime_error("ski: invalid aggregation '" + probe.aggregation + "' for " + pe->name);
+                    probe.projected = formName == "ParallelProjectionForm";
+                    if (probe.projected)
+                    {
+                        // ParallelProjectionForm.hpp:40-92
+                        probe.inclination = rd.quantity(*form, "inclination", "posangle", "0 deg");
+                        probe.azimuth = rd.quantity(*form, "azimuth", "posangle", "0 deg");
+                        probe.roll = rd.quantity(*form, "roll", "posangle", "0 deg");
+                        probe.fieldOfViewX = rd.quantity(*form, "fieldOfViewX", "length");
+                        probe.fieldOfViewY = rd.quantity(*form, "fieldOfViewY", "length");
+                        probe.centerX = rd.quantity(*form, "centerX", "length", "0");
+                        probe.centerY = rd.quantity(*form, "centerY", "length", "0");
+                        probe.numPixelsX = rd.integer(*form, "numPixelsX", 250);
+                        probe.numPixelsY = rd.integer(*form, "numPixelsY", 250);
+                        probe.numSampling = rd.integer(*form, "numSampling", 1);
+                        if (!(probe.fieldOfViewX > 0.) || !(probe.fieldOfViewY > 0.) || probe.numPixelsX < 1 || probe.numPixelsX > 10000
+                            || probe.numPixelsY < 1 || probe.numPixelsY > 10000 || probe.numSampling < 1 || probe.numSampling > 9)
+                            throw std::runtime_error("ski: ParallelProjectionForm of probe " + probe.name + ": value out of range");
+                    }
+                    if (const XmlElement* wg = pe->item("wavelengthGrid"))
+                    {
+                        if (pe->name != "OpacityProbe") throw std::runtime_error("ski: DensityProbe has no wavelengthGrid");
+                        if (_oligo) unsupported("OpacityProbe wavelengthGrid in an oligochromatic simulation");
+                        probe.ownGrid = makeWavelengthGrid(*wg, rd);
+                    }
+                    _probes.push_back(std::move(probe));
+                    continue;
+                }
                 if (pe->name != "RadiationFieldProbe") unsupported("probe " + pe->name);
                 const XmlElement* form = pe->item("form");
                 if (!form || form->name != "PerCellForm") unsupported("probe form " + (form ? form->name : std::string("(none)")));
@@ -820,6 +865,17 @@ namespace skh
         if (_rfGrid && !_oligo) addGrid(_rfGrid);  // Configuration.cpp:576-579,644
         for (auto& ins : _instruments)
             if (ins.ownGrid) addGrid(ins.ownGrid.get());
+        // an OpacityProbe's own grid is a MaterialWavelengthRangeInterface item (OpacityProbe.cpp:18-33, Configuration.cpp:594-596, 657-659);
+        // the grid in effect for every probe: Configuration::wavelengthGrid (Configuration.cpp:666-671)
+        for (auto& probe : _probes)
+        {
+            if (probe.ownGrid) addGrid(probe.ownGrid.get());
+            if (probe.type == "OpacityProbe" && _hasMedium)
+            {
+                probe.grid = (probe.ownGrid && !_oligo) ? probe.ownGrid.get() : defaultGrid;
+                if (!probe.grid) throw std::runtime_error("Cannot find a wavelength grid for instrument or probe");
+            }
+        }
         // MaterialWavelengthRangeInterface items: the normalisation wavelength and the tree policy wavelength
         for (auto& part : _media)
             if (part->normalizationWavelength() > 0)

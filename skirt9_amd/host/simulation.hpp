@@ -50,6 +50,29 @@ namespace skh
         int64_t radiationFieldSize() const;
         std::vector<std::string> writeRadiationField(const double* rf, const std::string& outdir) const;
 
+        // Probe maps (DensityProbe, OpacityProbe; ParallelProjectionForm, PerCellForm): probes.cpp.  A projected map is one FITS file: the
+        // pixels are sums over sub-sample rays of line integrals through the grid, which the caller's integrator computes (the engine's
+        // pmc_integrate_rays, handed over at run time: this library does not link the engine)
+        struct ProbeMapInfo
+        {
+            std::string fileName;  // <prefix>_<probeName>_<projectedFileid>.fits
+            int nx{0}, ny{0}, sampling{1}, numValues{1};
+            int64_t numRays{0};    // nx * ny * sampling^2
+            bool afterSetup{true};
+        };
+        // sums[i * numValues + v] = sum over the path of ray i of ds * cellValues[v * numCells + m]; nonzero: failure
+        typedef int (*IntegrateFn)(void* user, int64_t numRays, const double* origins, const double* directions, int32_t numValues,
+                                   const double* cellValues, double* sums);
+        int numProbeMaps() const;
+        ProbeMapInfo probeMapInfo(int map) const;
+        // the rays of a map, [numRays][3] each, ordered by pixel (j, i) and sub-sample (is, js) (ParallelProjectionForm.cpp:67-88)
+        void probeMapRays(int map, double* origins, double* directions) const;
+        // its cell values [numValues][numCells] in internal units (the projected unit factor is applied to the sums)
+        void probeMapValues(int map, double* cellValues) const;
+        // writes the probe files; when: 0 the probes with probeAfter Setup, 1 those with Run, -1 all.  The per-cell files need no
+        // integrator, which may be null when no projected map is written
+        std::vector<std::string> writeProbes(IntegrateFn integrate, void* user, const std::string& outdir, int when = -1) const;
+
         // human-readable summary (grid size, tables, ...) for logs and tests
         std::string summary() const;
 
@@ -111,6 +134,21 @@ namespace skh
         std::unique_ptr<WavelengthGrid> _rfGridOwn;       // radiationFieldWLG as configured (panchromatic)
         const WavelengthGrid* _rfGrid{nullptr};           // Configuration::radiationFieldWLG()
         std::vector<std::string> _rfProbeNames;           // RadiationFieldProbe items with a PerCellForm
+        // DensityProbe and OpacityProbe items
+        struct ProbeModel
+        {
+            std::string type, name, aggregation;  // aggregation: System | Type | Component
+            bool afterSetup{true};
+            bool projected{false};                // ParallelProjectionForm (else PerCellForm)
+            double inclination{0}, azimuth{0}, roll{0}, fieldOfViewX{0}, fieldOfViewY{0}, centerX{0}, centerY{0};
+            int numPixelsX{250}, numPixelsY{250}, numSampling{1};
+            std::unique_ptr<WavelengthGrid> ownGrid;  // OpacityProbe::wavelengthGrid (panchromatic only)
+            const WavelengthGrid* grid{nullptr};      // Configuration::wavelengthGrid(ownGrid), set by setup()
+        };
+        std::vector<ProbeModel> _probes;
+        struct ProbeQuantity;
+        std::vector<ProbeQuantity> probeQuantities(const ProbeModel& probe) const;
+        double probeCellValue(const ProbeQuantity& quantity, int value, int m) const;
         // instruments
         std::unique_ptr<WavelengthGrid> _defaultGrid;     // as configured in the ski (panchromatic)
         std::unique_ptr<WavelengthGrid> _oligoGrid;       // OligoWavelengthGrid

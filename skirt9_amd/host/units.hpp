@@ -126,6 +126,32 @@ namespace skh
             add("frequencymeanintensity", "MJy/sr", 1e-20);
             add("neutralsurfacebrightness", "W/m2/sr", 1.);
             add("neutralsurfacebrightness", "W/m2/arcsec2", 1. / arcsec2);
+            // the quantities of the density and opacity probes (SkirtUnitDef.cpp:161-209, 554-555)
+            add("masssurfacedensity", "kg/m2", 1.);
+            add("masssurfacedensity", "g/cm2", 10.);
+            add("masssurfacedensity", "Msun/AU2", Msun / pow(AU, 2));
+            add("masssurfacedensity", "Msun/pc2", Msun / pow(pc, 2));
+            add("massvolumedensity", "kg/m3", 1.);
+            add("massvolumedensity", "g/cm3", 1e3);
+            add("massvolumedensity", "Msun/AU3", Msun / pow(AU, 3));
+            add("massvolumedensity", "Msun/pc3", Msun / pow(pc, 3));
+            for (const char* one : {"1", ""})
+            {
+                const std::string per = one;
+                add("numbersurfacedensity", per + "/m2", 1.);
+                add("numbersurfacedensity", per + "/cm2", 1e4);
+                add("numbersurfacedensity", per + "/AU2", 1 / pow(AU, 2));
+                add("numbersurfacedensity", per + "/pc2", 1 / pow(pc, 2));
+                add("numbervolumedensity", per + "/m3", 1.);
+                add("numbervolumedensity", per + "/cm3", 1e6);
+                add("numbervolumedensity", per + "/AU3", 1 / pow(AU, 3));
+                add("numbervolumedensity", per + "/pc3", 1 / pow(pc, 3));
+                add("opacity", per + "/m", 1.);
+                add("opacity", per + "/cm", 1e2);
+                add("opacity", per + "/AU", 1 / AU);
+                add("opacity", per + "/pc", 1 / pc);
+            }
+            add("dimensionless", "1", 1.);
 
             // default units per unit system (SkirtUnitDef.cpp:556-764)
             def("SIUnits", {{"neutralmeanintensity", "W/m2/sr"}, {"wavelengthmeanintensity", "W/m3/sr"},
@@ -134,7 +160,9 @@ namespace skh
                             {"bolluminosity", "W"}, {"angle", "rad"}, {"posangle", "rad"},
                             {"frequencyfluxdensity", "W/m2/Hz"}, {"frequencysurfacebrightness", "W/m2/Hz/sr"},
                             {"wavelengthfluxdensity", "W/m3"}, {"wavelengthsurfacebrightness", "W/m3/sr"},
-                            {"neutralfluxdensity", "W/m2"}, {"neutralsurfacebrightness", "W/m2/sr"}});
+                            {"neutralfluxdensity", "W/m2"}, {"neutralsurfacebrightness", "W/m2/sr"},
+                            {"masssurfacedensity", "kg/m2"}, {"massvolumedensity", "kg/m3"}, {"numbersurfacedensity", "1/m2"},
+                            {"numbervolumedensity", "1/m3"}, {"opacity", "1/m"}, {"dimensionless", "1"}});
             def("StellarUnits", {{"neutralmeanintensity", "W/m2/sr"}, {"wavelengthmeanintensity", "W/m2/micron/sr"},
                                  {"frequencymeanintensity", "W/m2/Hz/sr"}, {"length", "AU"}, {"distance", "pc"}, {"wavelength", "micron"}, {"velocity", "km/s"},
                                  {"masscoefficient", "m2/kg"}, {"mass", "Msun"}, {"temperature", "K"}, {"magneticfield", "uG"},
@@ -142,7 +170,9 @@ namespace skh
                                  {"frequencyfluxdensity", "Jy"}, {"frequencysurfacebrightness", "MJy/sr"},
                                  {"wavelengthfluxdensity", "W/m2/micron"},
                                  {"wavelengthsurfacebrightness", "W/m2/micron/arcsec2"},
-                                 {"neutralfluxdensity", "W/m2"}, {"neutralsurfacebrightness", "W/m2/arcsec2"}});
+                                 {"neutralfluxdensity", "W/m2"}, {"neutralsurfacebrightness", "W/m2/arcsec2"},
+                                 {"masssurfacedensity", "Msun/AU2"}, {"massvolumedensity", "Msun/AU3"}, {"numbersurfacedensity", "1/cm2"},
+                                 {"numbervolumedensity", "1/cm3"}, {"opacity", "1/AU"}, {"dimensionless", "1"}});
             def("ExtragalacticUnits",
                 {{"neutralmeanintensity", "W/m2/sr"}, {"wavelengthmeanintensity", "W/m2/micron/sr"},
                  {"frequencymeanintensity", "W/m2/Hz/sr"},
@@ -151,7 +181,9 @@ namespace skh
                  {"angle", "arcsec"}, {"posangle", "deg"}, {"frequencyfluxdensity", "Jy"},
                  {"frequencysurfacebrightness", "MJy/sr"}, {"wavelengthfluxdensity", "W/m2/micron"},
                  {"wavelengthsurfacebrightness", "W/m2/micron/arcsec2"}, {"neutralfluxdensity", "W/m2"},
-                 {"neutralsurfacebrightness", "W/m2/arcsec2"}});
+                 {"neutralsurfacebrightness", "W/m2/arcsec2"},
+                 {"masssurfacedensity", "Msun/pc2"}, {"massvolumedensity", "Msun/pc3"}, {"numbersurfacedensity", "1/cm2"},
+                 {"numbervolumedensity", "1/cm3"}, {"opacity", "1/pc"}, {"dimensionless", "1"}});
         }
 
         bool hasSystem(const std::string& system) const { return _systems.count(system) != 0; }
