@@ -20,7 +20,7 @@ void pmcSetError(const std::string& message)
     t_error = message;
 }
 
-// device buffers of one pmc_integrate_rays call: freed when the call returns, whichever way
+// device buffers of one pmc_trace_ray or pmc_integrate_rays call: freed when the call returns, whichever way
 namespace
 {
     struct ScratchBuffers
@@ -883,10 +883,11 @@ int pmc_trace_ray(pmc_ctx* ctx, const double r[3], const double k[3], int32_t* m
     double* dds = nullptr;
     int32_t* dn = nullptr;
     double* dk = nullptr;
-    HIP_TRY(hipMalloc(&dm, sizeof(int32_t) * room * flavours));
-    HIP_TRY(hipMalloc(&dds, sizeof(double) * room * flavours));
-    HIP_TRY(hipMalloc(&dn, sizeof(int32_t) * flavours));
-    HIP_TRY(hipMalloc(&dk, sizeof(double) * 3));
+    ScratchBuffers scratch;
+    HIP_TRY(scratch.get(room * flavours, &dm));
+    HIP_TRY(scratch.get(room * flavours, &dds));
+    HIP_TRY(scratch.get(size_t(flavours), &dn));
+    HIP_TRY(scratch.get(size_t(3), &dk));
     hipError_t e = hipMemcpy(dk, k, 3 * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess && ctx->sceneDirty)
     {
@@ -919,10 +920,6 @@ int pmc_trace_ray(pmc_ctx* ctx, const double r[3], const double k[3], int32_t* m
                 rc = fail(PMC_ERR_DEVICE, "octree traversal: the scalar-direction and vector-direction steps disagree on this ray");
         }
     }
-    hipFree(dm);
-    hipFree(dds);
-    hipFree(dn);
-    hipFree(dk);
     return rc;
 }
 
@@ -1020,7 +1017,7 @@ int pmc_integrate_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, co
     hipEventDestroy(evB);
     if (e != hipSuccess) return hipFail(e, "pmc_integrate_rays");
     if (capped)
-        return fail(PMC_ERR_DEVICE, "pmc_integrate_rays: " + std::to_string(capped) + " ray walk(s) were still inside the grid after 100000 cells (traversal error)");
+        return fail(PMC_ERR_DEVICE, "pmc_integrate_rays: " + std::to_string(capped) + " ray walk(s) were still inside the grid after " PMC_STRINGIFY(PMC_RAY_STEP_CAP) " cells (traversal error)");
     return PMC_OK;
 }
 

@@ -529,6 +529,8 @@ struct PeelSortedArgs  // peel-off kernel; rec == nullptr: task records from Tas
 #ifndef PMC_VORO_CONES
 #define PMC_VORO_CONES 192  // direction cones of DevScene::vcull: 48, or 192 (every cone divided at the midpoints of its edges)
 #endif
+#define PMC_RAY_STEP_CAP 100000  // cell segments per ray of the ray kernels (pmc_ray.inc): the guard against a traversal that never leaves the grid
+
 #define PMC_RF_LOG_CHUNK 4096
 #define PMC_RF_BUCKET_BITS 13  // keys per partition of the log: 2^13 doubles = 64 KB of LDS in rfReduceKernel
 

@@ -36,6 +36,10 @@
 // The host enqueues generations until no slot is alive (pmc_api.hip); one 8-byte readback per generation and group tells
 // it when a group is done, and the kernels of the other groups keep the device busy meanwhile.
 //
+// Outside the photon loop, pmc_ray.inc runs single rays through the same traversal code: one ray cursor (rayStart, rayAdvance) under
+// traceRayKernel (pmc_trace_ray: the (m, ds) of one ray, for the bit-exact check) and integrateRaysKernel (pmc_integrate_rays: one ray per lane,
+// the probe maps' line integrals).
+//
 // The reference stores the whole path (<= 1000 x 40 B per thread) and binary-searches the interaction point
 // (SpatialGridPath.cpp:164-206).  Here the path is walked twice with bit-identical arithmetic instead: pass 1 yields
 // tau_path, pass 2 stops in the segment whose cumulative tau exceeds the sampled value and interpolates exactly as
@@ -270,7 +274,7 @@ namespace
 #include "pmc_walk.inc"
 #include "pmc_walk_tree.inc"
 #include "pmc_transition.inc"
-#include "pmc_probe.inc"
+#include "pmc_ray.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -341,6 +345,24 @@ static const auto peel2Kernels = flavourTable<16>([](auto f) {
     return KernelFlavour<PeelKernel2>{walkPeelKernel2<(F & 8) != 0, F & 7>, 16 + pmcPeelQueueBytes()};
 });
 
+// ray kernels (pmc_ray.inc), member i of a family: the octree, the wide octree, the Cartesian, Voronoi and binary-tree grids
+constexpr Grid RAY_GRIDS[5] = {GRID_TREE, GRID_TREE, GRID_CART, GRID_VORO, GRID_BIN};
+static int rayKernelIndex(int gridKind, int wide)
+{
+    return gridKind == PMC_GRID_OCTREE ? (wide ? 1 : 0) : gridKind == PMC_GRID_VORONOI ? 3 : gridKind == PMC_GRID_BINTREE ? 4 : 2;
+}
+typedef void (*IntegrateKernel)(int, ProbeArgs);
+static const auto integrateKernels = flavourTable<5>([](auto f) {
+    constexpr int F = decltype(f)::value;
+    return KernelFlavour<IntegrateKernel>{integrateRaysKernel<RAY_GRIDS[F], F == 1>, 0};
+});
+// single-ray tracer: the five with the direction in scalar registers, then the octree's two with the direction in vector registers
+typedef void (*TraceKernel)(int, double, double, double, double, double, double, const double*, int32_t*, double*, int32_t, int32_t*);
+static const auto traceKernels = flavourTable<7>([](auto f) {
+    constexpr int F = decltype(f)::value;
+    return KernelFlavour<TraceKernel>{traceRayKernel<RAY_GRIDS[F % 5], F % 5 == 1, (F < 5)>, 0};
+});
+
 template<typename Table> static hipError_t raiseLdsLimits(const Table& table, size_t walkMax)
 {
     for (const auto& k : table)
@@ -377,25 +399,14 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
         if (e != hipSuccess) return e;
     }
     for (hipError_t e : {raiseLdsLimits(peelKernels, walkMax), raiseLdsLimits(peel2Kernels, walkMax), raiseLdsLimits(propKernels, walkMax),
-                         raiseLdsLimits(walkKernels, walkMax), raiseLdsLimits(binWalkKernels, walkMax)})
+                         raiseLdsLimits(walkKernels, walkMax), raiseLdsLimits(binWalkKernels, walkMax), raiseLdsLimits(traceKernels, walkMax),
+                         raiseLdsLimits(integrateKernels, walkMax)})
         if (e != hipSuccess) return e;
     const struct
     {
         const void* kernel;
         size_t lds;
-    } all[] = {{reinterpret_cast<const void*>(&traceTreeKernel<false, false>), walkMax},
-               {reinterpret_cast<const void*>(&traceTreeKernel<false, true>), walkMax},
-               {reinterpret_cast<const void*>(&traceTreeKernel<true, false>), walkMax},
-               {reinterpret_cast<const void*>(&traceTreeKernel<true, true>), walkMax},
-               {reinterpret_cast<const void*>(&traceRayKernel<GRID_CART>), walkMax},
-               {reinterpret_cast<const void*>(&traceRayKernel<GRID_VORO>), walkMax},
-               {reinterpret_cast<const void*>(&traceRayKernel<GRID_BIN>), walkMax},
-               {reinterpret_cast<const void*>(&integrateRaysKernel<GRID_TREE, false>), walkMax},
-               {reinterpret_cast<const void*>(&integrateRaysKernel<GRID_TREE, true>), walkMax},
-               {reinterpret_cast<const void*>(&integrateRaysKernel<GRID_CART, false>), walkMax},
-               {reinterpret_cast<const void*>(&integrateRaysKernel<GRID_VORO, false>), walkMax},
-               {reinterpret_cast<const void*>(&integrateRaysKernel<GRID_BIN, false>), walkMax},
-               {reinterpret_cast<const void*>(&transitionKernel), transitionMax},
+    } all[] = {{reinterpret_cast<const void*>(&transitionKernel), transitionMax},
                {reinterpret_cast<const void*>(&transitionDipoleKernel), transitionMax},
                {reinterpret_cast<const void*>(&transitionKinKernel), transitionMax},
                {reinterpret_cast<const void*>(&transitionKinDipoleKernel), transitionMax},
@@ -718,29 +729,19 @@ extern "C" hipError_t pmcLaunchTrace(int slot, int gridKind, int wide, int unifo
                                      const double* kdev, int32_t* m, double* ds, int32_t cap, int32_t* n, size_t ldsBytes,
                                      hipStream_t stream)
 {
-    if (gridKind == PMC_GRID_OCTREE)
-    {
-        auto kernel = wide ? (uniform ? traceTreeKernel<true, true> : traceTreeKernel<true, false>)
-                           : (uniform ? traceTreeKernel<false, true> : traceTreeKernel<false, false>);
-        hipLaunchKernelGGL(kernel, dim3(1), dim3(64), ldsBytes, stream, slot, r[0], r[1], r[2], k[0], k[1], k[2], kdev, m, ds, cap, n);
-    }
-    else
-        hipLaunchKernelGGL(gridKind == PMC_GRID_VORONOI ? traceRayKernel<GRID_VORO> : gridKind == PMC_GRID_BINTREE ? traceRayKernel<GRID_BIN> : traceRayKernel<GRID_CART>, dim3(1), dim3(64), ldsBytes, stream, slot, r[0],
-                           r[1], r[2], k[0], k[1], k[2], m, ds, cap, n);
+    const TraceKernel kernel = traceKernels[rayKernelIndex(gridKind, wide) + (gridKind == PMC_GRID_OCTREE && !uniform ? 5 : 0)].kernel;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(64), ldsBytes, stream, slot, r[0], r[1], r[2], k[0], k[1], k[2], kdev, m, ds, cap, n);
     return hipGetLastError();
 }
 
-// batched ray integrals (pmc_probe.inc): one pass of PMC_INTEGRATE_PASS_VALUES values over numRays rays; `work` = the kernel's cursor and counters,
+// batched ray integrals (pmc_ray.inc): one pass of PMC_INTEGRATE_PASS_VALUES values over numRays rays; `work` = the kernel's cursor and counters,
 // zeroed by the caller (pmcProbeWorkWords words)
 extern "C" int pmcProbeWorkWords(void) { return PROBE_WORK_WORDS; }
 extern "C" hipError_t pmcLaunchIntegrate(int slot, int gridKind, int wide, const double* origins, const double* directions, const double* q, double* sums,
                                          unsigned long long numRays, unsigned long long* work, int grid, size_t ldsBytes, hipStream_t stream)
 {
     const ProbeArgs A = {origins, directions, q, sums, numRays, work};
-    const auto kernel = gridKind == PMC_GRID_OCTREE    ? (wide ? integrateRaysKernel<GRID_TREE, true> : integrateRaysKernel<GRID_TREE, false>)
-                        : gridKind == PMC_GRID_VORONOI ? integrateRaysKernel<GRID_VORO, false>
-                        : gridKind == PMC_GRID_BINTREE ? integrateRaysKernel<GRID_BIN, false>
-                                                       : integrateRaysKernel<GRID_CART, false>;
+    const IntegrateKernel kernel = integrateKernels[rayKernelIndex(gridKind, wide)].kernel;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), ldsBytes, stream, slot, A);
     return hipGetLastError();
 }

@@ -2183,78 +2183,3 @@
         v = waveSum(rewalks);
         if (lane == 0 && v) atomicAdd(S.counters + 6, v);
     }
-
-    // ================================================================================================
-    //  single-ray tracer (Cartesian, Voronoi and binary-tree grids; the octree's is in pmc_walk_tree.inc): the same traversal code,
-    //  one lane, (m, ds) written out
-    // ================================================================================================
-    template<int GRID> __global__ void traceRayKernel(const int sceneSlot, double rx, double ry, double rz, double kx, double ky,
-                                                      double kz, int32_t* mOut, double* dsOut, int32_t cap, int32_t* nOut)
-    {
-        static_assert(GRID != GRID_TREE, "the octree tracer is traceTreeKernel");
-        const DevScene& S = c_scene[sceneSlot];
-        extern __shared__ double lds[];
-        const int tid = threadIdx.x;
-        stageGrid<GRID>(S, lds, tid, blockDim.x);
-        __syncthreads();
-        if (tid != 0) return;
-        const GridLds L = makeGridLds(S, lds);
-        Walk w;
-        w.rx = rx, w.ry = ry, w.rz = rz;
-        setDirection(w, kx, ky, kz);
-        int n = 0;
-        w.tau = 0., w.s = 0., w.lastm = -1;
-        double cumds;
-        bool ok = moveInside(S, w, cumds);
-        if (ok)
-        {
-            if (cumds > 0.)
-            {
-                if (n < cap)
-                {
-                    mOut[n] = -1;
-                    dsOut[n] = cumds;
-                }
-                ++n;
-            }
-            if (GRID == GRID_CART)
-            {
-                w.ci = locateClip(L.grid, S.nx + 1, w.rx);
-                w.cj = locateClip(L.grid + (S.nx + 1), S.ny + 1, w.ry);
-                w.ck = locateClip(L.grid + (S.nx + 1) + (S.ny + 1), S.nz + 1, w.rz);
-                cartEnter(S, L, w);
-            }
-            else if (GRID == GRID_BIN)
-                binStart(S, w, -1);
-            else
-                ok = voroLocateAndEnter(S, w);
-            bool inside = ok;
-            int guard = 0;
-            while (inside && guard++ < 100000)
-            {
-                if (n < cap)
-                {
-                    mOut[n] = GRID == GRID_BIN ? S.cell_ext[w.cell] : w.cell;
-                    dsOut[n] = w.ds;
-                }
-                ++n;
-                if (GRID == GRID_BIN)
-                {
-                    // (the step of the walk kernel, and its service round for an undecided one)
-                    const int r = binAdvance(S, w);
-                    inside = r == ST_ACTIVE || (r == ST_SLOW && binStepSlow(S, w));
-                }
-                else if (GRID == GRID_VORO)
-                {
-                    const int r = voroAdvance(S, w);
-                    if (r == ST_SLOW)
-                        inside = voroStepSlow(S, w);
-                    else if (r == ST_EXIT)
-                        inside = false;
-                }
-                else
-                    inside = cartAdvance(S, L, w);
-            }
-        }
-        *nOut = n;
-    }

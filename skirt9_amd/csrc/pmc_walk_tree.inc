@@ -140,6 +140,24 @@
         d.posy = ((d.sgn >> 1) & 1u) - 1u;
         d.posz = ((d.sgn >> 2) & 1u) - 1u;
     }
+    // the direction of the generic Walk
+    __device__ __forceinline__ void dirFromWalk(const Walk& g, Dir& d)
+    {
+        d.kx = g.kx, d.ky = g.ky, d.kz = g.kz;
+        d.ikx = g.ikx, d.iky = g.iky, d.ikz = g.ikz;
+        d.sgn = g.sgn;
+        setDirMasks(d);
+    }
+    // position, pending segment and cell of the generic Walk (treeEnter, treeStepSlow); the running sums stay the caller's
+    template<bool WIDE> __device__ __forceinline__ void treeWalkFrom(const Walk& g, TWalk<WIDE>& w)
+    {
+        w.rx = g.rx, w.ry = g.ry, w.rz = g.rz;
+        w.ds = g.ds;
+        w.dens = g.dens;
+        w.cell = (uint32_t)g.cell;
+        w.axis = (uint32_t)g.axis;
+        setBox<WIDE>(w, (typename Pack<WIDE>::T)g.P, g.e);
+    }
     // SGN >= 0: the sign pattern of the direction is a compile-time constant (the peel-off kernel is instantiated per octant of the
     // observer's direction: every selection by sign folds away); SGN < 0: the direction's own (per lane, or in scalar registers)
     template<int SGN> __device__ __forceinline__ bool dirUpX(const Dir& d) { return SGN >= 0 ? !(SGN & 1) : d.posx != 0u; }
@@ -300,12 +318,7 @@
         g.cell = (int)w.cell;
         g.axis = (int)w.axis;
         if (!treeStepSlow(S, L, g)) return false;
-        w.rx = g.rx, w.ry = g.ry, w.rz = g.rz;
-        w.ds = g.ds;
-        w.dens = g.dens;
-        w.cell = (uint32_t)g.cell;
-        w.axis = (uint32_t)g.axis;
-        setBox<WIDE>(w, (typename Pack<WIDE>::T)g.P, g.e);
+        treeWalkFrom<WIDE>(g, w);
         return true;
     }
     __device__ __forceinline__ int treeEdgeStateAt(const TreeConst& C, double rx, double ry, double rz)
@@ -1547,115 +1560,4 @@
             }
             pos = end;
         }
-    }
-
-    // ================================================================================================
-    //  single-ray tracer on the octree: the traversal code of the walk kernels, one lane, (m, ds) written out.
-    //  UNIFORM: the direction comes from kernel arguments (scalar registers) and the steps run in the instantiation for the
-    //  direction's sign octant, as in the peel-off kernel; otherwise the direction comes from memory through the lane index
-    //  (vector registers, signs at run time, as in the propagation kernel)
-    // ================================================================================================
-    template<bool WIDE, int SGNX>
-    __device__ __forceinline__ int traceTreeSteps(const DevScene& S, const GridLds& L, const TreeConst& C, const char* nodes, const Dir& d, TWalk<WIDE>& w,
-                                                  int32_t* mOut, double* dsOut, int32_t cap, int n)
-    {
-        bool inside = true;
-        int guard = 0;
-        while (inside && guard++ < 100000)
-        {
-            if (n < cap)
-            {
-                mOut[n] = S.cell_ext[w.cell];
-                dsOut[n] = w.ds;
-            }
-            ++n;
-            CellLoad g;
-            cellIssue(C, w.cell, g);
-            const double step = w.ds + S.eps;
-            const double nrx = w.rx + d.kx * step, nry = w.ry + d.ky * step, nrz = w.rz + d.kz * step;
-            const uint32_t link = cellLink<SGNX>(g, d, w.axis);
-            w.rx = nrx, w.ry = nry, w.rz = nrz;
-#ifdef PMC_PROFILE
-            WalkProf prof = {{0, 0, 0, 0, 0, 0, 0, 0}, 0, {0, 0, 0, 0, 0, 0, 0, 0}};
-#endif
-            uint32_t cell2;
-            int r = treeResolve<WIDE, SGNX>(C, nodes, d, w, link, nrx, nry, nrz, cell2 PMC_WPROF_PASS);
-            if (r == ST_ACTIVE)
-            {
-                r = treeEnterBox<WIDE, SGNX>(C, d, w PMC_WPROF_PASS);
-                if (r == ST_ACTIVE) w.cell = cell2;
-            }
-            if (r == ST_EDGE) r = treeEdgeStateAt(C, w.rx, w.ry, w.rz);
-            if (r == ST_SLOW)
-                inside = treeSlowStep<WIDE>(S, L, d, w);
-            else if (r == ST_EXIT)
-                inside = false;
-        }
-        return n;
-    }
-
-    template<bool WIDE, bool UNIFORM>
-    __global__ void traceTreeKernel(const int sceneSlot, double rx, double ry, double rz, double kx, double ky, double kz,
-                                    const double* kdev, int32_t* mOut, double* dsOut, int32_t cap, int32_t* nOut)
-    {
-        const DevScene& S = c_scene[sceneSlot];
-        extern __shared__ double lds[];
-        const int tid = threadIdx.x;
-        requireLdsBaseZero(lds);
-        stageGrid<GRID_TREE>(S, lds, tid, blockDim.x);
-        __syncthreads();
-        if (tid != 0) return;
-        GridLds L = makeGridLds(S, lds);
-        if (!WIDE) L.gtab = nullptr;  // (octrees up to level 10 always have their table in LDS: the test folds away)
-        const char* leaves = reinterpret_cast<const char*>(S.leaves);
-        const char* nodes = reinterpret_cast<const char*>(S.nodes);
-        TreeConst C;
-        loadTreeConst(S, C);
-        if (!UNIFORM) kx = kdev[tid], ky = kdev[tid + 1], kz = kdev[tid + 2];
-        Walk g;
-        g.rx = rx, g.ry = ry, g.rz = rz;
-        setDirection(g, kx, ky, kz);
-        Dir d;
-        d.kx = g.kx, d.ky = g.ky, d.kz = g.kz;
-        d.ikx = g.ikx, d.iky = g.iky, d.ikz = g.ikz;
-        d.sgn = g.sgn;
-        setDirMasks(d);
-        int n = 0;
-        g.tau = 0., g.s = 0., g.lastm = -1;
-        double cumds;
-        if (moveInside(S, g, cumds))
-        {
-            if (cumds > 0.)
-            {
-                if (n < cap)
-                {
-                    mOut[n] = -1;
-                    dsOut[n] = cumds;
-                }
-                ++n;
-            }
-            const int m = topDown(S, L, g.rx, g.ry, g.rz);
-            treeEnter<false>(leaves, L, g, m);
-            TWalk<WIDE> w;
-            w.rx = g.rx, w.ry = g.ry, w.rz = g.rz;
-            w.tau = 0., w.s = 0., w.lastm = -1;
-            w.ds = g.ds, w.dens = g.dens;
-            w.cell = (uint32_t)g.cell, w.axis = (uint32_t)g.axis;
-            setBox<WIDE>(w, (typename Pack<WIDE>::T)g.P, g.e);
-            if (!UNIFORM)
-                n = traceTreeSteps<WIDE, -1>(S, L, C, nodes, d, w, mOut, dsOut, cap, n);
-            else
-                switch (d.sgn & 7u)
-                {
-                    case 0: n = traceTreeSteps<WIDE, 0>(S, L, C, nodes, d, w, mOut, dsOut, cap, n); break;
-                    case 1: n = traceTreeSteps<WIDE, 1>(S, L, C, nodes, d, w, mOut, dsOut, cap, n); break;
-                    case 2: n = traceTreeSteps<WIDE, 2>(S, L, C, nodes, d, w, mOut, dsOut, cap, n); break;
-                    case 3: n = traceTreeSteps<WIDE, 3>(S, L, C, nodes, d, w, mOut, dsOut, cap, n); break;
-                    case 4: n = traceTreeSteps<WIDE, 4>(S, L, C, nodes, d, w, mOut, dsOut, cap, n); break;
-                    case 5: n = traceTreeSteps<WIDE, 5>(S, L, C, nodes, d, w, mOut, dsOut, cap, n); break;
-                    case 6: n = traceTreeSteps<WIDE, 6>(S, L, C, nodes, d, w, mOut, dsOut, cap, n); break;
-                    default: n = traceTreeSteps<WIDE, 7>(S, L, C, nodes, d, w, mOut, dsOut, cap, n); break;
-                }
-        }
-        *nOut = n;
     }

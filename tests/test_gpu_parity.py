@@ -55,6 +55,37 @@ def test_trace_ray_bit_exact(name, scale):
         assert np.array_equal(ds_ref.view(np.uint64), ds_gpu.view(np.uint64)), (r, k)
 
 
+@pytest.mark.parametrize("name,half_x,half_z", [("cfg2small.ski", 20000 * 3.0857e16, 4000 * 3.0857e16), ("cfg1.ski", 3.0857e16, 3.0857e16)])
+def test_trace_ray_with_a_cap_below_the_path(name, half_x, half_z):
+    """pmc_trace_ray with fewer entries than the path has segments (include/pmc.h: n reports the whole path, min(cap, n) entries are written):
+    the branch of the recording code that no other test reaches.  One ray per grid kind (octree, Cartesian) that starts outside the grid and
+    crosses it, so that the first segment is the one outside (m = -1); caps 3 and 0 against the full trace, bit for bit, in caller buffers
+    prefilled with a sentinel."""
+    import ctypes as C
+    from skirt9_amd.engine import lib
+    sim = Simulation(ski(name)).setup()
+    eng = _engine(sim)
+    r = np.array([-2.0 * half_x, 0.11 * half_z, -0.07 * half_z])  # (half_x, half_z: the grid's half extents)
+    k = np.array([1.0, 0.02, 0.03])
+    k /= np.linalg.norm(k)
+    m_full, ds_full = eng.trace_ray(r, k)
+    n_full = len(m_full)
+    assert n_full > 4 and m_full[0] == -1 and (m_full[1:] >= 0).all()
+    room = n_full + 8
+    for cap in (3, 0):
+        m = np.full(room, -12345, dtype=np.int32)
+        ds = np.full(room, -777.25)
+        n = C.c_int32(-5)
+        rc = lib().pmc_trace_ray(eng._h, r.ctypes.data_as(C.c_void_p), k.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p),
+                                 ds.ctypes.data_as(C.c_void_p), cap, C.byref(n))
+        assert rc == 0  # PMC_OK
+        assert n.value == n_full
+        got = min(cap, n_full)
+        assert np.array_equal(m[:got], m_full[:got])
+        assert np.array_equal(ds[:got].view(np.uint64), ds_full[:got].view(np.uint64))
+        assert (m[got:] == -12345).all() and (ds[got:] == -777.25).all()
+
+
 def test_deepest_octree_rays_equal_the_reference():
     """tests/ski/cfg4deepest.ski: an octree of EIGHTEEN levels (TreePolicy.hpp:32-35 allows maxLevel up to 99; rounds 1-5 stopped at 15: 20-bit
     byte offsets in the box codes, 4-bit size exponents in links and task records).  The traversal kernel against the REFERENCE's own (m, ds)
