@@ -22,6 +22,9 @@
  *                        MediumSystem.cpp:1294-1300) and MediumSystem::meanIntensity reads (:1370-1380);
  *   pmc_radiation_field_device <- same table as a device pointer, for the counterpart of
  *                        MediumSystem::communicateRadiationField (MediumSystem.cpp:1304-1313: sumToAll) as one RCCL all-reduce
+ *   pmc_dust_temperatures <- MediumSystem::indicativeTemperature for every cell from that table (MediumSystem.cpp:1384-1427,
+ *                        EquilibriumDustEmissionCalculator.cpp:120-130): what TemperatureProbe writes, and the first step of a
+ *                        secondary dust emission source
  *   pmc_sampler_*     <- ParticleSnapshot::density(Position) evaluated for the sample positions of the setup phase
  *                        (ParticleSnapshot.cpp:233-243; DensityTreePolicy.cpp:141, MediumSystem.cpp:91-96)
  *   pmc_counters      <- no reference counterpart: counted cell visits / detector updates for the roofline
@@ -398,6 +401,45 @@ int pmc_integrate_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, co
 /* work of the most recent pmc_integrate_rays on this context: milliseconds in its kernels (HIP events), cell segments added (lane steps), and
    wave iterations that added them (64 lanes each: lanes in use = lane_steps / (64 wave_steps)) */
 int pmc_last_integrate_work(pmc_ctx* ctx, float* kernel_ms, uint64_t* lane_steps, uint64_t* wave_steps);
+/* Weighted averages along many rays (ProbeFormBridge::valuesAlongPath for the averaged quantities, ProbeFormBridge.cpp:652-676): per segment
+   with m >= 0, in path order and without fused multiply-add,
+       weight = ds * cell_weights[m];   sums[i][0] += weight;   sums[i][1 + v] += weight * cell_values[v * num_cells + m]
+   The RAW sums are returned, [num_rays][1 + num_values]: the caller divides (value * (unit factor / sums[i][0]) where sums[i][0] is not zero).
+   cell_weights is [num_cells]; everything else, the step cap and the errors are pmc_integrate_rays's; pmc_last_integrate_work reports this
+   call too.  The device keeps the weight and PMC_INTEGRATE_PASS_VALUES - 1 values per pass. */
+int pmc_integrate_weighted_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, const double* directions, int32_t num_values,
+                                const double* cell_weights, const double* cell_values, double* sums);
+
+/* ---------------------------------------------------------------- dust temperatures ---- */
+
+/* The energy balance of the dust per cell from the stored radiation field (EquilibriumDustEmissionCalculator::equilibriumTemperature,
+   MediumSystem::indicativeTemperature, MediumSystem.cpp:1370-1427).  For cell m and dust component h with mass_density[h][m] > 0:
+       J[ell]  = rf[m * num_lambda + ell] * cell_factor[m] / width[ell]
+       input   = sum over ell of sigma[h][ell] * J[ell] * width[ell], added from the LAST bin down to the first (the order in which the
+                 reference's valarray expression is summed)
+       T[h][m] = 0 if input <= 0, else the temperature at which planckabs[h] equals input: linear interpolation in (planckabs[h], temperature),
+                 clamped to the ends of the table
+   and T[h][m] = 0 where the component has no mass.  Row num_components is the mass-weighted mean over the components with mass, 0 where
+   none has.  All host pointers; the tables are a few KB per component and are kept in LDS by the kernel. */
+typedef struct pmc_dust_heating
+{
+    int32_t num_components;      /* H: dust components, 1 .. PMC_MAX_MEDIA */
+    int32_t num_lambda;          /* bins of the radiation field wavelength grid */
+    int32_t num_temperatures;    /* points of the temperature grid (the reference: 1001) */
+    int32_t num_cells;
+    const double* width;         /* [num_lambda] effective bin widths */
+    const double* sigma;         /* [H][num_lambda] absorption cross sections on the radiation field grid */
+    const double* planckabs;     /* [H][num_temperatures] Planck-integrated absorption, ascending */
+    const double* temperature;   /* [num_temperatures] ascending */
+    const double* cell_factor;   /* [num_cells] 1 / (4 pi V) */
+    const double* mass_density;  /* [H][num_cells] */
+} pmc_dust_heating;
+/* out: [num_components + 1][num_cells], from the context's radiation field table (its own or the bound one) as it stands, in the cell
+   numbering of pmc_download_radiation_field.  PMC_ERR_INVALID: the scene stores no field, or sizes that do not match it;
+   PMC_ERR_UNSUPPORTED: more than PMC_MAX_MEDIA components, or tables too large for the LDS of a workgroup */
+int pmc_dust_temperatures(pmc_ctx* ctx, const pmc_dust_heating* tables, double* out);
+/* milliseconds in the kernel of the most recent pmc_dust_temperatures on this context (HIP events) */
+int pmc_last_temperature_ms(pmc_ctx* ctx, float* kernel_ms);
 /* number of photon histories kept in flight on the device (default 24 Mi, fewer where the device memory is short; environment PMC_NUM_SLOTS).  The slots are
    divided into slot groups (default 3; environment PMC_NUM_GROUPS) whose generations run on separate streams */
 int pmc_set_num_slots(pmc_ctx* ctx, int64_t num_slots);

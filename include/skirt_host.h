@@ -72,6 +72,9 @@ typedef struct
 /* projected maps, in file order (valid after skh_setup; 0 for a simulation without a medium) */
 int32_t skh_num_probe_maps(const skh_simulation* sim);
 int skh_probe_map_info(const skh_simulation* sim, int32_t map, skh_probe_map* out);
+/* 1: the map is a weighted average along its rays (a TemperatureProbe's: skh_probe_map_values then gives the weights [num_cells], num_values
+   is 1), 0: a line integral, negative: error.  (A function of its own: skh_probe_map keeps its layout.) */
+int32_t skh_probe_map_averaged(const skh_simulation* sim, int32_t map);
 /* the rays [num_rays][3] of a map, ordered by pixel (j, i) and sub-sample (is, js), and its cell values [num_values][num_cells] in
    internal units (the unit factor of the projected quantity is applied to the integrals) */
 int skh_probe_map_rays(const skh_simulation* sim, int32_t map, double* origins, double* directions);
@@ -80,6 +83,38 @@ int skh_probe_map_values(const skh_simulation* sim, int32_t map, double* cell_va
    has no projected map.  skh_write_probes_when: only the probes with probeAfter Setup (when = 0) or Run (when = 1); -1: all */
 int skh_write_probes(const skh_simulation* sim, skh_integrate_fn integrate, void* user, const char* outdir);
 int skh_write_probes_when(const skh_simulation* sim, skh_integrate_fn integrate, void* user, const char* outdir, int32_t when);
+
+/* Dust temperatures from the stored radiation field (TemperatureProbe; EquilibriumDustEmissionCalculator::equilibriumTemperature), for a
+   panchromatic simulation that stores the field and has dust.  skh_dust_heating: the tables of pmc_dust_heating (include/pmc.h), owned by the
+   simulation, built at the first call.  skh_dust_temperatures: the CPU restatement of pmc_dust_temperatures from a host copy of the table
+   rf[m * nbins + ell]: out[H + 1][num_cells], the dust components in order, then their mass-weighted mean; skh_dust_temperatures_from: the same
+   for any tables.  The engine's result equals these bit for bit. */
+int skh_dust_heating(const skh_simulation* sim, pmc_dust_heating* out);
+int skh_dust_temperatures(const skh_simulation* sim, const double* rf, double* out);
+int skh_dust_temperatures_from(const pmc_dust_heating* tables, const double* rf, double* out);
+/* the medium components that are dust (the rows of the tables), up to PMC_MAX_MEDIA indices; returns their number (0 without dust heating) */
+int32_t skh_dust_components(const skh_simulation* sim, int32_t* components);
+
+/* The probes that need the radiation field -- TemperatureProbe (per cell and projected: a density-weighted average along the rays) and
+   DustAbsorptionPerCellProbe -- are written by skh_write_probes_with: next to the integrator it takes libpmc.so's
+   pmc_integrate_weighted_rays and pmc_dust_temperatures (user = the pmc_ctx, as for the integrator) and a host copy of the table.  With
+   temperatures == NULL the host computes the temperatures from rf; rf is needed by DustAbsorptionPerCellProbe in any case.  Members that
+   the ski file's probes do not need may be NULL. */
+typedef int (*skh_integrate_weighted_fn)(void* user, int64_t num_rays, const double* origins, const double* directions, int32_t num_values,
+                                         const double* cell_weights, const double* cell_values, double* sums);
+typedef int (*skh_temperature_fn)(void* user, const pmc_dust_heating* tables, double* out);
+typedef struct
+{
+    skh_integrate_fn integrate;
+    skh_integrate_weighted_fn integrate_weighted;
+    skh_temperature_fn temperatures;
+    void* user;
+    const double* rf;
+} skh_probe_engine;
+int skh_write_probes_with(const skh_simulation* sim, const skh_probe_engine* engine, const char* outdir, int32_t when);
+/* 1 if a probe written with `when` (0 Setup, 1 Run, -1 all) reads the radiation field table (TemperatureProbe, DustAbsorptionPerCellProbe), else 0:
+   a caller that keeps the table on the device copies it to the host only then */
+int32_t skh_probes_need_radiation_field(const skh_simulation* sim, int32_t when);
 
 /* A set-up scene as ONE file: everything pmc_create reads plus the numbers a driver of the photon loop needs.  In a job of
    one process per GPU, one process sets the simulation up (all host cores) and saves it, the others load it instead of

@@ -923,18 +923,22 @@ int pmc_trace_ray(pmc_ctx* ctx, const double r[3], const double k[3], int32_t* m
     return rc;
 }
 
-int pmc_integrate_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, const double* directions, int32_t num_values, const double* cell_values,
-                       double* sums)
+}  // extern "C"
+
+// pmc_integrate_rays (cell_weights == nullptr: sums [num_rays][num_values]) and pmc_integrate_weighted_rays (sums [num_rays][1 + num_values]: a pass
+// carries the weight and PMC_INTEGRATE_PASS_VALUES - 1 values; the sum of the weights is the same in every pass and is taken from the first)
+static int integrateRays(pmc_ctx* ctx, const std::string& name, int64_t num_rays, const double* origins, const double* directions, int32_t num_values,
+                         const double* cell_weights, const double* cell_values, double* sums)
 {
-    if (!ctx) return fail(PMC_ERR_INVALID, "null context");
-    if (num_rays < 0) return fail(PMC_ERR_INVALID, "pmc_integrate_rays: negative number of rays");
-    if (num_values < 0) return fail(PMC_ERR_INVALID, "pmc_integrate_rays: negative number of values");
-    if (num_rays > 0 && (!origins || !directions)) return fail(PMC_ERR_INVALID, "pmc_integrate_rays: null ray arrays");
-    if (num_values > 0 && !cell_values) return fail(PMC_ERR_INVALID, "pmc_integrate_rays: null cell values");
-    if (num_rays > 0 && num_values > 0 && !sums) return fail(PMC_ERR_INVALID, "pmc_integrate_rays: null result array");
+    const bool weighted = cell_weights != nullptr;
+    if (num_rays < 0) return fail(PMC_ERR_INVALID, name + ": negative number of rays");
+    if (num_values < 0) return fail(PMC_ERR_INVALID, name + ": negative number of values");
+    if (num_rays > 0 && (!origins || !directions)) return fail(PMC_ERR_INVALID, name + ": null ray arrays");
+    if (num_values > 0 && !cell_values) return fail(PMC_ERR_INVALID, name + ": null cell values");
+    if (num_rays > 0 && (num_values > 0 || weighted) && !sums) return fail(PMC_ERR_INVALID, name + ": null result array");
     ctx->integrateMs = 0.f;
     ctx->integrateLaneSteps = ctx->integrateWaveSteps = 0;
-    if (num_rays == 0 || num_values == 0) return PMC_OK;
+    if (num_rays == 0 || (num_values == 0 && !weighted)) return PMC_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (ctx->sceneDirty)
@@ -954,7 +958,7 @@ int pmc_integrate_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, co
         ext.resize(slots);
         HIP_TRY(hipMemcpy(ext.data(), D.cell_ext, slots * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (int32_t m : ext)
-            if (m >= D.num_cells) return fail(PMC_ERR_DEVICE, "pmc_integrate_rays: cell numbering table out of range");
+            if (m >= D.num_cells) return fail(PMC_ERR_DEVICE, name + ": cell numbering table out of range");
     }
     const int64_t batchMax = int64_t(1) << 22;  // rays per launch (device memory: 10 doubles per ray)
     const size_t batchRoom = size_t(std::min(num_rays, batchMax));
@@ -978,7 +982,10 @@ int pmc_integrate_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, co
     std::vector<unsigned long long> work(workWords);
     unsigned long long capped = 0;
     hipError_t e = hipSuccess;
-    const int numPasses = (num_values + W - 1) / W;
+    const int perPass = weighted ? W - 1 : W;            // caller's values per pass
+    const int lead = weighted ? 1 : 0;                   // members of a record (and of a ray's sums) in front of them
+    const size_t stride = size_t(lead + num_values);     // the caller's sums per ray
+    const int numPasses = std::max((num_values + perPass - 1) / perPass, 1);
     for (int64_t first = 0; first < num_rays && e == hipSuccess; first += batchMax)
     {
         const size_t n = size_t(std::min(batchMax, num_rays - first));
@@ -988,17 +995,18 @@ int pmc_integrate_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, co
         const int grid = int(std::max<size_t>(1, std::min<size_t>((n + 255) / 256, size_t(ctx->numCU) * 4)));
         for (int pass = 0; pass < numPasses && e == hipSuccess; ++pass)
         {
-            const int v0 = pass * W, nv = std::min(W, num_values - v0);
+            const int v0 = pass * perPass, nv = std::min(perPass, num_values - v0);
             for (size_t c = 0; c < slots; ++c)
             {
                 const int64_t m = renumbered ? int64_t(ext[c]) : int64_t(c);
-                for (int j = 0; j < W; ++j) q[c * W + j] = (j < nv && m >= 0) ? cell_values[size_t(v0 + j) * numCells + size_t(m)] : 0.;
+                if (weighted) q[c * W] = m >= 0 ? cell_weights[size_t(m)] : 0.;
+                for (int j = 0; j < perPass; ++j) q[c * W + lead + j] = (j < nv && m >= 0) ? cell_values[size_t(v0 + j) * numCells + size_t(m)] : 0.;
             }
             e = hipMemcpy(dQ, q.data(), q.size() * sizeof(double), hipMemcpyHostToDevice);
             if (e == hipSuccess) e = hipMemsetAsync(dWork, 0, workWords * sizeof(unsigned long long), ctx->stream);
             if (e == hipSuccess) e = hipEventRecord(evA, ctx->stream);
             if (e == hipSuccess)
-                e = pmcLaunchIntegrate(ctx->slot, D.grid_kind, ctx->wide, dOrigins, dDirections, dQ, dSums, n, dWork, grid, ctx->walkLds, ctx->stream);
+                e = pmcLaunchIntegrate(ctx->slot, D.grid_kind, ctx->wide, weighted ? 1 : 0, dOrigins, dDirections, dQ, dSums, n, dWork, grid, ctx->walkLds, ctx->stream);
             if (e == hipSuccess) e = hipEventRecord(evB, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
             if (e == hipSuccess) e = hipMemcpy(part.data(), dSums, W * n * sizeof(double), hipMemcpyDeviceToHost);
@@ -1010,15 +1018,35 @@ int pmc_integrate_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, co
             ctx->integrateLaneSteps += work[2];
             ctx->integrateWaveSteps += work[3];
             for (size_t i = 0; i < n; ++i)
-                for (int j = 0; j < nv; ++j) sums[(size_t(first) + i) * size_t(num_values) + size_t(v0 + j)] = part[i * W + j];
+            {
+                if (weighted && pass == 0) sums[(size_t(first) + i) * stride] = part[i * W];
+                for (int j = 0; j < nv; ++j) sums[(size_t(first) + i) * stride + size_t(lead + v0 + j)] = part[i * W + lead + j];
+            }
         }
     }
     hipEventDestroy(evA);
     hipEventDestroy(evB);
-    if (e != hipSuccess) return hipFail(e, "pmc_integrate_rays");
+    if (e != hipSuccess) return hipFail(e, name.c_str());
     if (capped)
-        return fail(PMC_ERR_DEVICE, "pmc_integrate_rays: " + std::to_string(capped) + " ray walk(s) were still inside the grid after " PMC_STRINGIFY(PMC_RAY_STEP_CAP) " cells (traversal error)");
+        return fail(PMC_ERR_DEVICE, name + ": " + std::to_string(capped) + " ray walk(s) were still inside the grid after " PMC_STRINGIFY(PMC_RAY_STEP_CAP) " cells (traversal error)");
     return PMC_OK;
+}
+
+extern "C" {
+
+int pmc_integrate_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, const double* directions, int32_t num_values, const double* cell_values,
+                       double* sums)
+{
+    if (!ctx) return fail(PMC_ERR_INVALID, "null context");
+    return integrateRays(ctx, "pmc_integrate_rays", num_rays, origins, directions, num_values, nullptr, cell_values, sums);
+}
+
+int pmc_integrate_weighted_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, const double* directions, int32_t num_values,
+                                const double* cell_weights, const double* cell_values, double* sums)
+{
+    if (!ctx) return fail(PMC_ERR_INVALID, "null context");
+    if (!cell_weights) return fail(PMC_ERR_INVALID, "pmc_integrate_weighted_rays: null cell weights");
+    return integrateRays(ctx, "pmc_integrate_weighted_rays", num_rays, origins, directions, num_values, cell_weights, cell_values, sums);
 }
 
 int pmc_last_integrate_work(pmc_ctx* ctx, float* kernel_ms, uint64_t* lane_steps, uint64_t* wave_steps)

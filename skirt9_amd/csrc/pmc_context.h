@@ -1,7 +1,7 @@
 // pmc_context.h -- what the translation units of the host side of libpmc.so share: the context behind a pmc_ctx handle, the error text of the
 // calling thread, the launchers of pmc_kernels.hip.  pmc_api.hip holds the ABI entry points (scene upload: pmc_create), pmc_tables.hip the
 // table builders (octree flattening, Voronoi run / cone / observer tables), pmc_run.hip the generation loop (pmc_run_primary), pmc_comm.hip the
-// RCCL calls, pmc_tuning.hip the switch table of include/pmc_tuning.h.
+// RCCL calls, pmc_tuning.hip the switch table of include/pmc_tuning.h, pmc_temperature.hip the dust temperatures (kernel and entry point).
 #ifndef PMC_CONTEXT_H
 #define PMC_CONTEXT_H
 
@@ -69,8 +69,8 @@ extern "C" hipError_t pmcLaunchTrace(int slot, int gridKind, int wide, int unifo
                                      const double* kdev, int32_t* m, double* ds, int32_t cap, int32_t* n, size_t ldsBytes,
                                      hipStream_t stream);
 extern "C" int pmcProbeWorkWords(void);
-extern "C" hipError_t pmcLaunchIntegrate(int slot, int gridKind, int wide, const double* origins, const double* directions, const double* q, double* sums,
-                                         unsigned long long numRays, unsigned long long* work, int grid, size_t ldsBytes, hipStream_t stream);
+extern "C" hipError_t pmcLaunchIntegrate(int slot, int gridKind, int wide, int averaged, const double* origins, const double* directions, const double* q,
+                                         double* sums, unsigned long long numRays, unsigned long long* work, int grid, size_t ldsBytes, hipStream_t stream);
 
 // error text of the calling thread (pmc_last_error); defined in pmc_api.hip
 void pmcSetError(const std::string& message);
@@ -124,6 +124,7 @@ struct pmc_ctx
     // work of the most recent pmc_integrate_rays (pmc_last_integrate_work)
     float integrateMs{0};
     unsigned long long integrateLaneSteps{0}, integrateWaveSteps{0};
+    float temperatureMs{0};  // kernel of the most recent pmc_dust_temperatures (pmc_last_temperature_ms)
     DevScene dev{};
     std::vector<void*> allocations;
     std::vector<void*> slotAllocations;

@@ -354,7 +354,12 @@ static int rayKernelIndex(int gridKind, int wide)
 typedef void (*IntegrateKernel)(int, ProbeArgs);
 static const auto integrateKernels = flavourTable<5>([](auto f) {
     constexpr int F = decltype(f)::value;
-    return KernelFlavour<IntegrateKernel>{integrateRaysKernel<RAY_GRIDS[F], F == 1>, 0};
+    return KernelFlavour<IntegrateKernel>{integrateRaysKernel<RAY_GRIDS[F], F == 1, false>, 0};
+});
+// ... and the weighted averages (pmc_integrate_weighted_rays)
+static const auto integrateWeightedKernels = flavourTable<5>([](auto f) {
+    constexpr int F = decltype(f)::value;
+    return KernelFlavour<IntegrateKernel>{integrateRaysKernel<RAY_GRIDS[F], F == 1, true>, 0};
 });
 // single-ray tracer: the five with the direction in scalar registers, then the octree's two with the direction in vector registers
 typedef void (*TraceKernel)(int, double, double, double, double, double, double, const double*, int32_t*, double*, int32_t, int32_t*);
@@ -400,7 +405,7 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
     }
     for (hipError_t e : {raiseLdsLimits(peelKernels, walkMax), raiseLdsLimits(peel2Kernels, walkMax), raiseLdsLimits(propKernels, walkMax),
                          raiseLdsLimits(walkKernels, walkMax), raiseLdsLimits(binWalkKernels, walkMax), raiseLdsLimits(traceKernels, walkMax),
-                         raiseLdsLimits(integrateKernels, walkMax)})
+                         raiseLdsLimits(integrateKernels, walkMax), raiseLdsLimits(integrateWeightedKernels, walkMax)})
         if (e != hipSuccess) return e;
     const struct
     {
@@ -737,11 +742,12 @@ extern "C" hipError_t pmcLaunchTrace(int slot, int gridKind, int wide, int unifo
 // batched ray integrals (pmc_ray.inc): one pass of PMC_INTEGRATE_PASS_VALUES values over numRays rays; `work` = the kernel's cursor and counters,
 // zeroed by the caller (pmcProbeWorkWords words)
 extern "C" int pmcProbeWorkWords(void) { return PROBE_WORK_WORDS; }
-extern "C" hipError_t pmcLaunchIntegrate(int slot, int gridKind, int wide, const double* origins, const double* directions, const double* q, double* sums,
-                                         unsigned long long numRays, unsigned long long* work, int grid, size_t ldsBytes, hipStream_t stream)
+// (averaged: the records are (w, v0, v1, v2) and the sums the raw (sum of weights, weighted sums) of pmc_integrate_weighted_rays)
+extern "C" hipError_t pmcLaunchIntegrate(int slot, int gridKind, int wide, int averaged, const double* origins, const double* directions, const double* q,
+                                         double* sums, unsigned long long numRays, unsigned long long* work, int grid, size_t ldsBytes, hipStream_t stream)
 {
     const ProbeArgs A = {origins, directions, q, sums, numRays, work};
-    const IntegrateKernel kernel = integrateKernels[rayKernelIndex(gridKind, wide)].kernel;
+    const IntegrateKernel kernel = (averaged ? integrateWeightedKernels : integrateKernels)[rayKernelIndex(gridKind, wide)].kernel;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), ldsBytes, stream, slot, A);
     return hipGetLastError();
 }

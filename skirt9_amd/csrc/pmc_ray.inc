@@ -164,6 +164,9 @@
     //  q is laid out for the step's gather: per pass of PMC_INTEGRATE_PASS_VALUES values one record [cell][PMC_INTEGRATE_PASS_VALUES] in the
     //  numbering the kernel walks in (octree, binary tree: device cells), rows beyond the caller's last value zero.  The sums of a pass are
     //  kept in registers.
+    //
+    //  AVERAGED (pmc_integrate_weighted_rays, ProbeFormBridge.cpp:652-676): the cell record of a pass is (w, v0, v1, v2); a step adds
+    //  weight = ds * w to sum[0] and weight * v to the sums behind it, and the raw sums go back: the caller divides.
     // ================================================================================================
     constexpr int PROBE_WIDTH = PMC_INTEGRATE_PASS_VALUES;
     constexpr unsigned long long PROBE_CHUNK = 64;  // rays a wave takes from the cursor at a time
@@ -212,7 +215,7 @@
         return rank < avail ? base + rank : none;
     }
 
-    template<int GRID, bool WIDE> __global__ __launch_bounds__(256) void integrateRaysKernel(const int sceneSlot, const ProbeArgs A)
+    template<int GRID, bool WIDE, bool AVERAGED> __global__ __launch_bounds__(256) void integrateRaysKernel(const int sceneSlot, const ProbeArgs A)
     {
         const DevScene& S = c_scene[sceneSlot];
         extern __shared__ double lds[];
@@ -266,8 +269,18 @@
                 // the pending segment (m, ds): every cell of these grids has m >= 0
                 const double ds = p.w.ds;
                 const double* q = A.q + (size_t)(uint32_t)p.w.cell * PROBE_WIDTH;
+                if constexpr (AVERAGED)
+                {
+                    const double weight = ds * q[0];
+                    sum[0] += weight;
 #pragma unroll
-                for (int v = 0; v < PROBE_WIDTH; ++v) sum[v] += ds * q[v];
+                    for (int v = 1; v < PROBE_WIDTH; ++v) sum[v] += weight * q[v];
+                }
+                else
+                {
+#pragma unroll
+                    for (int v = 0; v < PROBE_WIDTH; ++v) sum[v] += ds * q[v];
+                }
                 bool inside = rayAdvance<GRID, WIDE, -1>(S, L, C, nodes, p);
                 if (inside && ++guard >= PMC_RAY_STEP_CAP)
                 {

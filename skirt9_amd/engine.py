@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .host import CounterValues, FrameLayout, SceneExt, SceneHead
+from .host import CounterValues, DustHeating, FrameLayout, SceneExt, SceneHead, heating_struct
 
 _LIBDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 
@@ -18,7 +18,7 @@ _LIBDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 SYMBOLS = ["pmc_abi_version", "pmc_build_info", "pmc_last_error", "pmc_frame_layout_of", "pmc_create", "pmc_create_ext", "pmc_destroy", "pmc_bind_frames",
            "pmc_clear_frames", "pmc_run_primary", "pmc_set_progress", "pmc_sync", "pmc_download", "pmc_frames_device", "pmc_frames_size",
            "pmc_last_kernel_ms", "pmc_counters", "pmc_reset_counters", "pmc_trace_ray", "pmc_integrate_rays",
-           "pmc_last_integrate_work", "pmc_set_launch",
+           "pmc_last_integrate_work", "pmc_integrate_weighted_rays", "pmc_dust_temperatures", "pmc_last_temperature_ms", "pmc_set_launch",
            "pmc_set_num_slots", "pmc_last_timing", "pmc_last_walk_timing", "pmc_walk_work", "pmc_radiation_field_size", "pmc_radiation_field_device",
            "pmc_download_radiation_field", "pmc_clear_radiation_field", "pmc_bind_radiation_field", "pmc_sampler_create",
            "pmc_sampler_density", "pmc_sampler_destroy", "pmc_history_range", "pmc_comm_init_all", "pmc_comm_unique_id",
@@ -75,6 +75,10 @@ def lib():
         if hasattr(L, "pmc_integrate_rays"):  # (absent from engines built from an older commit and loaded through PMC_LIBRARY)
             L.pmc_integrate_rays.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
             L.pmc_last_integrate_work.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        if hasattr(L, "pmc_dust_temperatures"):  # (likewise)
+            L.pmc_integrate_weighted_rays.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.pmc_dust_temperatures.argtypes = [C.c_void_p, C.POINTER(DustHeating), C.c_void_p]
+            L.pmc_last_temperature_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.pmc_set_launch.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.pmc_set_num_slots.argtypes = [C.c_void_p, C.c_int64]
         L.pmc_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -386,8 +390,56 @@ class Engine:
         """``integrate_rays`` as the C callback of skh_write_probes (include/skirt_host.h skh_integrate_fn): (function address, user pointer)"""
         return C.cast(lib().pmc_integrate_rays, C.c_void_p).value, self._h
 
+    def integrate_weighted_rays(self, origins, directions, cell_weights, cell_values):
+        """the raw sums of a weighted average along rays (pmc_integrate_weighted_rays): per segment weight = ds * cell_weights[m];
+        sums[i, 0] += weight; sums[i, 1 + v] += weight * cell_values[v, m].  cell_weights: [num_cells]; cell_values: [V][num_cells] (V may
+        be 0) or [num_cells]; returns [n][1 + V].  The average of value v along ray i is sums[i, 1 + v] / sums[i, 0] where that is not zero"""
+        r = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        k = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        if r.shape != k.shape:
+            raise ValueError("origins and directions differ in shape")
+        w = np.ascontiguousarray(cell_weights, dtype=np.float64).reshape(-1)
+        q = np.ascontiguousarray(cell_values, dtype=np.float64)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        if q.ndim != 2:
+            raise ValueError("cell_values must be [V][num_cells]")
+        if w.size != self.num_cells or (q.shape[0] and q.shape[1] != self.num_cells):
+            raise ValueError(f"cell_weights and cell_values must have {self.num_cells} cells")
+        out = np.zeros((r.shape[0], 1 + q.shape[0]), dtype=np.float64)
+        _check(lib().pmc_integrate_weighted_rays(self._h, r.shape[0], r.ctypes.data_as(C.c_void_p), k.ctypes.data_as(C.c_void_p), q.shape[0],
+                                                 w.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def weighted_callback(self):
+        """``integrate_weighted_rays`` as the C callback of skh_write_probes_with (skh_integrate_weighted_fn): (function address, user pointer)"""
+        if not hasattr(lib(), "pmc_integrate_weighted_rays"):  # (an engine built from an older commit and loaded through PMC_LIBRARY)
+            return None, self._h
+        return C.cast(lib().pmc_integrate_weighted_rays, C.c_void_p).value, self._h
+
+    def dust_temperatures(self, tables):
+        """[H + 1][num_cells]: the equilibrium temperature of every dust component in every cell and their mass-weighted mean
+        (pmc_dust_temperatures), from the radiation field table of this context as it stands on the device -- its own or the bound one.
+        tables: ``Simulation.temperature_tables()``, or any dict of that form"""
+        struct, keep = heating_struct(tables)
+        out = np.empty((struct.num_components + 1, struct.num_cells), dtype=np.float64)
+        _check(lib().pmc_dust_temperatures(self._h, C.byref(struct), out.ctypes.data_as(C.c_void_p)))
+        del keep
+        return out
+
+    def temperature_callback(self):
+        """``dust_temperatures`` as the C callback of skh_write_probes_with (skh_temperature_fn): (function address, user pointer)"""
+        if not hasattr(lib(), "pmc_dust_temperatures"):  # (likewise)
+            return None, self._h
+        return C.cast(lib().pmc_dust_temperatures, C.c_void_p).value, self._h
+
+    def last_temperature_ms(self):
+        """milliseconds in the kernel of the most recent dust_temperatures (HIP events)"""
+        ms = C.c_float(0)
+        _check(lib().pmc_last_temperature_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def last_integrate_work(self):
-        """the most recent integrate_rays: dict(kernel_ms, lane_steps, wave_steps); lanes in use = lane_steps / (64 wave_steps)"""
+        """the most recent integrate_rays or integrate_weighted_rays: dict(kernel_ms, lane_steps, wave_steps); lanes in use = lane_steps / (64 wave_steps)"""
         ms, a, b = C.c_float(0), C.c_uint64(0), C.c_uint64(0)
         _check(lib().pmc_last_integrate_work(self._h, C.byref(ms), C.byref(a), C.byref(b)))
         return {"kernel_ms": float(ms.value), "lane_steps": int(a.value), "wave_steps": int(b.value)}

@@ -95,6 +95,69 @@ INTEGRATE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_double)
                            C.POINTER(C.c_double))
 
 
+# skh_integrate_weighted_fn and skh_temperature_fn (include/skirt_host.h)
+INTEGRATE_WEIGHTED_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), C.POINTER(C.c_double))
+TEMPERATURE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double))
+
+
+class DustHeating(C.Structure):
+    """pmc_dust_heating (include/pmc.h)"""
+    _fields_ = [("num_components", C.c_int32), ("num_lambda", C.c_int32), ("num_temperatures", C.c_int32), ("num_cells", C.c_int32),
+                ("width", C.POINTER(C.c_double)), ("sigma", C.POINTER(C.c_double)), ("planckabs", C.POINTER(C.c_double)),
+                ("temperature", C.POINTER(C.c_double)), ("cell_factor", C.POINTER(C.c_double)), ("mass_density", C.POINTER(C.c_double))]
+
+
+class ProbeEngine(C.Structure):
+    """skh_probe_engine (include/skirt_host.h)"""
+    _fields_ = [("integrate", C.c_void_p), ("integrate_weighted", C.c_void_p), ("temperatures", C.c_void_p), ("user", C.c_void_p),
+                ("rf", C.c_void_p)]
+
+
+HEATING_ARRAYS = ("width", "sigma", "planckabs", "temperature", "cell_factor", "mass_density")
+
+
+def heating_tables_from(struct):
+    """a pmc_dust_heating as a dict of numpy arrays (copies): width [L], sigma [H][L], planckabs [H][NT], temperature [NT], cell_factor [cells],
+    mass_density [H][cells]"""
+    import numpy as np
+    H, L, NT, cells = struct.num_components, struct.num_lambda, struct.num_temperatures, struct.num_cells
+    shapes = {"width": (L,), "sigma": (H, L), "planckabs": (H, NT), "temperature": (NT,), "cell_factor": (cells,), "mass_density": (H, cells)}
+    return {name: np.ctypeslib.as_array(getattr(struct, name), shape=shapes[name]).copy() for name in HEATING_ARRAYS}
+
+
+def heating_struct(tables):
+    """the pmc_dust_heating of a dict as ``Simulation.temperature_tables`` returns it (sizes from the shapes of the arrays); returns
+    (struct, arrays): the struct points into the arrays, which the caller keeps alive while it is in use"""
+    import numpy as np
+    arrays = {name: np.ascontiguousarray(tables[name], dtype=np.float64) for name in HEATING_ARRAYS}
+    sigma, planck, rho = arrays["sigma"], arrays["planckabs"], arrays["mass_density"]
+    if sigma.ndim != 2 or planck.ndim != 2 or rho.ndim != 2 or not (sigma.shape[0] == planck.shape[0] == rho.shape[0]):
+        raise ValueError("sigma, planckabs and mass_density must be [H][...] for the same H")
+    if (arrays["width"].shape != (sigma.shape[1],) or arrays["temperature"].shape != (planck.shape[1],)
+            or arrays["cell_factor"].shape != (rho.shape[1],)):
+        raise ValueError("width, temperature and cell_factor do not match sigma, planckabs and mass_density")
+    struct = DustHeating(sigma.shape[0], sigma.shape[1], planck.shape[1], rho.shape[1])
+    for name in HEATING_ARRAYS:
+        setattr(struct, name, arrays[name].ctypes.data_as(C.POINTER(C.c_double)))
+    return struct, arrays
+
+
+def dust_temperatures(tables, rf):
+    """the CPU restatement of the engine's dust temperature kernel for any tables (skh_dust_temperatures_from): [H + 1][num_cells] from
+    rf[m * L + ell]"""
+    import numpy as np
+    struct, keep = heating_struct(tables)
+    data = np.ascontiguousarray(rf, dtype=np.float64).reshape(-1)
+    if data.size != struct.num_cells * struct.num_lambda:
+        raise ValueError("the radiation field table does not match the tables")
+    out = np.empty((struct.num_components + 1, struct.num_cells), dtype=np.float64)
+    if lib().skh_dust_temperatures_from(C.byref(struct), data.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0:
+        raise RuntimeError(lib().skh_last_error().decode())
+    del keep
+    return out
+
+
 def scene_head(sim):
     """the leading members (grid, medium) of the pmc_scene of a set-up Simulation, for inspection"""
     return SceneHead.from_address(sim.scene)
@@ -142,6 +205,16 @@ def lib():
         L.skh_probe_map_values.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.skh_write_probes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
         L.skh_write_probes_when.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32]
+        L.skh_probe_map_averaged.restype = C.c_int32
+        L.skh_probe_map_averaged.argtypes = [C.c_void_p, C.c_int32]
+        L.skh_probes_need_radiation_field.restype = C.c_int32
+        L.skh_probes_need_radiation_field.argtypes = [C.c_void_p, C.c_int32]
+        L.skh_write_probes_with.argtypes = [C.c_void_p, C.POINTER(ProbeEngine), C.c_char_p, C.c_int32]
+        L.skh_dust_heating.argtypes = [C.c_void_p, C.POINTER(DustHeating)]
+        L.skh_dust_components.restype = C.c_int32
+        L.skh_dust_components.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.skh_dust_temperatures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.skh_dust_temperatures_from.argtypes = [C.POINTER(DustHeating), C.c_void_p, C.c_void_p]
         L.skh_scene_save.argtypes = [C.c_void_p, C.c_char_p]
         L.skh_scene_load.restype = C.c_void_p
         L.skh_scene_load.argtypes = [C.c_char_p]
@@ -263,9 +336,10 @@ class Simulation:
             raise RuntimeError(lib().skh_last_error().decode())
 
     def probe_maps(self):
-        """the projected maps (DensityProbe / OpacityProbe with a ParallelProjectionForm) in file order, one dict each: file_name, nx, ny,
-        sampling, num_values, num_rays, after_setup, and the arrays origins [num_rays][3], directions [num_rays][3] (ordered by pixel
-        (j, i) and sub-sample (is, js)) and cell_values [num_values][num_cells] (internal units)"""
+        """the projected maps (DensityProbe / OpacityProbe / TemperatureProbe with a ParallelProjectionForm) in file order, one dict each:
+        file_name, nx, ny, sampling, num_values, num_rays, after_setup, averaged, and the arrays origins [num_rays][3], directions
+        [num_rays][3] (ordered by pixel (j, i) and sub-sample (is, js)) and cell_values [num_values][num_cells] (internal units; of an
+        averaged map -- a TemperatureProbe's -- the weights of the cells)"""
         import numpy as np
         assert self._setup, "call setup() first"
         L = lib()
@@ -283,26 +357,71 @@ class Simulation:
                 raise RuntimeError(L.skh_last_error().decode())
             maps.append({"file_name": info.file_name.decode(), "nx": int(info.nx), "ny": int(info.ny), "sampling": int(info.sampling),
                          "num_values": int(info.num_values), "num_rays": int(info.num_rays), "after_setup": bool(info.after_setup),
-                         "origins": origins, "directions": directions, "cell_values": values})
+                         "averaged": L.skh_probe_map_averaged(self._h, index) == 1, "origins": origins, "directions": directions, "cell_values": values})
         return maps
 
-    def write_probes(self, outdir, integrator=None, when=None):
-        """write the DensityProbe / OpacityProbe files into outdir.  integrator: an ``Engine`` (its pmc_integrate_rays is handed to the host
-        library as a C function: the rays never pass through Python), or a callable (origins [n][3], directions [n][3], cell_values
-        [V][num_cells]) -> sums [n][V]; None serves a ski file without projected maps.  when: "Setup" or "Run" for the probes with that
-        probeAfter only, None for all"""
+    def dust_components(self):
+        """the medium components that are dust, in order: the rows of ``temperature_tables`` and ``dust_temperatures`` (empty unless the
+        simulation is panchromatic, stores the radiation field and has dust)"""
+        assert self._setup, "call setup() first"
+        out = (C.c_int32 * 16)()
+        n = lib().skh_dust_components(self._h, out)
+        if n < 0:
+            raise RuntimeError(lib().skh_last_error().decode())
+        return [int(out[i]) for i in range(n)]
+
+    def _heating(self):
+        assert self._setup, "call setup() first"
+        struct = DustHeating()
+        if lib().skh_dust_heating(self._h, C.byref(struct)) != 0:
+            raise RuntimeError(lib().skh_last_error().decode())
+        return struct
+
+    def temperature_tables(self):
+        """the tables of the energy balance per dust component (pmc_dust_heating, include/pmc.h) as a dict of numpy arrays: what
+        ``Engine.dust_temperatures`` takes.  Built at the first call (a thousand Planck integrals per component)"""
+        return heating_tables_from(self._heating())
+
+    def dust_temperatures(self, rf):
+        """[H + 1][num_cells]: the equilibrium temperature of every dust component in every cell, then their mass-weighted mean, from the
+        table rf[m * nbins + ell] -- the CPU restatement (skh_dust_temperatures) of the engine's kernel, equal to it bit for bit"""
+        import numpy as np
+        struct = self._heating()
+        data = np.ascontiguousarray(rf, dtype=np.float64).reshape(-1)
+        assert data.size == self.radiation_field_size
+        out = np.empty((struct.num_components + 1, struct.num_cells), dtype=np.float64)
+        if lib().skh_dust_temperatures(self._h, data.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError(lib().skh_last_error().decode())
+        return out
+
+    def write_probes(self, outdir, integrator=None, when=None, weighted=None, temperatures=None, rf=None):
+        """write the probe files into outdir.  integrator: an ``Engine`` (its pmc_integrate_rays, pmc_integrate_weighted_rays and
+        pmc_dust_temperatures are handed to the host library as C functions: rays and tables never pass through Python; only when a
+        TemperatureProbe or DustAbsorptionPerCellProbe is among the probes written is the radiation field table downloaded from it, unless rf
+        is given), or a callable (origins [n][3], directions [n][3],
+        cell_values [V][num_cells]) -> sums [n][V]; None serves a ski file without projected maps.  With a callable, the TemperatureProbe
+        maps need `weighted`, a callable (origins, directions, cell_weights [num_cells], cell_values [V][num_cells]) -> sums [n][1 + V]
+        (the raw sums of pmc_integrate_weighted_rays), and the temperatures come from `temperatures`, a callable (tables) ->
+        [H + 1][num_cells], or else are computed by the host from `rf`, the table rf[m * nbins + ell].  when: "Setup" or "Run" for the
+        probes with that probeAfter only, None for all"""
         import numpy as np
         assert self._setup, "call setup() first"
         os.makedirs(outdir, exist_ok=True)
         code = {None: -1, "Setup": 0, "Run": 1}[when]
         failure = []
-        if integrator is None:
-            function, user = None, None
-        elif hasattr(integrator, "integrate_callback"):
-            function, user = integrator.integrate_callback()
-        else:
-            num_cells = int(scene_head(self).grid.num_cells)
-
+        keep = []
+        engine = ProbeEngine()
+        num_cells = int(scene_head(self).grid.num_cells)
+        if hasattr(integrator, "integrate_callback"):
+            engine.integrate, engine.user = integrator.integrate_callback()
+            needs_field = lib().skh_probes_need_radiation_field(self._h, code) == 1
+            if needs_field:
+                # (an engine without these entry points -- an older libpmc.so -- gives None: the host layer then says what the probe lacks)
+                engine.integrate_weighted = getattr(integrator, "weighted_callback", lambda: (None, None))()[0]
+                engine.temperatures = getattr(integrator, "temperature_callback", lambda: (None, None))()[0]
+                if rf is None and integrator.radiation_field_size == self.radiation_field_size:
+                    rf = integrator.download_radiation_field()
+        elif integrator is not None:
             def call(_, n, origins, directions, num_values, values, sums):
                 try:
                     r = np.ctypeslib.as_array(origins, shape=(n, 3))
@@ -314,9 +433,43 @@ class Simulation:
                     failure.append(error)
                     return 1
 
-            keep = INTEGRATE_FN(call)
-            function, user = C.cast(keep, C.c_void_p), None
-        if lib().skh_write_probes_when(self._h, function, user, os.fsencode(outdir), code) != 0:
+            keep.append(INTEGRATE_FN(call))
+            engine.integrate = C.cast(keep[-1], C.c_void_p)
+        if weighted is not None:
+            def call_weighted(_, n, origins, directions, num_values, weights, values, sums):
+                try:
+                    r = np.ctypeslib.as_array(origins, shape=(n, 3))
+                    k = np.ctypeslib.as_array(directions, shape=(n, 3))
+                    w = np.ctypeslib.as_array(weights, shape=(num_cells,))
+                    q = np.ctypeslib.as_array(values, shape=(num_values, num_cells))
+                    result = np.asarray(weighted(r, k, w, q), dtype=np.float64).reshape(n, 1 + num_values)
+                    np.ctypeslib.as_array(sums, shape=(n, 1 + num_values))[:] = result
+                    return 0
+                except Exception as error:
+                    failure.append(error)
+                    return 1
+
+            keep.append(INTEGRATE_WEIGHTED_FN(call_weighted))
+            engine.integrate_weighted = C.cast(keep[-1], C.c_void_p)
+        if temperatures is not None:
+            def call_temperatures(_, tables, out):
+                try:
+                    struct = DustHeating.from_address(tables)
+                    shape = (struct.num_components + 1, struct.num_cells)
+                    np.ctypeslib.as_array(out, shape=shape)[:] = np.asarray(temperatures(heating_tables_from(struct)), dtype=np.float64).reshape(shape)
+                    return 0
+                except Exception as error:
+                    failure.append(error)
+                    return 1
+
+            keep.append(TEMPERATURE_FN(call_temperatures))
+            engine.temperatures = C.cast(keep[-1], C.c_void_p)
+        if rf is not None:
+            table = np.ascontiguousarray(rf, dtype=np.float64).reshape(-1)
+            assert table.size == self.radiation_field_size
+            keep.append(table)
+            engine.rf = table.ctypes.data
+        if lib().skh_write_probes_with(self._h, C.byref(engine), os.fsencode(outdir), code) != 0:
             if failure:
                 raise failure[0]
             raise RuntimeError(lib().skh_last_error().decode())

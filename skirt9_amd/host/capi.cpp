@@ -252,6 +252,31 @@ int skh_probe_map_info(const skh_simulation* h, int32_t map, skh_probe_map* out)
     }
 }
 
+int32_t skh_probe_map_averaged(const skh_simulation* h, int32_t map)
+{
+    try
+    {
+        if (!h || !h->sim) throw std::runtime_error("invalid argument");
+        return h->sim->probeMapInfo(map).averaged ? 1 : 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int32_t skh_probes_need_radiation_field(const skh_simulation* h, int32_t when)
+{
+    try
+    {
+        return h && h->sim && h->sim->probesNeedRadiationField(when) ? 1 : 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
 int skh_probe_map_rays(const skh_simulation* h, int32_t map, double* origins, double* directions)
 {
     try
@@ -297,6 +322,85 @@ int skh_write_probes_when(const skh_simulation* h, skh_integrate_fn integrate, v
 int skh_write_probes(const skh_simulation* h, skh_integrate_fn integrate, void* user, const char* outdir)
 {
     return skh_write_probes_when(h, integrate, user, outdir, -1);
+}
+
+int skh_write_probes_with(const skh_simulation* h, const skh_probe_engine* engine, const char* outdir, int32_t when)
+{
+    try
+    {
+        if (!h || !h->sim || !engine || !outdir) throw std::runtime_error("invalid argument");
+        skh::Simulation::ProbeEngine e;
+        e.integrate = engine->integrate;
+        e.weighted = engine->integrate_weighted;
+        e.temperatures = engine->temperatures;
+        e.user = engine->user;
+        e.rf = engine->rf;
+        h->sim->writeProbes(e, outdir, when);
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int skh_dust_heating(const skh_simulation* h, pmc_dust_heating* out)
+{
+    try
+    {
+        if (!h || !h->sim || !out) throw std::runtime_error("invalid argument");
+        *out = h->sim->dustHeating().flat;
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int32_t skh_dust_components(const skh_simulation* h, int32_t* components)
+{
+    try
+    {
+        if (!h || !h->sim || !h->sim->hasDustHeating()) return 0;
+        const std::vector<int>& dust = h->sim->dustHeating().components;
+        for (size_t b = 0; components && b != dust.size(); ++b) components[b] = dust[b];
+        return static_cast<int32_t>(dust.size());
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int skh_dust_temperatures(const skh_simulation* h, const double* rf, double* out)
+{
+    try
+    {
+        if (!h || !h->sim || !rf || !out) throw std::runtime_error("invalid argument");
+        h->sim->dustTemperatures(rf, out);
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int skh_dust_temperatures_from(const pmc_dust_heating* tables, const double* rf, double* out)
+{
+    try
+    {
+        if (!tables || !rf || !out) throw std::runtime_error("invalid argument");
+        if (!tables->width || !tables->sigma || !tables->planckabs || !tables->temperature || !tables->cell_factor || !tables->mass_density)
+            throw std::runtime_error("null table");
+        skh::Simulation::dustTemperatures(*tables, rf, out);
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
 }
 
 int skh_summary(const skh_simulation* h, char* buffer, int32_t capacity)

@@ -11,7 +11,9 @@
 // ski file, set it up, run the primary emission segment (here: on the GPU through the C ABI of include/pmc.h),
 // write the instrument output.  The density and opacity probes of the ski file are written with the line integrals of their projected
 // maps computed on the first device (pmc_integrate_rays): those with probeAfter="Setup" before the photon loop, the others after it
-// (ProbeSystem::probeSetup / probeRun).  There is no CPU fallback: without a HIP device pmc_create fails and so does the run.
+// (ProbeSystem::probeSetup / probeRun).  The temperature probes are written after the loop -- with several devices after the radiation field
+// has been summed over them -- from the table on the first device: the dust temperatures by pmc_dust_temperatures, the averages along the
+// rays of their maps by pmc_integrate_weighted_rays.  There is no CPU fallback: without a HIP device pmc_create fails and so does the run.
 
 #include "../../include/pmc.h"
 #include "../../include/skirt_host.h"
@@ -144,8 +146,20 @@ int main(int argc, char** argv)
                                           const double* cellValues, double* sums) {
         return pmc_integrate_rays(static_cast<pmc_ctx*>(user), numRays, origins, directions, numValues, cellValues, sums);
     };
+    skh_probe_engine probeEngine{};
+    probeEngine.integrate = integrate;
+    probeEngine.integrate_weighted = [](void* user, int64_t numRays, const double* origins, const double* directions, int32_t numValues,
+                                        const double* cellWeights, const double* cellValues, double* sums) {
+        return pmc_integrate_weighted_rays(static_cast<pmc_ctx*>(user), numRays, origins, directions, numValues, cellWeights, cellValues, sums);
+    };
+    probeEngine.temperatures = [](void* user, const pmc_dust_heating* tables, double* out) {
+        return pmc_dust_temperatures(static_cast<pmc_ctx*>(user), tables, out);
+    };
     auto writeProbes = [&](int when) {
-        if (skh_write_probes_when(sim, integrate, ctxs[0], outdir.c_str(), when) == 0) return true;
+        probeEngine.user = ctxs[0];
+        // (after the run: the host copy of the radiation field table, for DustAbsorptionPerCellProbe)
+        probeEngine.rf = when == 1 && !rf.empty() ? rf.data() : nullptr;
+        if (skh_write_probes_with(sim, &probeEngine, outdir.c_str(), when) == 0) return true;
         // (the host layer reports that the integrator failed; the engine says why)
         errors[0] = std::string(skh_last_error()) + (*pmc_last_error() ? std::string(": ") + pmc_last_error() : std::string());
         return false;

@@ -53,6 +53,19 @@ namespace skh
         if (fluxStyle == "Wavelength") return out("wavelengthmeanintensity", Jlambda);
         return out("frequencymeanintensity", lambda * lambda * Jlambda / constants::c);
     }
+    std::string OutputUnits::smonluminosity() const
+    {
+        if (fluxStyle == "Neutral") return "lambda*L_lambda";
+        if (fluxStyle == "Wavelength") return "L_lambda";
+        return "L_nu";
+    }
+    std::string OutputUnits::umonluminosity() const { return unit(stylePrefix(fluxStyle) + "monluminosity"); }
+    double OutputUnits::omonluminosity(double lambda, double Llambda) const
+    {
+        if (fluxStyle == "Neutral") return out("neutralmonluminosity", lambda * Llambda);
+        if (fluxStyle == "Wavelength") return out("wavelengthmonluminosity", Llambda);
+        return out("frequencymonluminosity", lambda * lambda * Llambda / constants::c);
+    }
     double OutputUnits::osurfacebrightness(double lambda, double flambda) const
     {
         if (fluxStyle == "Neutral") return out("neutralsurfacebrightness", lambda * flambda);
@@ -498,15 +511,10 @@ namespace skh
 
     // ================================================================ DustMix (DustMix.cpp:47-162)
 
-    void DustMix::setup(double rangeMin, double rangeMax, const std::vector<double>& simulationWavelengths)
+    // the wavelengths at which the dust properties are sampled (DustMix.cpp:57-82): every integer multiple of 1/1000 dex inside the range, plus
+    // all configured wavelengths; beyond 10 cm the dust is transparent: the table then ends with 10 cm and one point just above it
+    static Array dustSampleWavelengths(double rangeMin, double rangeMax, const std::vector<double>& simulationWavelengths, bool& beyondRadio)
     {
-        if (inLambda.size() != inKappaExt.size() || inLambda.size() != inAlbedo.size()
-            || inLambda.size() != inAsymmpar.size())
-            throw std::runtime_error("Number of listed properties does not match number of listed wavelengths");
-        if (inLambda.empty()) throw std::runtime_error("Dust properties must be tabulated for at least one wavelength");
-
-        // sample wavelengths: every integer multiple of 1/1000 dex inside the range, plus all configured wavelengths
-        // (DustMix.cpp:57-72)
         const double perDecade = 1000;
         const int firstTick = std::floor(perDecade * log10(rangeMin));
         const int lastTick = std::ceil(perDecade * log10(rangeMax));
@@ -516,26 +524,22 @@ namespace skh
         samples.insert(samples.end(), simulationWavelengths.begin(), simulationWavelengths.end());
         std::sort(samples.begin(), samples.end());
         samples.erase(std::unique(samples.begin(), samples.end()), samples.end());
-
-        // beyond 10 cm the dust is transparent: the table ends with 10 cm and one point just above it (DustMix.cpp:74-82)
         const double tenCm = 0.1;
-        const bool beyondRadio = samples.back() > tenCm;
+        beyondRadio = samples.back() > tenCm;
         if (beyondRadio)
         {
             samples.resize(tab::bracket(samples, tenCm) + 1);
             if (samples.empty() || samples.back() != tenCm) samples.push_back(tenCm);
             samples.push_back(tenCm * 1.001);
         }
-        lambdaSample = samples;
-        const int numLambda = static_cast<int>(lambdaSample.size());
+        return samples;
+    }
 
-        // index grid shifted to the left of the sample points (DustMix.cpp:93-98)
-        lambdaBorder.assign(numLambda, 0.);
-        lambdaBorder[0] = lambdaSample[0];
-        for (int ell = 1; ell != numLambda; ++ell) lambdaBorder[ell] = sqrt(lambdaSample[ell] * lambdaSample[ell - 1]);
-
-        // TabulatedDustMix::getOpticalProperties (TabulatedDustMix.cpp:12-45)
-        Array inl = inLambda, ink = inKappaExt, ina = inAlbedo, ing = inAsymmpar;
+    // TabulatedDustMix::getOpticalProperties (TabulatedDustMix.cpp:12-45): the configured table in ascending order, as cross sections
+    void DustMix::tabulated(Array& inl, Array& insigmaabs, Array& insigmasca, Array& ing) const
+    {
+        Array ink = inKappaExt, ina = inAlbedo;
+        inl = inLambda, ing = inAsymmpar;
         if (inl.size() > 1 && inl[0] > inl[inl.size() - 1])
         {
             std::reverse(inl.begin(), inl.end());
@@ -543,12 +547,49 @@ namespace skh
             std::reverse(ina.begin(), ina.end());
             std::reverse(ing.begin(), ing.end());
         }
-        Array insigmaabs(inl.size()), insigmasca(inl.size());
+        insigmaabs.assign(inl.size(), 0.);
+        insigmasca.assign(inl.size(), 0.);
         for (size_t i = 0; i < inl.size(); ++i)
         {
             insigmaabs[i] = mu * ink[i] * (1. - ina[i]);
             insigmasca[i] = mu * ink[i] * ina[i];
         }
+    }
+
+    void DustMix::heatingSamples(Array& lambdav, Array& sigmaabsv) const
+    {
+        // Configuration::simulationWavelengthRange (Configuration.cpp:576-582, 599): a simulation with a radiation field extends its range to
+        // 0.09 - 2000 micron for these integrals, before the narrow margin is applied; the tables of the photon loop are sampled on the
+        // range without that extension (the same ticks inside it), so they stay what they were
+        const double margin = 1. + 1. / 100.;
+        const double lo = std::min(setupRangeMin_, 0.09e-6 / margin), hi = std::max(setupRangeMax_, 2000e-6 * margin);
+        bool beyondRadio;
+        lambdav = dustSampleWavelengths(lo, hi, setupWavelengths_, beyondRadio);
+        Array inl, insigmaabs, insigmasca, ing;
+        tabulated(inl, insigmaabs, insigmasca, ing);
+        sigmaabsv = tab::resampleClamped<tab::logLog>(lambdav, inl, insigmaabs);
+    }
+
+    void DustMix::setup(double rangeMin, double rangeMax, const std::vector<double>& simulationWavelengths)
+    {
+        if (inLambda.size() != inKappaExt.size() || inLambda.size() != inAlbedo.size()
+            || inLambda.size() != inAsymmpar.size())
+            throw std::runtime_error("Number of listed properties does not match number of listed wavelengths");
+        if (inLambda.empty()) throw std::runtime_error("Dust properties must be tabulated for at least one wavelength");
+        setupRangeMin_ = rangeMin, setupRangeMax_ = rangeMax, setupWavelengths_ = simulationWavelengths;
+
+        // sample wavelengths (DustMix.cpp:57-82)
+        bool beyondRadio;
+        lambdaSample = dustSampleWavelengths(rangeMin, rangeMax, simulationWavelengths, beyondRadio);
+        const int numLambda = static_cast<int>(lambdaSample.size());
+
+        // index grid shifted to the left of the sample points (DustMix.cpp:93-98)
+        lambdaBorder.assign(numLambda, 0.);
+        lambdaBorder[0] = lambdaSample[0];
+        for (int ell = 1; ell != numLambda; ++ell) lambdaBorder[ell] = sqrt(lambdaSample[ell] * lambdaSample[ell - 1]);
+
+        Array inl, insigmaabs, insigmasca, ing;
+        tabulated(inl, insigmaabs, insigmasca, ing);
         sigmaAbs = tab::resampleClamped<tab::logLog>(lambdaSample, inl, insigmaabs);
         sigmaSca = tab::resampleClamped<tab::logLog>(lambdaSample, inl, insigmasca);
         asymmpar = tab::resampleClamped<tab::logLin>(lambdaSample, inl, ing);

@@ -39,6 +39,9 @@ namespace skh
         std::string smeanintensity() const;  // Units.cpp:613-651
         std::string umeanintensity() const;
         double omeanintensity(double lambda, double Jlambda) const;
+        std::string smonluminosity() const;  // Units.cpp:443-481
+        std::string umonluminosity() const;
+        double omonluminosity(double lambda, double Llambda) const;
     };
 
     // ---------------------------------------------------------------- geometries
@@ -297,6 +300,7 @@ namespace skh
         int indexForLambda(double lambda) const { return tab::bracketClipped(lambdaBorder, lambda); }
         double sectionExt(double lambda) const { return sigmaExt[indexForLambda(lambda)]; }
         double sectionSca(double lambda) const { return sigmaSca[indexForLambda(lambda)]; }
+        double sectionAbs(double lambda) const { return sigmaAbs[indexForLambda(lambda)]; }
     };
 
     // DustMix tables for a TabulatedDustMix subclass (MeanListDustMix / MeanFileDustMix):
@@ -309,6 +313,14 @@ namespace skh
 
         void setup(double rangeMin, double rangeMax, const std::vector<double>& simulationWavelengths) override;
         double mass() const override { return mu; }
+        // what EquilibriumDustEmissionCalculator::precalculate gets (DustMix.cpp:207-210): the sampling wavelengths of a simulation with a
+        // radiation field and the absorption cross sections on them, before the suppression beyond 10 cm (:212-219)
+        void heatingSamples(Array& lambdav, Array& sigmaabsv) const;
+
+    private:
+        void tabulated(Array& inl, Array& insigmaabs, Array& insigmasca, Array& ing) const;
+        double setupRangeMin_{0}, setupRangeMax_{0};
+        std::vector<double> setupWavelengths_;
     };
 
     // ElectronMix without polarization and without thermal dispersion, above the Compton limit (SKIRT/core/ElectronMix.cpp:99-146):

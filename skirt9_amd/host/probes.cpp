@@ -1,10 +1,14 @@
-// probes.cpp -- the density and opacity probes of the spatial grid, per cell and in parallel projection:
+// probes.cpp -- the density, opacity and temperature probes of the spatial grid, per cell and in parallel projection:
 //   <prefix>_<probe>_<fileid>.dat            PerCellForm (PerCellForm.cpp:14-38)
 //   <prefix>_<probe>_<projectedFileid>.fits  ParallelProjectionForm (ParallelProjectionForm.cpp:18-116)
 // restating DensityProbe::probe (DensityProbe.cpp:14-100), OpacityProbe::probe (OpacityProbe.cpp:37-168) and the ProbeFormBridge between a
 // probe and its form (ProbeFormBridge.cpp:37-57, 114-136, 548-584, 628-650, 707-725) for the aggregations System, Type and Component.
 // The line integrals of a projected map -- ProbeFormBridge::valuesAlongPath -- are not computed here: the caller's integrator walks the
 // rays (the engine's pmc_integrate_rays); this file makes the rays and the cell values, averages the sub-samples and writes the files.
+// TemperatureProbe (TemperatureProbe.cpp:31-114, dust only) is the one averaged quantity: its cell values are the dust temperatures of
+// temperature.cpp -- from the engine's pmc_dust_temperatures or from the host's restatement --, its maps are density-weighted averages along the
+// rays (ProbeFormBridge.cpp:61-82, 652-676; the engine's pmc_integrate_weighted_rays returns the raw sums, the division is done here).
+// DustAbsorptionPerCellProbe (DustAbsorptionPerCellProbe.cpp:25-63) is a text file from the same radiation field table.
 
 #include "simulation.hpp"
 #include "units.hpp"
@@ -19,7 +23,8 @@ namespace skh
     // one ProbeFormBridge::writeQuantity call: a scalar (density) or compound (opacity per wavelength) quantity accumulated along paths
     struct Simulation::ProbeQuantity
     {
-        enum Kind { MassDensity, NumberDensity, Opacity } kind{MassDensity};
+        enum Kind { MassDensity, NumberDensity, Opacity, Temperature } kind{MassDensity};
+        int temperatureRow{0};  // Temperature: the row of the table [H + 1][numCells] of Simulation::dustTemperatures; the weights are the mass density of `components`
         std::string fileid, projectedFileid, quantity, projectedQuantity, description, projectedDescription;
         std::vector<int> components;  // the medium components summed, in order
         bool compound{false};
@@ -38,6 +43,29 @@ namespace skh
         {
             (_media[h]->mix->isElectrons() ? electrons : dust).push_back(h);
             all.push_back(h);
+        }
+        if (probe.type == "DustAbsorptionPerCellProbe") return result;  // (a file of its own kind: writeProbes)
+        if (probe.type == "TemperatureProbe")
+        {
+            // TemperatureProbe.cpp:45-79: dust only, and only with a panchromatic radiation field (the electron components of this path
+            // keep no temperature: hasTemperature, :16-27)
+            if (!hasDustHeating()) return result;
+            auto add = [&](const std::string& id, const std::vector<int>& components, int row) {
+                ProbeQuantity q;
+                q.kind = ProbeQuantity::Temperature;
+                q.fileid = q.projectedFileid = id + "_T";
+                q.quantity = q.projectedQuantity = "temperature";
+                q.description = "indicative temperature";
+                q.projectedDescription = "density-weighted indicative temperature";
+                q.components = components;
+                q.temperatureRow = row;
+                result.push_back(q);
+            };
+            if (probe.aggregation == "Type")
+                add("dust", dust, static_cast<int>(dust.size()));
+            else
+                for (size_t b = 0; b != dust.size(); ++b) add(std::to_string(dust[b]), {dust[b]}, static_cast<int>(b));
+            return result;
         }
         if (probe.type == "DensityProbe")
         {
@@ -111,7 +139,7 @@ namespace skh
         {
             const double n = _density[h][m];
             const MaterialMix& mix = *_media[h]->mix;
-            if (q.kind == ProbeQuantity::MassDensity)
+            if (q.kind == ProbeQuantity::MassDensity || q.kind == ProbeQuantity::Temperature)  // (a temperature's weight: MediumSystem.cpp:513-518, 547-550)
                 result += n * mix.mass();
             else if (q.kind == ProbeQuantity::NumberDensity)
                 result += n;
@@ -153,6 +181,7 @@ namespace skh
                     info.numValues = q.numValues();
                     info.numRays = int64_t(info.nx) * info.ny * info.sampling * info.sampling;
                     info.afterSetup = probe.afterSetup;
+                    info.averaged = q.kind == ProbeQuantity::Temperature;
                     return info;
                 }
         }
@@ -236,19 +265,115 @@ namespace skh
         noSuchMap(map);
     }
 
+    bool Simulation::probesNeedRadiationField(int when) const
+    {
+        if (!_hasMedium || !_storeRadiationField) return false;
+        bool hasDust = false;  // (MediumSystem::hasDust: without dust neither probe writes a file)
+        for (const auto& part : _media) hasDust = hasDust || !part->mix->isElectrons();
+        if (!hasDust) return false;
+        for (const ProbeModel& probe : _probes)
+        {
+            if (when >= 0 && (when == 0) != probe.afterSetup) continue;
+            if (probe.type == "DustAbsorptionPerCellProbe" || (probe.type == "TemperatureProbe" && hasDustHeating())) return true;
+        }
+        return false;
+    }
+
     std::vector<std::string> Simulation::writeProbes(IntegrateFn integrate, void* user, const std::string& outdir, int when) const
+    {
+        ProbeEngine engine;
+        engine.integrate = integrate;
+        engine.user = user;
+        return writeProbes(engine, outdir, when);
+    }
+
+    std::vector<std::string> Simulation::writeProbes(const ProbeEngine& engine, const std::string& outdir, int when) const
     {
         std::vector<std::string> files;
         std::string base = outdir;
         if (!base.empty() && base.back() != '/') base += '/';
         base += _prefix + "_";
         const int numCells = _grid->numCells();
+        // the dust temperatures [H + 1][numCells], computed when the first probe asks for them: by the engine from the table on the device,
+        // else by the host from the caller's copy of it
+        std::vector<double> temperatures;
+        auto needTemperatures = [&](const std::string& probeName) {
+            if (!temperatures.empty()) return;
+            const DustHeating& tables = dustHeating();
+            temperatures.assign(size_t(tables.flat.num_components + 1) * numCells, 0.);
+            if (engine.temperatures)
+            {
+                if (engine.temperatures(engine.user, &tables.flat, temperatures.data()) != 0)
+                    throw std::runtime_error("probe " + probeName + ": the computation of the dust temperatures failed");
+            }
+            else if (engine.rf)
+                dustTemperatures(engine.rf, temperatures.data());
+            else
+                throw std::runtime_error("probe " + probeName + " needs the radiation field: hand over the table or the engine that holds it");
+        };
         for (const ProbeModel& probe : _probes)
         {
             if (when >= 0 && (when == 0) != probe.afterSetup) continue;
+            if (probe.type == "DustAbsorptionPerCellProbe")
+            {
+                // DustAbsorptionPerCellProbe.cpp:25-63 through TextOutFile; MediumSystem::hasDust
+                if (!_hasMedium || !_storeRadiationField) continue;
+                std::vector<int> dust;
+                for (size_t h = 0; h != _media.size(); ++h)
+                    if (!_media[h]->mix->isElectrons()) dust.push_back(static_cast<int>(h));
+                if (dust.empty()) continue;
+                if (!engine.rf) throw std::runtime_error("probe " + probe.name + " needs the radiation field table");
+                const WavelengthGrid& wlg = *_rfGrid;
+                const int nbins = wlg.numBins();
+                const bool reverse = _units.wavelengthStyle != "Wavelength";
+                const std::string path = base + probe.name + "_Labs.dat";
+                std::ofstream out(path);
+                if (!out) throw std::runtime_error("Could not open output file " + path);
+                out << "# Spectral luminosity absorbed by dust per spatial cell" << std::endl;
+                out << "# column 1: spatial cell index (1)" << std::endl;
+                for (int i = 0; i != nbins; ++i)
+                {
+                    const int ell = reverse ? nbins - 1 - i : i;
+                    char buf[40];
+                    snprintf(buf, sizeof(buf), "%1.6g", _units.owavelength(wlg.wavelength(ell)));
+                    out << "# column " << (i + 2) << ": " << _units.smonluminosity() << "^abs at " << _units.swavelength() << " = " << buf << " "
+                        << _units.uwavelength() << " (" << _units.umonluminosity() << ")" << std::endl;
+                }
+                for (int m = 0; m != numCells; ++m)
+                {
+                    char buf[40];
+                    snprintf(buf, sizeof(buf), "%1.0f", double(m));
+                    std::string line = buf;
+                    // MediumSystem::meanIntensity (MediumSystem.cpp:1370-1380) and the factor 4 pi V back again
+                    const double Jfactor = 1. / (4. * M_PI * _grid->volume(m));
+                    const double factor = 4. * M_PI * _grid->volume(m);
+                    for (int i = 0; i != nbins; ++i)
+                    {
+                        const int ell = reverse ? nbins - 1 - i : i;
+                        const double lambda = wlg.wavelength(ell);
+                        const double J = engine.rf[size_t(m) * nbins + ell] * Jfactor / wlg.effectiveWidth(ell);
+                        // MediumSystem::opacityAbs(lambda, m, Dust) (MediumSystem.cpp:599-605; DustMix.cpp:347-351)
+                        double opacity = 0.;
+                        for (int h : dust)
+                        {
+                            const double n = _density[h][m];
+                            opacity += n > 0. ? n * _media[h]->mix->sectionAbs(lambda) : 0.;
+                        }
+                        const double Labs = J * factor * opacity;
+                        snprintf(buf, sizeof(buf), " %1.9e", _units.omonluminosity(lambda, Labs));
+                        line += buf;
+                    }
+                    out << line << std::endl;
+                }
+                files.push_back(path);
+                continue;
+            }
             for (const ProbeQuantity& q : probeQuantities(probe))
             {
                 const int numValues = q.numValues();
+                const bool averaged = q.kind == ProbeQuantity::Temperature;
+                if (averaged) needTemperatures(probe.name);
+                const double* temperature = averaged ? temperatures.data() + size_t(q.temperatureRow) * numCells : nullptr;
                 if (!probe.projected)
                 {
                     // PerCellForm.cpp:14-38 through TextOutFile (TextOutFile.cpp:61-103): the cell index as 'd', the values as 'e' with 9 digits
@@ -280,7 +405,7 @@ namespace skh
                         for (int v = 0; v != numValues; ++v)
                         {
                             // ProbeFormBridge::valuesInCell: the value times the unit factor
-                            snprintf(buf, sizeof(buf), " %1.9e", probeCellValue(q, v, m) * unitFactor);
+                            snprintf(buf, sizeof(buf), " %1.9e", (averaged ? temperature[m] : probeCellValue(q, v, m)) * unitFactor);
                             line += buf;
                         }
                         out << line << std::endl;
@@ -290,10 +415,12 @@ namespace skh
                 }
 
                 // ParallelProjectionForm.cpp:18-116
-                if (!integrate) throw std::runtime_error("probe " + probe.name + " is a projected map: it needs an integrator");
+                if (averaged ? !engine.weighted : !engine.integrate)
+                    throw std::runtime_error("probe " + probe.name + " is a projected map: it needs an integrator");
                 const int Nxp = probe.numPixelsX, Nyp = probe.numPixelsY, Ns = probe.numSampling;
                 const int Nsampling2 = Ns * Ns;
                 const double projectedUnitFactor = _units.out(q.projectedQuantity, 1.);
+                // (an averaged quantity: the weights of the cells -- probeCellValue of a temperature is its weight -- next to the values)
                 std::vector<double> cellValues(size_t(numValues) * numCells);
                 for (int v = 0; v != numValues; ++v)
                     for (int m = 0; m != numCells; ++m) cellValues[size_t(v) * numCells + m] = probeCellValue(q, v, m);
@@ -301,6 +428,7 @@ namespace skh
                 // (rows in batches of about a million rays: the rays of a 10000 x 10000 map with 81 samples would not fit in memory at once)
                 const int raysPerRow = Nxp * Nsampling2;
                 const int rowsPerBatch = std::max(1, (1 << 20) / raysPerRow);
+                const int sumsPerRay = averaged ? 2 : numValues;
                 std::vector<double> origins, directions, sums;
                 for (int j0 = 0; j0 < Nyp; j0 += rowsPerBatch)
                 {
@@ -308,18 +436,31 @@ namespace skh
                     const size_t numRays = size_t(j1 - j0) * raysPerRow;
                     origins.resize(3 * numRays);
                     directions.resize(3 * numRays);
-                    sums.assign(numRays * numValues, 0.);
+                    sums.assign(numRays * sumsPerRay, 0.);
                     projectionRays(probe, j0, j1, origins.data(), directions.data());
-                    if (integrate(user, static_cast<int64_t>(numRays), origins.data(), directions.data(), numValues, cellValues.data(), sums.data()) != 0)
-                        throw std::runtime_error("probe " + probe.name + ": the ray integrator failed");
+                    const int rc = averaged ? engine.weighted(engine.user, static_cast<int64_t>(numRays), origins.data(), directions.data(), 1,
+                                                              cellValues.data(), temperature, sums.data())
+                                            : engine.integrate(engine.user, static_cast<int64_t>(numRays), origins.data(), directions.data(), numValues,
+                                                               cellValues.data(), sums.data());
+                    if (rc != 0) throw std::runtime_error("probe " + probe.name + ": the ray integrator failed");
                     size_t ray = 0;
                     for (int j = j0; j != j1; ++j)
                         for (int i = 0; i != Nxp; ++i)
                             for (int s = 0; s != Nsampling2; ++s, ++ray)
                                 for (int p = 0; p != numValues; ++p)
                                 {
-                                    // valuesAlongPath: the sum times the projected unit factor; then the share of the sub-sample
-                                    const double value = sums[ray * numValues + p] * projectedUnitFactor;
+                                    double value;
+                                    if (averaged)
+                                    {
+                                        // valuesAlongPath, GridScalarAveraged: if (totalWeight) value *= unit factor / totalWeight
+                                        const double totalWeight = sums[ray * 2];
+                                        value = sums[ray * 2 + 1];
+                                        if (totalWeight) value *= projectedUnitFactor / totalWeight;
+                                    }
+                                    else
+                                        // valuesAlongPath: the sum times the projected unit factor
+                                        value = sums[ray * numValues + p] * projectedUnitFactor;
+                                    // ... then the share of the sub-sample
                                     vvv[(size_t(p) * Nyp + j) * Nxp + i] += value / Nsampling2;
                                 }
                 }

@@ -746,12 +746,32 @@ namespace skh
         }
         if (_instruments.empty()) unsupported("a simulation without instruments");
 
-        // ---- probes: the radiation field per cell (RadiationFieldProbe + PerCellForm); densities and opacities per cell and in parallel
-        //      projection (DensityProbe, OpacityProbe + PerCellForm, ParallelProjectionForm: probes.cpp); nothing else is on this path
+        // ---- probes: the radiation field per cell (RadiationFieldProbe + PerCellForm); densities, opacities and dust temperatures per cell and
+        //      in parallel projection (DensityProbe, OpacityProbe, TemperatureProbe + PerCellForm, ParallelProjectionForm) and the absorbed
+        //      luminosity per cell (DustAbsorptionPerCellProbe): probes.cpp; nothing else is on this path
         if (const XmlElement* ps = sim.item("probeSystem"))
             for (const XmlElement* pe : ps->items("probes"))
             {
-                if (pe->name == "DensityProbe" || pe->name == "OpacityProbe")
+                const bool temperatureProbe = pe->name == "TemperatureProbe";
+                if (temperatureProbe || pe->name == "DustAbsorptionPerCellProbe")
+                {
+                    // without a panchromatic radiation field the reference writes nothing for these (TemperatureProbe.cpp:45); here the
+                    // probe is refused instead
+                    if (_oligo) unsupported(pe->name + " in an oligochromatic simulation");
+                    if (!_storeRadiationField) unsupported(pe->name + " in a simulation that does not store the radiation field");
+                }
+                if (pe->name == "DustAbsorptionPerCellProbe")
+                {
+                    // DustAbsorptionPerCellProbe.hpp: no form, always after the run
+                    if (rd.boolean(*pe, "writeWavelengthGrid", false)) unsupported("DustAbsorptionPerCellProbe writeWavelengthGrid");
+                    ProbeModel probe;
+                    probe.type = pe->name;
+                    probe.name = pe->attr("probeName", "");
+                    probe.afterSetup = false;
+                    _probes.push_back(std::move(probe));
+                    continue;
+                }
+                if (pe->name == "DensityProbe" || pe->name == "OpacityProbe" || temperatureProbe)
                 {
                     ProbeModel probe;
                     probe.type = pe->name;
@@ -759,10 +779,12 @@ namespace skh
                     // (SpatialGridFormProbe.hpp:23: the default form is DefaultCutsForm)
                     const XmlElement* form = pe->item("form");
                     const std::string formName = form ? form->name : std::string("DefaultCutsForm");
-                    if (formName != "PerCellForm" && formName != "ParallelProjectionForm") unsupported("probe form " + formName);
-                    // (SpatialGridWhenFormProbe.hpp:31: Setup unless the probe is a temperature probe)
-                    const std::string after = pe->attr("probeAfter", "Setup");
-                    if (after != "Setup" && after != "Run") unsupported(pe->name + " probeAfter " + after);
+                    if (formName != "PerCellForm" && formName != "ParallelProjectionForm")
+                        unsupported((temperatureProbe ? "TemperatureProbe form " : "probe form ") + formName);
+                    // (SpatialGridWhenFormProbe.hpp:31: Setup unless the probe is a temperature probe; a temperature probe before the
+                    // secondary emission phase only warns, TemperatureProbe.cpp:49-54, and one after it needs that phase)
+                    const std::string after = pe->attr("probeAfter", temperatureProbe ? "Run" : "Setup");
+                    if (temperatureProbe ? after != "Run" : (after != "Setup" && after != "Run")) unsupported(pe->name + " probeAfter " + after);
                     probe.afterSetup = after == "Setup";
                     probe.aggregation = pe->attr("aggregation", "Type");
                     if (probe.aggregation == "Fragment") unsupported(pe->name + " aggregation Fragment");
@@ -788,7 +810,7 @@ namespace skh
                     }
                     if (const XmlElement* wg = pe->item("wavelengthGrid"))
                     {
-                        if (pe->name != "OpacityProbe") throw std::runtime_error("ski: DensityProbe has no wavelengthGrid");
+                        if (pe->name != "OpacityProbe") throw std::runtime_error("ski: " + pe->name + " has no wavelengthGrid");
                         if (_oligo) unsupported("OpacityProbe wavelengthGrid in an oligochromatic simulation");
                         probe.ownGrid = makeWavelengthGrid(*wg, rd);
                     }

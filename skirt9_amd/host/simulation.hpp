@@ -8,6 +8,7 @@
 
 #include "model.hpp"
 #include <cstdint>
+#include <mutex>
 
 namespace skh
 {
@@ -59,6 +60,7 @@ namespace skh
             int nx{0}, ny{0}, sampling{1}, numValues{1};
             int64_t numRays{0};    // nx * ny * sampling^2
             bool afterSetup{true};
+            bool averaged{false};  // a weighted average along the rays (TemperatureProbe) instead of an integral
         };
         // sums[i * numValues + v] = sum over the path of ray i of ds * cellValues[v * numCells + m]; nonzero: failure
         typedef int (*IntegrateFn)(void* user, int64_t numRays, const double* origins, const double* directions, int32_t numValues,
@@ -72,6 +74,41 @@ namespace skh
         // writes the probe files; when: 0 the probes with probeAfter Setup, 1 those with Run, -1 all.  The per-cell files need no
         // integrator, which may be null when no projected map is written
         std::vector<std::string> writeProbes(IntegrateFn integrate, void* user, const std::string& outdir, int when = -1) const;
+
+        // Dust temperatures from the stored radiation field (temperature.cpp): the tables of EquilibriumDustEmissionCalculator::precalculate
+        // (EquilibriumDustEmissionCalculator.cpp:18-93) per dust component, in the layout of pmc_dust_heating (include/pmc.h) together with the
+        // cell factors 1 / (4 pi V) and the mass densities; built at the first request (a thousand Planck integrals per component) and valid
+        // while the simulation lives.  Only for a panchromatic simulation that stores the radiation field and has dust.
+        struct DustHeating
+        {
+            std::vector<int> components;  // the dust components h, in order
+            Array lambda, width, temperature, sigma, planckabs, cellFactor, massDensity;
+            pmc_dust_heating flat{};
+        };
+        bool hasDustHeating() const;
+        const DustHeating& dustHeating() const;
+        // out[h][m] for the dust components in order, then the mass-weighted mean (MediumSystem::indicativeTemperature,
+        // MediumSystem.cpp:1384-1427): [H + 1][numCells], from the table rf[m * nbins + ell]
+        void dustTemperatures(const double* rf, double* out) const { dustTemperatures(dustHeating().flat, rf, out); }
+        static void dustTemperatures(const pmc_dust_heating& tables, const double* rf, double* out);
+
+        // TemperatureProbe and DustAbsorptionPerCellProbe need the radiation field: what the caller hands to writeProbes next to the integrator.
+        // temperatures (the engine's pmc_dust_temperatures, from the table on the device) or, without it, rf (the table on the host, from
+        // which the host computes them); rf also serves DustAbsorptionPerCellProbe; weighted: the engine's pmc_integrate_weighted_rays
+        typedef int (*WeightedFn)(void* user, int64_t numRays, const double* origins, const double* directions, int32_t numValues,
+                                  const double* cellWeights, const double* cellValues, double* sums);
+        typedef int (*TemperatureFn)(void* user, const pmc_dust_heating* tables, double* out);
+        struct ProbeEngine
+        {
+            IntegrateFn integrate{nullptr};
+            WeightedFn weighted{nullptr};
+            TemperatureFn temperatures{nullptr};
+            void* user{nullptr};
+            const double* rf{nullptr};
+        };
+        std::vector<std::string> writeProbes(const ProbeEngine& engine, const std::string& outdir, int when = -1) const;
+        // whether a probe written with `when` reads the radiation field (a TemperatureProbe or DustAbsorptionPerCellProbe that writes a file)
+        bool probesNeedRadiationField(int when = -1) const;
 
         // human-readable summary (grid size, tables, ...) for logs and tests
         std::string summary() const;
@@ -134,7 +171,9 @@ namespace skh
         std::unique_ptr<WavelengthGrid> _rfGridOwn;       // radiationFieldWLG as configured (panchromatic)
         const WavelengthGrid* _rfGrid{nullptr};           // Configuration::radiationFieldWLG()
         std::vector<std::string> _rfProbeNames;           // RadiationFieldProbe items with a PerCellForm
-        // DensityProbe and OpacityProbe items
+        mutable std::mutex _heatingLock;
+        mutable std::unique_ptr<DustHeating> _heating;
+        // DensityProbe, OpacityProbe, TemperatureProbe and DustAbsorptionPerCellProbe items
         struct ProbeModel
         {
             std::string type, name, aggregation;  // aggregation: System | Type | Component

@@ -162,7 +162,8 @@ namespace skh
                             {"wavelengthfluxdensity", "W/m3"}, {"wavelengthsurfacebrightness", "W/m3/sr"},
                             {"neutralfluxdensity", "W/m2"}, {"neutralsurfacebrightness", "W/m2/sr"},
                             {"masssurfacedensity", "kg/m2"}, {"massvolumedensity", "kg/m3"}, {"numbersurfacedensity", "1/m2"},
-                            {"numbervolumedensity", "1/m3"}, {"opacity", "1/m"}, {"dimensionless", "1"}});
+                            {"numbervolumedensity", "1/m3"}, {"opacity", "1/m"}, {"dimensionless", "1"},
+                            {"neutralmonluminosity", "W"}, {"wavelengthmonluminosity", "W/m"}, {"frequencymonluminosity", "W/Hz"}});
             def("StellarUnits", {{"neutralmeanintensity", "W/m2/sr"}, {"wavelengthmeanintensity", "W/m2/micron/sr"},
                                  {"frequencymeanintensity", "W/m2/Hz/sr"}, {"length", "AU"}, {"distance", "pc"}, {"wavelength", "micron"}, {"velocity", "km/s"},
                                  {"masscoefficient", "m2/kg"}, {"mass", "Msun"}, {"temperature", "K"}, {"magneticfield", "uG"},
@@ -172,7 +173,8 @@ namespace skh
                                  {"wavelengthsurfacebrightness", "W/m2/micron/arcsec2"},
                                  {"neutralfluxdensity", "W/m2"}, {"neutralsurfacebrightness", "W/m2/arcsec2"},
                                  {"masssurfacedensity", "Msun/AU2"}, {"massvolumedensity", "Msun/AU3"}, {"numbersurfacedensity", "1/cm2"},
-                                 {"numbervolumedensity", "1/cm3"}, {"opacity", "1/AU"}, {"dimensionless", "1"}});
+                                 {"numbervolumedensity", "1/cm3"}, {"opacity", "1/AU"}, {"dimensionless", "1"},
+                                 {"neutralmonluminosity", "Lsun"}, {"wavelengthmonluminosity", "Lsun/micron"}, {"frequencymonluminosity", "W/Hz"}});
             def("ExtragalacticUnits",
                 {{"neutralmeanintensity", "W/m2/sr"}, {"wavelengthmeanintensity", "W/m2/micron/sr"},
                  {"frequencymeanintensity", "W/m2/Hz/sr"},
@@ -183,7 +185,8 @@ namespace skh
                  {"wavelengthsurfacebrightness", "W/m2/micron/arcsec2"}, {"neutralfluxdensity", "W/m2"},
                  {"neutralsurfacebrightness", "W/m2/arcsec2"},
                  {"masssurfacedensity", "Msun/pc2"}, {"massvolumedensity", "Msun/pc3"}, {"numbersurfacedensity", "1/cm2"},
-                 {"numbervolumedensity", "1/cm3"}, {"opacity", "1/pc"}, {"dimensionless", "1"}});
+                 {"numbervolumedensity", "1/cm3"}, {"opacity", "1/pc"}, {"dimensionless", "1"},
+                 {"neutralmonluminosity", "Lsun"}, {"wavelengthmonluminosity", "Lsun/micron"}, {"frequencymonluminosity", "W/Hz"}});
         }
 
         bool hasSystem(const std::string& system) const { return _systems.count(system) != 0; }
