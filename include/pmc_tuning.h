@@ -18,7 +18,8 @@ extern "C" {
      PMC_RF_ATOMICS, PMC_RF_LOG_PER_SLOT, PMC_STAT_ATOMICS, PMC_STAT_LOG_ENTRIES, PMC_STAT_POOL_NO_GROWTH, PMC_PROP_NO_CHECKPOINTS (octree: at run; Voronoi: at pmc_create),
      PMC_VORO_NO_CULL, PMC_VORO_NO_OBSERVER_LISTS, PMC_VORO_CONE_CULL_ONLY, PMC_VORO_NO_PEEL_KERNEL, PMC_VORO_NO_PROP_KERNEL, PMC_VORO_PLAIN_PROP_ONLY, PMC_VORO_NO_CONE_TABLES, PMC_VORO_NO_DEFERRED_SCAN, PMC_VORO_LINK_COUNT_MAX, PMC_VPROP_XCD_SEGMENTS, PMC_VORO_WALKS_IN_SERIES, PMC_VPROP_BLOCKS_PER_CU, PMC_VPEEL_BLOCKS_PER_CU,
      PMC_TREE_AS_BINTREE (at pmc_create: an octree scene runs through the tables and kernels of the binary tree, every octree node as its three levels of splits),
-     PMC_POISON_ALLOCATIONS (test aid: device arrays the engine does not initialise are filled with 0xA5 bytes)                          alternative code paths (cross-checks, A/B)
+     PMC_POISON_ALLOCATIONS (test aid: device arrays the engine does not initialise are filled with 0xA5 bytes),
+     PMC_LAUNCH_GENERIC (at run: the generic launch kernel whatever the scene's sources are)                                             alternative code paths (cross-checks, A/B)
      PMC_WALK_BLOCKS_PER_CU, PMC_PEEL_BLOCKS_PER_CU, PMC_LAUNCH_BLOCKS_PER_CU,
      PMC_CYCLE_BLOCKS_PER_CU, PMC_TRANSITION_BLOCKS_PER_CU,
      PMC_LIST_TASKS_PER_LANE, PMC_CELL_ORDER, PMC_CELL_SHUFFLE                launch geometry, order of the cell table
@@ -52,6 +53,11 @@ typedef struct pmc_debug_table_values
     int64_t num_slots;
 } pmc_debug_table_values;
 int pmc_debug_tables(pmc_ctx* ctx, pmc_debug_table_values* out);
+
+/* Test aid: the launch kernel the next pmc_run_primary of this context runs (skirt9_amd/csrc/pmc_device.h PMC_LAUNCH_*: bit 0 a moving source, bit 1
+   oligochromatic sources only, bit 2 isotropic emission only, bits 3-4 the geometry set: 0 any, 1 one Sersic source, 2 point sources only).  0, and bit 0
+   alone, is the generic kernel -- of scenes no special flavour covers, and of every scene under the switch PMC_LAUNCH_GENERIC. */
+int pmc_launch_flavour(pmc_ctx* ctx, int32_t* flavour);
 
 /* Test aid: the device function with which the transition kernel turns a uniform deviate X into the scattering cosine of the dipole phase
    function (DipolePhaseFunction::generateCosineFromPhaseFunction), run over n host-supplied deviates u; cos_out: n doubles on the host. */

@@ -58,7 +58,7 @@ extern "C" hipError_t pmcLaunchDipoleCosines(const double* u, int64_t n, double*
 extern "C" hipError_t pmcLaunchSourceVelocities(int slot, int source, const double* r, int64_t n, double* out, hipStream_t stream);
 extern "C" hipError_t pmcLaunchTransition(int slot, int flavour, int slotBase, int numSlots, int group, uint64_t seed, const int* list, int listLen, int maxBlocks,
                                           size_t ldsBytes, const StatLogArgs* statLog, uint64_t count, hipStream_t stream);
-extern "C" hipError_t pmcLaunchLaunch(int slot, int kin, int slotBase, int numSlots, int group, uint64_t first, uint64_t count, uint64_t seed, int initial,
+extern "C" hipError_t pmcLaunchLaunch(int slot, int flavour, int slotBase, int numSlots, int group, uint64_t first, uint64_t count, uint64_t seed, int initial,
                                       int maxBlocks, size_t ldsBytes, const StatLogArgs* statLog, hipStream_t stream);
 extern "C" hipError_t pmcLaunchStatFlush(int slot, const uint32_t* keys, const double* vals, uint32_t* sortedKeys, double* sortedVals, unsigned long long n,
                                          int numParts, void* temp, int numCU, const uint32_t* chunkFill, hipStream_t stream);

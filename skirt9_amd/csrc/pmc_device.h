@@ -247,6 +247,42 @@ struct DevSource
     double  angular_cos_delta;
 };
 
+// ---- launch flavours: what a scene fixes of SourceSystem::launch, so that its launch kernel holds nothing of what the scene cannot reach
+// (launchHistory, pmc_transition.inc; the kernels are listed once: launchKernels, pmc_kernels.hip).  A flavour is
+//   PMC_LAUNCH_KIN        some source moves (DevScene::kin)
+// | PMC_LAUNCH_OLIGO      every source is oligochromatic: no SED sampling, no black body, no wavelength bias
+// | PMC_LAUNCH_ISOTROPIC  every source emits isotropically
+// | geometry << PMC_LAUNCH_GEOM_SHIFT
+//      PMC_LAUNCH_GEOM_ANY     the switch over DevSource::source_kind
+//      PMC_LAUNCH_GEOM_SERSIC  ONE source, a Sersic profile (its tables are staged in LDS)
+//      PMC_LAUNCH_GEOM_POINT   point sources only
+// Flavour 0, and PMC_LAUNCH_KIN alone, is the generic kernel, which asks the source for everything.
+#define PMC_LAUNCH_KIN 1
+#define PMC_LAUNCH_OLIGO 2
+#define PMC_LAUNCH_ISOTROPIC 4
+#define PMC_LAUNCH_GEOM_SHIFT 3
+#define PMC_LAUNCH_GEOM_ANY 0
+#define PMC_LAUNCH_GEOM_SERSIC 1
+#define PMC_LAUNCH_GEOM_POINT 2
+#define PMC_LAUNCH_FLAVOURS (3 << PMC_LAUNCH_GEOM_SHIFT)
+// the flavour of the sources src[0 .. numSources) (plain host code: it reads the kinds only, never the tables)
+static inline int pmcLaunchFlavourOf(const DevSource* src, int numSources, int kin)
+{
+    int flavour = kin ? PMC_LAUNCH_KIN : 0;
+    if (!src || numSources < 1 || numSources > PMC_MAX_SOURCES) return flavour;
+    bool oligo = true, isotropic = true, points = true;
+    for (int si = 0; si < numSources; ++si)
+    {
+        oligo = oligo && src[si].lambda_mode == PMC_LAMBDA_OLIGO;
+        isotropic = isotropic && src[si].angular_kind == PMC_ANGULAR_ISOTROPIC;
+        points = points && src[si].source_kind == PMC_SOURCE_POINT;
+    }
+    // (several sources that are not all points -- sources of mixed kinds --: the generic kernel)
+    if (numSources > 1 && !points) return flavour;
+    const int geometry = points ? PMC_LAUNCH_GEOM_POINT : src[0].source_kind == PMC_SOURCE_SERSIC ? PMC_LAUNCH_GEOM_SERSIC : PMC_LAUNCH_GEOM_ANY;
+    return flavour | (oligo ? PMC_LAUNCH_OLIGO : 0) | (isotropic ? PMC_LAUNCH_ISOTROPIC : 0) | (geometry << PMC_LAUNCH_GEOM_SHIFT);
+}
+
 // the bulk velocity of a source at a launch position (pmc.h pmc_source_velocity): magnitude * field(r)
 struct DevVelocity
 {

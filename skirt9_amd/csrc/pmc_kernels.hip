@@ -361,6 +361,12 @@ static const auto integrateWeightedKernels = flavourTable<5>([](auto f) {
     constexpr int F = decltype(f)::value;
     return KernelFlavour<IntegrateKernel>{integrateRaysKernel<RAY_GRIDS[F], F == 1, true>, 0};
 });
+// launch kernel: the launch flavour (pmc_device.h PMC_LAUNCH_*, pmcLaunchFlavourOf); flavour 0 (| PMC_LAUNCH_KIN) is the generic kernel
+typedef void (*LaunchKernel)(int, int, int, int, uint64_t, uint64_t, uint64_t, int, StatLogArgs);
+static const auto launchKernels = flavourTable<PMC_LAUNCH_FLAVOURS>([](auto f) {
+    constexpr int F = decltype(f)::value;
+    return KernelFlavour<LaunchKernel>{launchKernel<F>, 0};
+});
 // single-ray tracer: the five with the direction in scalar registers, then the octree's two with the direction in vector registers
 typedef void (*TraceKernel)(int, double, double, double, double, double, double, const double*, int32_t*, double*, int32_t, int32_t*);
 static const auto traceKernels = flavourTable<7>([](auto f) {
@@ -415,8 +421,6 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
                {reinterpret_cast<const void*>(&transitionDipoleKernel), transitionMax},
                {reinterpret_cast<const void*>(&transitionKinKernel), transitionMax},
                {reinterpret_cast<const void*>(&transitionKinDipoleKernel), transitionMax},
-               {reinterpret_cast<const void*>(&launchKernel), transitionMax},
-               {reinterpret_cast<const void*>(&launchKinKernel), transitionMax},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_TREE, true>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_CART, true>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
                {reinterpret_cast<const void*>(&cycleStartKernel<GRID_VORO, true>), walkMax + 16 + size_t(PMC_SORT_OBS) * PMC_PEEL_TILES * PMC_PEEL_TILES * sizeof(uint32_t)},
@@ -430,7 +434,7 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
         hipError_t e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
         if (e != hipSuccess) return e;
     }
-    return hipSuccess;
+    return raiseLdsLimits(launchKernels, transitionMax);
 }
 
 // does the octree propagation kernel of this walk flavour keep its pass-1 checkpoints in LDS, behind the grid tables of ldsBytes?
@@ -656,13 +660,15 @@ extern "C" hipError_t pmcLaunchTransition(int slot, int flavour, int slotBase, i
     return hipGetLastError();
 }
 
-// launches of new histories into the slots of the group whose history ended (initial: into all slots of the group); kin: some source moves
-extern "C" hipError_t pmcLaunchLaunch(int slot, int kin, int slotBase, int numSlots, int group, uint64_t first, uint64_t count, uint64_t seed, int initial,
+// launches of new histories into the slots of the group whose history ended (initial: into all slots of the group); flavour: the launch
+// flavour of the scene (pmcLaunchFlavourOf), or the generic one (PMC_LAUNCH_KIN alone where some source moves)
+extern "C" hipError_t pmcLaunchLaunch(int slot, int flavour, int slotBase, int numSlots, int group, uint64_t first, uint64_t count, uint64_t seed, int initial,
                                       int maxBlocks, size_t ldsBytes, const StatLogArgs* statLog, hipStream_t stream)
 {
     const StatLogArgs none = {nullptr, nullptr, 0ull, 0, nullptr, nullptr, nullptr};
     const int grid = std::max(1, std::min((numSlots + 255) / 256, maxBlocks));
-    hipLaunchKernelGGL(kin ? launchKinKernel : launchKernel, dim3(grid), dim3(256), ldsBytes, stream, slot, slotBase, numSlots, group, first, count, seed, initial,
+    if (flavour < 0 || flavour >= PMC_LAUNCH_FLAVOURS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(launchKernels[flavour].kernel, dim3(grid), dim3(256), ldsBytes, stream, slot, slotBase, numSlots, group, first, count, seed, initial,
                        statLog ? *statLog : none);
     return hipGetLastError();
 }

@@ -198,6 +198,7 @@ namespace
         unsigned long long rfLogPerSlot, statLogEntries;
         bool poolGrows;  // the statistics pool grows when a group could run out of blocks
         int statInstruments;
+        int launchFlavour;  // the launch kernel of the scene (pmc_device.h PMC_LAUNCH_*)
         // launch geometry
         int launchBlocks, cycleBlocks, transitionBlocks;
         int voroPropGrid, voroPeelGrid, voroPropSegments;
@@ -243,6 +244,14 @@ namespace
             ctx->sceneDirty = false;
         }
         return PMC_OK;
+    }
+
+    // the launch kernel of the context's scene: the flavour its sources select, or (PMC_LAUNCH_GENERIC: tests, A/B runs) the generic kernel
+    int launchFlavour(const pmc_ctx* ctx)
+    {
+        const DevScene& D = ctx->dev;
+        if (pmcTune("PMC_LAUNCH_GENERIC") != nullptr) return D.kin ? PMC_LAUNCH_KIN : 0;
+        return pmcLaunchFlavourOf(D.src, D.num_sources, D.kin);
     }
 
     SegmentPlan planSegment(const pmc_ctx* ctx, int numSlots, uint64_t first, uint64_t count, uint64_t seed)
@@ -348,6 +357,7 @@ namespace
         P.statLogEntries = std::max<unsigned long long>((entries + PMC_RF_LOG_CHUNK - 1) / PMC_RF_LOG_CHUNK, 1ull) * PMC_RF_LOG_CHUNK;
         for (int i = 0; i < D.num_instruments; ++i) P.statInstruments += D.inst[i].record_stats ? 1 : 0;
         P.poolGrows = D.any_stats && ctx->statPoolBlocks > 0 && pmcTune("PMC_STAT_POOL_NO_GROWTH") == nullptr;
+        P.launchFlavour = launchFlavour(ctx);
         P.launchBlocks = ctx->numCU * 4;  // persistent launch workgroups, as the transition kernel's
         if (const char* env = pmcTune("PMC_LAUNCH_BLOCKS_PER_CU")) P.launchBlocks = ctx->numCU * std::max(1, atoi(env));
         P.cycleBlocks = ctx->numCU * 4;  // persistent cycle start workgroups (grid tables staged once per workgroup)
@@ -754,7 +764,8 @@ namespace
         {
             if (g > 0) HIP_TRY(hipStreamWaitEvent(sg, ctx->evStart, 0));
             HIP_TRY(hipEventRecord(ctx->evB[g], sg));
-            HIP_TRY(pmcLaunchLaunch(ctx->slot, ctx->dev.kin, P.base[g], P.size[g], g, P.first, P.count, P.seed, 1, (P.size[g] + 255) / 256, ctx->launchLds, nullptr, sg));
+            // (the same persistent workgroups as every later generation: every slot takes a history)
+            HIP_TRY(pmcLaunchLaunch(ctx->slot, P.launchFlavour, P.base[g], P.size[g], g, P.first, P.count, P.seed, 1, P.launchBlocks, ctx->launchLds, nullptr, sg));
             return enqueueCycleStart(ctx, P, S, g, initial, listIn, listLen);
         }
         if (P.poolGrows)
@@ -791,7 +802,7 @@ namespace
         const StatLogArgs statLog = statLogOf(ctx, P, g);
         HIP_TRY(pmcLaunchTransition(ctx->slot, (ctx->dev.any_dipole ? 1 : 0) | (ctx->dev.kin ? 2 : 0), P.base[g], P.size[g], g, P.seed, listIn, listLen, P.transitionBlocks, ctx->transitionLds, &statLog, P.count, sg));
         if (!listIn)
-            HIP_TRY(pmcLaunchLaunch(ctx->slot, ctx->dev.kin, P.base[g], P.size[g], g, P.first, P.count, P.seed, 0, P.launchBlocks, ctx->launchLds, &statLog, sg));
+            HIP_TRY(pmcLaunchLaunch(ctx->slot, P.launchFlavour, P.base[g], P.size[g], g, P.first, P.count, P.seed, 0, P.launchBlocks, ctx->launchLds, &statLog, sg));
         return enqueueCycleStart(ctx, P, S, g, initial, listIn, listLen);
     }
 
@@ -930,6 +941,13 @@ namespace
 }
 
 extern "C" {
+
+int pmc_launch_flavour(pmc_ctx* ctx, int32_t* flavour)
+{
+    if (!ctx || !flavour) return fail(PMC_ERR_INVALID, "pmc_launch_flavour: invalid argument");
+    *flavour = launchFlavour(ctx);
+    return PMC_OK;
+}
 
 int pmc_run_primary(pmc_ctx* ctx, uint64_t first, uint64_t count, uint64_t seed)
 {

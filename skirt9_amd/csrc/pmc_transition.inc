@@ -1324,14 +1324,24 @@
     // KIN (a scene with a moving source): the packet's wavelength is Doppler-shifted by the source's velocity along the launch direction
     // (PhotonPacket.cpp:18-40: the weight W = L lambda0 keeps the sampled wavelength), and so is, by the velocity along its line of sight,
     // that of the emission peel-off packet towards every observer (:66-85): SlotArrays::obsLambda, obsExt, obsEll
-    template<bool KIN = false>
+    // F: the launch flavour (pmc_device.h PMC_LAUNCH_*, pmcLaunchFlavourOf) -- what the scene fixes of the steps below is a constant here, and the
+    // code of every other wavelength mode, source geometry and angular distribution is not in the kernel; the deviates drawn, and their order,
+    // are those of the generic form (F = 0, or PMC_LAUNCH_KIN alone), which asks the source for each of them
+    template<int F = 0>
     __device__ __forceinline__ bool launchHistory(const DevScene& S, const DustLds& L, Counters& cnt, int slot, uint64_t history, uint64_t seed)
     {
+        constexpr bool KIN = (F & PMC_LAUNCH_KIN) != 0;
+        constexpr bool OLIGO = (F & PMC_LAUNCH_OLIGO) != 0;
+        constexpr bool ISOTROPIC = (F & PMC_LAUNCH_ISOTROPIC) != 0;
+        constexpr int GEOM = F >> PMC_LAUNCH_GEOM_SHIFT;
         const SlotArrays& A = S.slots;
-        // SourceSystem::launch (SourceSystem.cpp:100-107): the source that owns this history index
+        // SourceSystem::launch (SourceSystem.cpp:100-107): the source that owns this history index (the Sersic flavour: the only one)
         int si = 0;
-        while (si + 1 < S.num_sources && history >= S.src_first[si + 1]) ++si;
+        if (GEOM != PMC_LAUNCH_GEOM_SERSIC)
+            while (si + 1 < S.num_sources && history >= S.src_first[si + 1]) ++si;
         const DevSource& Q = S.src[si];
+        const int sourceKind = GEOM == PMC_LAUNCH_GEOM_SERSIC ? PMC_SOURCE_SERSIC : GEOM == PMC_LAUNCH_GEOM_POINT ? PMC_SOURCE_POINT : Q.source_kind;
+        const int angularKind = ISOTROPIC ? PMC_ANGULAR_ISOTROPIC : Q.angular_kind;
         Rng rng;
         rng.h0 = (uint32_t)history;
         rng.h1 = (uint32_t)(history >> 32);
@@ -1339,7 +1349,7 @@
         rng.have = 0;
         rng.spare = 0.;
         double lambda, w;
-        if (Q.lambda_mode == PMC_LAMBDA_OLIGO)
+        if (OLIGO || Q.lambda_mode == PMC_LAMBDA_OLIGO)
         {
             (void)rngUniform(rng, seed);  // the `uniform() > xi` test of NormalizedSource::launch with xi = 1
             int index = (int)(rngUniform(rng, seed) * Q.num_oligo);
@@ -1392,17 +1402,18 @@
             }
         }
         double rx, ry, rz;
-        if (Q.source_kind == PMC_SOURCE_POINT)
+        if (sourceKind == PMC_SOURCE_POINT)
         {
             rx = Q.src_pos[0];
             ry = Q.src_pos[1];
             rz = Q.src_pos[2];
         }
-        else if (Q.source_kind == PMC_SOURCE_SERSIC)
+        else if (sourceKind == PMC_SOURCE_SERSIC)
         {
             // (the tables of a single source are staged in LDS)
-            const double* sv = S.num_sources == 1 ? L.src : Q.sersic_s;
-            const double* Mv = S.num_sources == 1 ? L.src + Q.sersic_n : Q.sersic_M;
+            const bool staged = GEOM == PMC_LAUNCH_GEOM_SERSIC || S.num_sources == 1;
+            const double* sv = staged ? L.src : Q.sersic_s;
+            const double* Mv = staged ? L.src + Q.sersic_n : Q.sersic_M;
             double X = rngUniform(rng, seed);
             int n = Q.sersic_n;
             int i = locate(Mv, n, X);
@@ -1420,7 +1431,7 @@
             ry = dy * radius;
             rz = dz * radius;
         }
-        else if (Q.source_kind == PMC_SOURCE_EXP_DISK)
+        else if (sourceKind == PMC_SOURCE_EXP_DISK)
         {
             // ExpDiskGeometry::randomCylRadius / randomZ with SepAxGeometry::generatePosition
             const double hR = Q.src_box[0], hz = Q.src_box[1], Rmin = Q.src_box[2], Rmax = Q.src_box[3], zmax = Q.src_box[4];
@@ -1443,7 +1454,7 @@
             ry = R * sinphi;
             rz = z;
         }
-        else if (Q.source_kind == PMC_SOURCE_PLUMMER)
+        else if (sourceKind == PMC_SOURCE_PLUMMER)
         {
             const double t = pow(rngUniform(rng, seed), 1.0 / 3.0);
             const double radius = Q.src_box[0] * t / sqrt((1.0 - t) * (1.0 + t));
@@ -1463,21 +1474,21 @@
             rz = Q.src_box[2] + z * (Q.src_box[5] - Q.src_box[2]);
         }
         // SpheroidalGeometryDecorator::generatePosition (SpheroidalGeometryDecorator.cpp:19-25)
-        if ((Q.source_kind == PMC_SOURCE_SERSIC || Q.source_kind == PMC_SOURCE_PLUMMER) && Q.src_box[5] != 0.) rz = Q.src_box[5] * rz;
+        if ((sourceKind == PMC_SOURCE_SERSIC || sourceKind == PMC_SOURCE_PLUMMER) && Q.src_box[5] != 0.) rz = Q.src_box[5] * rz;
         // OffsetGeometryDecorator::generatePosition (OffsetGeometryDecorator.cpp:33-39)
-        if (Q.source_kind != PMC_SOURCE_POINT && (Q.src_pos[0] != 0. || Q.src_pos[1] != 0. || Q.src_pos[2] != 0.))
+        if (sourceKind != PMC_SOURCE_POINT && (Q.src_pos[0] != 0. || Q.src_pos[1] != 0. || Q.src_pos[2] != 0.))
         {
             rx = rx + Q.src_pos[0];
             ry = ry + Q.src_pos[1];
             rz = rz + Q.src_pos[2];
         }
         double kx, ky, kz;
-        if (Q.angular_kind != PMC_ANGULAR_ISOTROPIC)
+        if (angularKind != PMC_ANGULAR_ISOTROPIC)
         {
             // AxAngularDistribution::generateDirection (AxAngularDistribution.cpp:36-39) with the inclination cosine of
             // LaserAngularDistribution.cpp:20-23, ConicalAngularDistribution.cpp:29-36, NetzerAngularDistribution.cpp:42-45 (Random::cdfLinLin)
             double costheta = 1.;
-            if (Q.angular_kind == PMC_ANGULAR_CONICAL)
+            if (angularKind == PMC_ANGULAR_CONICAL)
             {
                 const double X = rngUniform(rng, seed);
                 if (X < 0.5)
@@ -1485,7 +1496,7 @@
                 else
                     costheta = 1.0 - 2.0 * Q.angular_cos_delta - 2.0 * X * (1.0 - Q.angular_cos_delta);
             }
-            else if (Q.angular_kind == PMC_ANGULAR_NETZER)
+            else if (angularKind == PMC_ANGULAR_NETZER)
             {
                 const double X = rngUniform(rng, seed);
                 const int i = locateClip(S.netzer_X, PMC_NETZER_POINTS + 1, X);
@@ -1589,7 +1600,7 @@
         // the photon cycle starts with the emission peel-offs and the first propagation walk
         A.Lthreshold[slot] = (W / lambda) / S.min_weight_reduction;  // MonteCarloSimulation.cpp:566
         PMC_T_STAMP(4);
-        announceCycle<false, KIN>(S, slot, seed, rng, rx, ry, rz, kx, ky, kz, W, asym, 0, nullptr, nullptr, Q.angular_kind != PMC_ANGULAR_ISOTROPIC ? &Q : nullptr);
+        announceCycle<false, KIN>(S, slot, seed, rng, rx, ry, rz, kx, ky, kz, W, asym, 0, nullptr, nullptr, angularKind != PMC_ANGULAR_ISOTROPIC ? &Q : nullptr);
         storeRng(A, slot, rng);
         return true;
     }
@@ -1841,8 +1852,9 @@
     //  lanes whose history has ended (first generation: all) flush the per-history statistics, take up the next history --
     //  its index follows from the scanned counts -- launch it and start its first cycle
     // ================================================================================================
-    //  KIN: the flavour of a scene with a moving source (launchKinKernel)
-    template<bool KIN>
+    //  F: the launch flavour (pmc_device.h PMC_LAUNCH_*: a moving source, and what the scene fixes of SourceSystem::launch); the statistics
+    //  flush, the first cycle and the workgroup's epilogue are the same code in every flavour
+    template<int F>
     __device__ __forceinline__ void launchBody(const int sceneSlot, const int slotBase, const int numSlots, const int group, const uint64_t first,
                                                const uint64_t count, const uint64_t seed, const int initial, const StatLogArgs& statLog)
     {
@@ -1851,6 +1863,7 @@
         const int tid = threadIdx.x;
         const int lane = tid & 63;
         BlockLds B;
+        constexpr bool KIN = (F & PMC_LAUNCH_KIN) != 0;
         Counters cnt = {0, 0, 0, 0, 0};
         StatLogWave logWave = statLogBegin(statLog);
         PMC_T_PROF_BEGIN;
@@ -1862,13 +1875,13 @@
         // (the first history index this group may not take in this generation: endedScanKernel)
         const unsigned long long hlimit = initial ? count : min(count, (unsigned long long)S.counters[PMC_CTR_HLIMIT(group)]);
         uint32_t liveCount = 0;
-        // Every WAVE serves its own run of slots -- 64 in the first generation (all slots launch), otherwise 256, of which
-        // about a quarter have ended -- and compacts the ended ones into its own list in LDS: what follows (statistics flush,
-        // source sampling, the start of a cycle) is long divergent code that then runs with full waves, in slot order, and no
-        // wave waits for another one (with one list per workgroup the first wave did the work of a tile while the other
-        // three sat at the barrier: half of the kernel's wave cycles).
+        // Persistent workgroups (the tables are staged once).  Every WAVE serves runs of 256 slots.  In the first generation every slot
+        // of the run takes a history; afterwards about a quarter have ended, and the wave compacts them into its own list in LDS: what
+        // follows (statistics flush, source sampling, the start of a cycle) is long divergent code that then runs with full waves, in
+        // slot order, and no wave waits for another one (with one list per workgroup the first wave did the work of a tile while the
+        // other three sat at the barrier: half of the kernel's wave cycles).
         const int wv = tid >> 6;
-        const int perWave = initial ? 64 : 256;
+        const int perWave = 256;
         const int span = perWave * ((int)blockDim.x >> 6);
         const int slotEnd = slotBase + numSlots;
         int* const myList = B.sortSlot + wv * 256;
@@ -1879,7 +1892,7 @@
             int n = 0;
             unsigned long long h0 = 0;
             if (initial)
-                n = max(0, min(64, slotEnd - wbase));
+                n = max(0, min(perWave, slotEnd - wbase));
             else if (wbase < slotEnd)
             {
                 int md[4];
@@ -1947,7 +1960,7 @@
                         else
                         {
                             cnt.histories += 1;
-                            if (launchHistory<KIN>(S, L, cnt, slot, first + h, seed)) event = EV_TASK;
+                            if (launchHistory<F>(S, L, cnt, slot, first + h, seed)) event = EV_TASK;
                         }
                     }
                 }
@@ -1967,17 +1980,12 @@
         PMC_T_PROF_END(200);
         addCounters(S, cnt, lane);
     }
+    template<int F>
     __global__ __launch_bounds__(256, PMC_LAUNCH_MIN_WAVES) void launchKernel(const int sceneSlot, const int slotBase, const int numSlots, const int group,
                                                         const uint64_t first, const uint64_t count, const uint64_t seed, const int initial,
                                                         const StatLogArgs statLog)
     {
-        launchBody<false>(sceneSlot, slotBase, numSlots, group, first, count, seed, initial, statLog);
-    }
-    __global__ __launch_bounds__(256, PMC_LAUNCH_MIN_WAVES) void launchKinKernel(const int sceneSlot, const int slotBase, const int numSlots, const int group,
-                                                        const uint64_t first, const uint64_t count, const uint64_t seed, const int initial,
-                                                        const StatLogArgs statLog)
-    {
-        launchBody<true>(sceneSlot, slotBase, numSlots, group, first, count, seed, initial, statLog);
+        launchBody<F>(sceneSlot, slotBase, numSlots, group, first, count, seed, initial, statLog);
     }
 
     // ================================================================================================

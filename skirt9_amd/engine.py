@@ -23,7 +23,8 @@ SYMBOLS = ["pmc_abi_version", "pmc_build_info", "pmc_last_error", "pmc_frame_lay
            "pmc_download_radiation_field", "pmc_clear_radiation_field", "pmc_bind_radiation_field", "pmc_sampler_create",
            "pmc_sampler_density", "pmc_sampler_destroy", "pmc_history_range", "pmc_comm_init_all", "pmc_comm_unique_id",
            "pmc_comm_init_rank", "pmc_comm_size", "pmc_comm_destroy", "pmc_reduce_frames", "pmc_allreduce_radiation_field",
-           "pmc_debug_tables", "pmc_tuning_set", "pmc_tuning_clear", "pmc_tune_dipole_cosines", "pmc_tune_source_velocities"]
+           "pmc_debug_tables", "pmc_tuning_set", "pmc_tuning_clear", "pmc_tune_dipole_cosines", "pmc_tune_source_velocities",
+           "pmc_launch_flavour"]
 
 _lib = None
 
@@ -295,6 +296,13 @@ class Engine:
         lib().pmc_debug_tables.argtypes = [C.c_void_p, C.POINTER(DebugTables)]
         _check(lib().pmc_debug_tables(self._h, C.byref(t)))
         return t
+
+    def launch_flavour(self):
+        """the launch kernel the next run_primary uses (include/pmc_tuning.h pmc_launch_flavour): 0 or 1 is the generic kernel"""
+        f = C.c_int32(-1)
+        lib().pmc_launch_flavour.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        _check(lib().pmc_launch_flavour(self._h, C.byref(f)))
+        return int(f.value)
 
     def reduce_frames(self, comm_handle, root=0):
         """end of a segment on several devices: ONE ncclReduce (f64, sum) of the detector arrays onto `root`
