@@ -1,11 +1,13 @@
-// pmc_context.h -- what the translation units of the host side of libpmc.so share: the context behind a pmc_ctx handle, the error text of the
-// calling thread, the launchers of pmc_kernels.hip.  pmc_api.hip holds the ABI entry points (scene upload: pmc_create), pmc_tables.hip the
-// table builders (octree flattening, Voronoi run / cone / observer tables), pmc_run.hip the generation loop (pmc_run_primary), pmc_comm.hip the
-// RCCL calls, pmc_tuning.hip the switch table of include/pmc_tuning.h, pmc_temperature.hip the dust temperatures (kernel and entry point).
+// pmc_context.h -- what the translation units of the host side of libpmc.so share: the context behind a pmc_ctx handle (as a TableSink it is
+// where the tables of a scene go: device memory), the device buffers of one call, the launchers of pmc_kernels.hip.  pmc_api.hip holds the ABI
+// entry points (pmc_create: the stages of pmc_scene_build.h between the context's resources and the device-side configuration), pmc_tables.h
+// the grid tables (octree flattening, binary tree, Voronoi run / cone / observer tables) and the error text of the calling thread, both plain
+// host code; pmc_run.hip the generation loop (pmc_run_primary), pmc_comm.hip the RCCL calls, pmc_tuning.hip the switch table of
+// include/pmc_tuning.h, pmc_temperature.hip the dust temperatures (kernel and entry point).
 #ifndef PMC_CONTEXT_H
 #define PMC_CONTEXT_H
 
-#include "pmc_device.h"
+#include "pmc_tables.h"
 #include "../../include/pmc_layout.h"
 #include "../../include/pmc_tuning.h"
 #include <hip/hip_runtime.h>
@@ -72,15 +74,8 @@ extern "C" int pmcProbeWorkWords(void);
 extern "C" hipError_t pmcLaunchIntegrate(int slot, int gridKind, int wide, int averaged, const double* origins, const double* directions, const double* q,
                                          double* sums, unsigned long long numRays, unsigned long long* work, int grid, size_t ldsBytes, hipStream_t stream);
 
-// error text of the calling thread (pmc_last_error); defined in pmc_api.hip
-void pmcSetError(const std::string& message);
 namespace
 {
-    inline int fail(int code, const std::string& message)
-    {
-        pmcSetError(message);
-        return code;
-    }
     inline int hipFail(hipError_t e, const char* what)
     {
         return fail(PMC_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
@@ -104,7 +99,7 @@ struct GroupReadback
     unsigned long long statFreeBlocks;  // free blocks of the group's share of the statistics pool
 };
 
-struct pmc_ctx
+struct pmc_ctx final : TableSink
 {
     int device{0};
     int slot{-1};
@@ -175,18 +170,30 @@ struct pmc_ctx
     uint32_t* statWaveFill[PMC_MAX_GROUPS]{};
     uint32_t* statChunkFill[PMC_MAX_GROUPS]{};
 
-    template<typename T> int upload(const T* host, size_t count, const T** out)
+    // TableSink (upload<T>, the tables of pmc_create): device memory that lives as long as the context
+    int uploadBytes(const void* host, size_t elementBytes, size_t count, const void** out) override
     {
-        *out = nullptr;
-        if (!count) return PMC_OK;
         void* d = nullptr;
-        hipError_t e = hipMalloc(&d, count * sizeof(T));
+        hipError_t e = hipMalloc(&d, count * elementBytes);
         if (e != hipSuccess) return hipFail(e, "hipMalloc");
         allocations.push_back(d);
-        e = hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice);
+        e = hipMemcpy(d, host, count * elementBytes, hipMemcpyHostToDevice);
         if (e != hipSuccess) return hipFail(e, "hipMemcpy");
-        *out = static_cast<const T*>(d);
+        *out = d;
         return PMC_OK;
+    }
+    int allocateBytes(size_t bytes, void** out, bool zero) override
+    {
+        unsigned char* d = nullptr;
+        const int rc = allocate(bytes, &d, zero);
+        *out = d;
+        return rc;
+    }
+    // (a device that does not say: plenty)
+    size_t freeBytes() override
+    {
+        size_t freeNow = 0, total = 0;
+        return hipMemGetInfo(&freeNow, &total) == hipSuccess ? freeNow : ~size_t(0);
     }
     // (planning pass of allocateSlots: the requests are only added up)
     bool planning{false};
@@ -232,12 +239,29 @@ struct pmc_ctx
     }
 };
 
-// pmc_tables.hip: the device tables of an octree (flattened tree, links, coordinate table; devToCell = device cell index -> caller's cell index)
-// and of a Voronoi grid (cell records, neighbour entries, cone masks, tables of runs per cone and per observer)
-int pmcUploadOctreeGrid(pmc_ctx* ctx, const pmc_scene* scene, const pmc_medium& med, std::vector<int32_t>& devToCell);
-int pmcUploadVoronoiGrid(pmc_ctx* ctx, const pmc_scene* scene, const pmc_medium& med);
-// ... and of a binary tree, or of an octree that is to run through the binary tree's tables and kernels (sets DevScene::grid_kind to PMC_GRID_BINTREE)
-int pmcUploadBinTreeGrid(pmc_ctx* ctx, const pmc_scene* scene, const pmc_medium& med, std::vector<int32_t>& devToCell);
+// device buffers of one call (pmc_trace_ray, pmc_integrate_rays, pmc_dust_temperatures): freed when the call returns, whichever way
+struct CallBuffers
+{
+    std::vector<void*> owned;
+    ~CallBuffers()
+    {
+        for (void* d : owned) hipFree(d);
+    }
+    // room for `count` elements, filled from `host` if there is one
+    template<typename T> hipError_t get(size_t count, T** out, const T* host = nullptr)
+    {
+        void* d = nullptr;
+        hipError_t e = hipMalloc(&d, std::max(count, size_t(1)) * sizeof(T));
+        if (e != hipSuccess) return e;
+        owned.push_back(d);
+        *out = static_cast<T*>(d);
+        if (host) return hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice);
+        // (test aid, as in pmc_ctx::allocate: what the call does not write shows)
+        if (pmcTune("PMC_POISON_ALLOCATIONS")) return hipMemset(d, 0xA5, std::max(count, size_t(1)) * sizeof(T));
+        return hipSuccess;
+    }
+};
+
 // pmc_run.hip: the pool of packet slots
 int pmcAllocateSlots(pmc_ctx* ctx, int64_t n);
 

@@ -331,7 +331,7 @@ struct DevScene
     const int32_t* nbr_start;    // [6*num_cells + 1]
     const int32_t* nbr_list;     // leaf cell indices
     int32_t num_cells;
-    // octree: the device tables number the cells in their own order (pmc_api.hip buildTree: depth-first order of the
+    // octree: the device tables number the cells in their own order (pmc_tables.h buildTree: depth-first order of the
     // tree); cell_ext[device index] = the caller's cell index m, cell_slots = entries per device table
     const int32_t* cell_ext;
     int32_t cell_slots;

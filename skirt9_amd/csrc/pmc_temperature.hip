@@ -138,28 +138,6 @@ namespace
             }
         }
     }
-
-    // device buffers of one call: freed when the call returns, whichever way
-    struct CallBuffers
-    {
-        std::vector<void*> owned;
-        ~CallBuffers()
-        {
-            for (void* d : owned) hipFree(d);
-        }
-        hipError_t get(size_t count, double** out, const double* host)
-        {
-            void* d = nullptr;
-            hipError_t e = hipMalloc(&d, std::max(count, size_t(1)) * sizeof(double));
-            if (e != hipSuccess) return e;
-            owned.push_back(d);
-            *out = static_cast<double*>(d);
-            if (host) return hipMemcpy(d, host, count * sizeof(double), hipMemcpyHostToDevice);
-            // (test aid, as in pmc_ctx::allocate: what the kernel does not write shows)
-            if (pmcTune("PMC_POISON_ALLOCATIONS")) return hipMemset(d, 0xA5, std::max(count, size_t(1)) * sizeof(double));
-            return hipSuccess;
-        }
-    };
 }
 
 extern "C" {
@@ -196,7 +174,7 @@ int pmc_dust_temperatures(pmc_ctx* ctx, const pmc_dust_heating* T, double* out)
     HIP_TRY(buffers.get(size_t(NT), &dTemp, T->temperature));
     HIP_TRY(buffers.get(numCells, &dFactor, T->cell_factor));
     HIP_TRY(buffers.get(size_t(H) * numCells, &dRho, T->mass_density));
-    HIP_TRY(buffers.get(size_t(H + 1) * numCells, &dOut, nullptr));
+    HIP_TRY(buffers.get(size_t(H + 1) * numCells, &dOut));
     A.rf = ctx->dev.rf, A.width = dWidth, A.sigma = dSigma, A.planckabs = dPlanck, A.temperature = dTemp, A.cellFactor = dFactor, A.rho = dRho, A.out = dOut;
     A.numCells = T->num_cells, A.numLambda = L, A.numT = NT, A.H = H;
     hipEvent_t evA = nullptr, evB = nullptr;
