@@ -39,9 +39,9 @@ skh_simulation* skh_load(const char* ski_path)
 {
     try
     {
-        auto h = new skh_simulation();
-        h->sim = skh::Simulation::fromFile(ski_path);
-        return h;
+        // (the simulation first: a refused ski file leaves no handle behind)
+        auto sim = skh::Simulation::fromFile(ski_path);
+        return new skh_simulation{std::move(sim)};
     }
     catch (const std::exception& e)
     {

@@ -12,6 +12,8 @@
 
 namespace skh
 {
+    struct Reader;  // attribute access for the readers of the ski file (ski_reader.cpp)
+
     class Simulation
     {
     public:
@@ -136,9 +138,53 @@ namespace skh
 
     private:
         Simulation() {}
+        struct ProbeModel;
+        struct SourceTables;
+        struct WavelengthRange
+        {
+            double min, max;
+        };
+        struct SimulationWavelengths
+        {
+            WavelengthRange range;             // with the margins for kinematics and redshift
+            std::vector<double> wavelengths;   // the characteristic wavelengths of the simulation, ascending
+        };
+
+        // ski_reader.cpp: the systems of the ski file in document order; what reads a single element without the state of the simulation
+        // is a free function there
         void parse(const XmlElement& root);
-        void buildScene();
-        void flattenSourceGeometry(const SourceModel& source, pmc_source& flat) const;
+        void readUnits(const XmlElement& sim, Reader& rd);
+        void readMode(const XmlElement& sim, Reader& rd);
+        void readRandom(const XmlElement& sim, const Reader& rd);
+        void readCosmology(const XmlElement& sim, const Reader& rd);
+        void readSourceSystem(const XmlElement& sim, const Reader& rd);
+        const XmlElement& readMediumSystem(const XmlElement& sim, const Reader& rd);
+        void readRadiationFieldOptions(const XmlElement& mediumSystem, const Reader& rd);
+        void readInstrumentSystem(const XmlElement& sim, const Reader& rd);
+        void readProbeSystem(const XmlElement& sim, const Reader& rd);
+        static ProbeModel readDustAbsorptionProbe(const XmlElement& probe, const Reader& rd);
+        static ProbeModel readFormProbe(const XmlElement& probe, const Reader& rd);
+        static std::string readRadiationFieldProbe(const XmlElement& probe, const Reader& rd);
+
+        // simulation.cpp: the stages of setup(), in order
+        void chooseWavelengthGrids();
+        SimulationWavelengths simulationWavelengths() const;
+        void setupMedia(const SimulationWavelengths& simulation);
+        void setupGrid();
+        void sampleDensities();
+        void flattenScene();
+        static SourceTables buildSourceTables(SourceModel& source, WavelengthRange sourceRange, const WavelengthGrid* oligoGrid, pmc_source& flat);
+        void setLaunchWeights();
+        void flattenSources();
+        // and what they share
+        const WavelengthGrid* defaultWavelengthGrid() const { return _oligo ? _oligoGrid.get() : _defaultGrid.get(); }
+        const WavelengthGrid* gridInEffect(const WavelengthGrid* own) const;
+        WavelengthRange sourceWavelengthRange() const;
+        void flattenGrid();
+        void flattenMedia();
+        pmc_instrument flattenInstrument(const InstrumentModel& instrument) const;
+        void flattenRadiationField();
+        static void flattenSourceGeometry(const SourceModel& source, pmc_source& flat);
 
         std::string _prefix;
         std::string _inputPath{"."};
@@ -208,6 +254,9 @@ namespace skh
         pmc_scene _scene{};
         pmc_scene_ext _sceneExt{};
     };
+
+    // the refusal of a ski file: "ski: <what> is not supported on the MI355X primary-emission path"
+    [[noreturn]] void unsupported(const std::string& what);
 
     // FITS primary image (BITPIX -32) + ASCII table of the third axis, byte-compatible with what the reference
     // produces through CFITSIO (FITSInOut.cpp:127-215)
