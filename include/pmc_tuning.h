@@ -68,6 +68,58 @@ int pmc_tune_dipole_cosines(pmc_ctx* ctx, const double* u, int64_t n, double* co
    source at rest gives zeros. */
 int pmc_tune_source_velocities(pmc_ctx* ctx, int32_t source, const double* r, int64_t n, double* v_out);
 
+/* ---- Test aids: the counting sort and the reduce kernels behind the radiation-field log and the statistics log (skirt9_amd/csrc/pmc_walk_tree.inc:
+   rfHistKernel, rfScanKernel, rfScatterKernel, rfReduceKernel, statReduceKernel), run on logs that the HOST supplies instead of the walk and launch
+   kernels.  A log is n (key, value) pairs in whole chunks of `chunk` entries: n > 0, a multiple of `chunk`, at most `max_entries`.  Every aid checks
+   its arguments and returns PMC_ERR_INVALID with a message instead of launching; it allocates the device buffers it needs and frees them, works on
+   the context's stream, returns when its results are on the host, and leaves the context as pmc_run_primary expects it.  Any 32-bit value is a valid
+   key: the kernels drop the keys beyond the partitions, and the reduce kernels those beyond the table.  No reference counterpart. */
+
+/* The log geometry of this context and the constants the kernels are built with (every member an int64_t):
+     cell_slots, rf_num_lambda   cells of the device numbering (padding slots included: pmc_tune_cell_numbering), bins of the stored field
+     rf_keys, rf_parts           keys of the radiation-field log (cell_slots * rf_num_lambda on a tree grid) and its partitions of 2^rf_bucket_bits keys
+     rf_logged                   1: the next pmc_run_primary of this context sends the field's contributions through the log (a stored field on an
+                                 octree, at most max_parts partitions, no switch PMC_RF_ATOMICS), 0: it adds them atomically
+     stat_records, stat_parts    records of the statistics accumulator and the partitions of 2^stat_bucket_bits records of its log
+     stat_logged                 as rf_logged, for the statistics (switch PMC_STAT_ATOMICS)
+     chunk                       entries per chunk of a log = per tile of the counting sort
+     rf_bucket_bits, stat_bucket_bits
+     scan_threads, sort_block    lanes of rfScanKernel and rfScatterKernel: with more partitions than lanes a lane takes several of them
+     max_parts                   partitions the sort's LDS histograms hold
+     reduce_span                 entries of the partitioned log per workgroup of the reduce kernels
+     rf_short_run, stat_short_run   a run of a partition inside a span with fewer entries is added entry by entry instead of through LDS
+     max_entries                 the largest n the aids below accept (2^24) */
+typedef struct pmc_log_geometry_values
+{
+    int64_t cell_slots, rf_num_lambda, rf_keys, rf_parts, rf_logged;
+    int64_t stat_records, stat_parts, stat_logged;
+    int64_t chunk, rf_bucket_bits, stat_bucket_bits, scan_threads, sort_block, max_parts, reduce_span, rf_short_run, stat_short_run, max_entries;
+} pmc_log_geometry_values;
+int pmc_tune_log_geometry(pmc_ctx* ctx, pmc_log_geometry_values* out);
+
+/* The counting sort alone (the three kernels in front of a reduce), on num_parts partitions of the caller's choice in [1, max_parts]; no table of the
+   scene is involved.  stat = 0: partitions of 2^rf_bucket_bits keys, stat = 1: of 2^stat_bucket_bits.  fills: NULL, or per chunk the entries of it
+   that are there (0 .. chunk; what lies behind them is never used).  The live entries are those that are there and whose partition, key >> bits, is
+   below num_parts.  Out: start[num_parts + 1], the first place of every partition in the partitioned log (start[num_parts] = live entries), and
+   sorted_keys[n], sorted_vals[n], of which the first start[num_parts] places hold the live entries by partition, in any order inside one; the
+   places behind them hold zeros. */
+int pmc_tune_log_partition(pmc_ctx* ctx, int32_t stat, int32_t num_parts, const uint32_t* keys, const double* vals, const uint32_t* fills, int64_t n,
+                           uint32_t* sorted_keys, double* sorted_vals, uint64_t* start);
+
+/* The radiation-field log as the end of a generation flushes it, with the context's own rf_parts: vals[i] is added to the context's radiation field table
+   (its own or the bound one; see pmc_download_radiation_field) at [cell_ext[key / rf_num_lambda] * rf_num_lambda + key % rf_num_lambda], for the keys
+   below rf_keys whose cell is no padding slot.  Adds to what the table holds.  PMC_ERR_INVALID unless rf_logged. */
+int pmc_tune_rf_log_flush(pmc_ctx* ctx, const uint32_t* keys, const double* vals, int64_t n);
+
+/* The statistics log as the end of a segment flushes it, with the context's own stat_parts: every entry that is there (fills as above, or NULL) with a
+   key below stat_records adds 1, w, w^2, w^3, w^4 (w = its value, the powers formed as ((w w) w) w) to its record of the accumulator, which is copied
+   to acc_out[stat_records][5] and cleared again: the frames are not touched.  PMC_ERR_INVALID unless stat_logged. */
+int pmc_tune_stat_log_flush(pmc_ctx* ctx, const uint32_t* keys, const double* vals, const uint32_t* fills, int64_t n, double* acc_out);
+
+/* ext_out[cell_slots]: the caller's cell index of every cell of the device numbering of a tree grid, -1 for a padding slot that holds no cell.
+   PMC_ERR_INVALID on a grid without a device numbering. */
+int pmc_tune_cell_numbering(pmc_ctx* ctx, int32_t* ext_out);
+
 #ifdef __cplusplus
 }
 #endif

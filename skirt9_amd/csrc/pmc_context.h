@@ -2,7 +2,7 @@
 // where the tables of a scene go: device memory), the device buffers of one call, the launchers of pmc_kernels.hip.  pmc_api.hip holds the ABI
 // entry points (pmc_create: the stages of pmc_scene_build.h between the context's resources and the device-side configuration), pmc_tables.h
 // the grid tables (octree flattening, binary tree, Voronoi run / cone / observer tables) and the error text of the calling thread, both plain
-// host code; pmc_run.hip the generation loop (pmc_run_primary), pmc_comm.hip the RCCL calls, pmc_tuning.hip the switch table of
+// host code; pmc_run.hip the generation loop (pmc_run_primary), pmc_comm.hip the RCCL calls, pmc_tuning.hip the switch table and the test aids of
 // include/pmc_tuning.h, pmc_temperature.hip the dust temperatures (kernel and entry point).
 #ifndef PMC_CONTEXT_H
 #define PMC_CONTEXT_H
@@ -65,6 +65,11 @@ extern "C" hipError_t pmcLaunchLaunch(int slot, int flavour, int slotBase, int n
 extern "C" hipError_t pmcLaunchStatFlush(int slot, const uint32_t* keys, const double* vals, uint32_t* sortedKeys, double* sortedVals, unsigned long long n,
                                          int numParts, void* temp, int numCU, const uint32_t* chunkFill, hipStream_t stream);
 extern "C" int pmcStatBucketBits();
+// test aids (include/pmc_tuning.h): the constants the log kernels are built with (the members of *out that do not depend on a context), and the
+// counting sort alone (stat: the statistics log's instantiation)
+extern "C" void pmcLogConstants(pmc_log_geometry_values* out);
+extern "C" hipError_t pmcLaunchLogPartition(int stat, const uint32_t* keys, const double* vals, uint32_t* sortedKeys, double* sortedVals, unsigned long long n,
+                                            int numParts, void* temp, int numCU, const uint32_t* fills, hipStream_t stream);
 extern "C" hipError_t pmcLaunchCycleStart(int slot, int gridKind, int kin, int slotBase, int numSlots, int listCounter, int* listOut, const int* listIn,
                                           int listLen, int maxBlocks, size_t ldsBytes, const PeelSortArgs* sort, hipStream_t stream);
 extern "C" hipError_t pmcLaunchTrace(int slot, int gridKind, int wide, int uniform, const double r[3], const double k[3],
@@ -264,5 +269,16 @@ struct CallBuffers
 
 // pmc_run.hip: the pool of packet slots
 int pmcAllocateSlots(pmc_ctx* ctx, int64_t n);
+
+// pmc_run.hip: which of the context's sums go through a log, and in how many partitions (the segment plan of pmc_run_primary and
+// pmc_tune_log_geometry; the switches PMC_RF_ATOMICS and PMC_STAT_ATOMICS are sampled here)
+struct LogPlan
+{
+    int64_t rfKeys, rfParts;  // keys of the radiation-field log (cells counted in the device numbering on an octree, padding included), partitions
+    bool rfLogged;
+    int64_t statRecords, statParts;
+    bool statLogged;
+};
+LogPlan pmcLogPlan(const pmc_ctx* ctx);
 
 #endif

@@ -569,6 +569,10 @@ struct PeelSortedArgs  // peel-off kernel; rec == nullptr: task records from Tas
 
 #define PMC_RF_LOG_CHUNK 4096
 #define PMC_RF_BUCKET_BITS 13  // keys per partition of the log: 2^13 doubles = 64 KB of LDS in rfReduceKernel
+// a run of a partition (within a workgroup's span of the partitioned log) with fewer entries than this is added to the table entry by entry:
+// not worth clearing and flushing the partition's sums in LDS (64 KB in rfReduceKernel, 80 KB in statReduceKernel)
+#define PMC_RF_SHORT_RUN 4096
+#define PMC_STAT_SHORT_RUN 1024
 
 #define PMC_NUM_COUNTERS 512
 #define PMC_CTR_HISTORY 8

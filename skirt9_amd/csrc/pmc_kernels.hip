@@ -63,6 +63,7 @@
 
 #include "pmc_device.h"
 #include "../../include/pmc_philox.h"
+#include "../../include/pmc_tuning.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
@@ -632,6 +633,25 @@ extern "C" hipError_t pmcLaunchStatFlush(int slot, const uint32_t* keys, const d
     const unsigned long long blocks = (n + PMC_RF_REDUCE_SPAN - 1) / PMC_RF_REDUCE_SPAN;
     hipLaunchKernelGGL(statReduceKernel, dim3((unsigned)blocks), dim3(RF_REDUCE_BLOCK), lds, stream, slot, sortedKeys, sortedVals, start, (uint32_t)numParts);
     return hipGetLastError();
+}
+// test aids (include/pmc_tuning.h): the constants the kernels above are built with, and the counting sort alone
+extern "C" void pmcLogConstants(pmc_log_geometry_values* out)
+{
+    out->chunk = PMC_RF_LOG_CHUNK;
+    out->rf_bucket_bits = PMC_RF_BUCKET_BITS;
+    out->stat_bucket_bits = PMC_STAT_BUCKET_BITS;
+    out->scan_threads = PMC_SCAN_THREADS;
+    out->sort_block = RF_SORT_BLOCK;
+    out->max_parts = RF_MAX_PARTS;
+    out->reduce_span = (int64_t)PMC_RF_REDUCE_SPAN;
+    out->rf_short_run = PMC_RF_SHORT_RUN;
+    out->stat_short_run = PMC_STAT_SHORT_RUN;
+}
+extern "C" hipError_t pmcLaunchLogPartition(int stat, const uint32_t* keys, const double* vals, uint32_t* sortedKeys, double* sortedVals, unsigned long long n,
+                                            int numParts, void* temp, int numCU, const uint32_t* fills, hipStream_t stream)
+{
+    return stat ? launchPartition<PMC_STAT_BUCKET_BITS>(keys, vals, sortedKeys, sortedVals, n, numParts, temp, numCU, stream, fills)
+                : launchPartition<PMC_RF_BUCKET_BITS>(keys, vals, sortedKeys, sortedVals, n, numParts, temp, numCU, stream, fills);
 }
 // end of a segment: statistics accumulator -> wifu arrays of the frames
 extern "C" hipError_t pmcLaunchStatMerge(int slot, int blocks, hipStream_t stream)

@@ -162,6 +162,26 @@ int pmcAllocateSlots(pmc_ctx* ctx, int64_t n)
     return allocateSlots(ctx, n);
 }
 
+// ---- radiation field on an octree: the contributions of a generation go to a log per slot group (pmc_device.h RfLogArgs), which is
+// partitioned by key range and summed after the generation.  Tables beyond 2^26 entries have more partitions than the counting sort's
+// LDS histogram holds: atomics.  (The keys of the log count cells in the device numbering: cell_slots of them, padding included.)
+// ---- statistics: the contributions of ended histories go to a log per slot group (pmc_device.h StatLogArgs), which is partitioned by
+// record range and summed in LDS when it has filled up, and at the end of the segment
+LogPlan pmcLogPlan(const pmc_ctx* ctx)
+{
+    const DevScene& D = ctx->dev;
+    const bool octree = D.grid_kind == PMC_GRID_OCTREE;
+    LogPlan L;
+    L.rfKeys = octree ? int64_t(D.cell_slots) * D.rf_num_lambda : ctx->rfSize;
+    L.rfParts = (L.rfKeys + (int64_t(1) << PMC_RF_BUCKET_BITS) - 1) >> PMC_RF_BUCKET_BITS;
+    L.rfLogged = D.rf_store && octree && L.rfParts <= pmcRfMaxParts() && pmcTune("PMC_RF_ATOMICS") == nullptr;
+    const int statBits = pmcStatBucketBits();
+    L.statRecords = D.stat_acc_records;
+    L.statParts = (D.stat_acc_records + (int64_t(1) << statBits) - 1) >> statBits;
+    L.statLogged = D.any_stats && D.stat_acc_records > 0 && L.statParts <= pmcRfMaxParts() && pmcTune("PMC_STAT_ATOMICS") == nullptr;
+    return L;
+}
+
 namespace
 {
     // ---- one segment of pmc_run_primary: the plan (decided once, before the first kernel), the buffers it needs, the generations of the slot
@@ -326,31 +346,24 @@ namespace
         if (const char* v = pmcTune("PMC_VPROP_BLOCKS_PER_CU")) propBlocks = std::max(1, atoi(v));
         if (const char* v = pmcTune("PMC_VPEEL_BLOCKS_PER_CU")) peelBlocks = std::max(1, atoi(v));
         P.voroPropGrid = ctx->numCU * propBlocks, P.voroPeelGrid = ctx->numCU * peelBlocks;
-        // ---- radiation field on an octree: the contributions of a generation go to a log per slot group (pmc_device.h RfLogArgs),
-        // which is partitioned by key range and summed after the generation.  128 entries per slot (config 2: 60 per propagation
-        // walk on average); a wave that finds the log full falls back to atomic adds into the table.
-        // (tables beyond 2^26 entries have more partitions than the counting sort's LDS histogram holds: atomics)
-        // (the keys of the log count cells in the device numbering: cell_slots of them, padding included)
-        const int64_t rfKeys = P.octree ? int64_t(D.cell_slots) * D.rf_num_lambda : ctx->rfSize;
-        const int64_t rfParts = (rfKeys + (int64_t(1) << PMC_RF_BUCKET_BITS) - 1) >> PMC_RF_BUCKET_BITS;
-        P.rfLogged = D.rf_store && P.octree && rfParts <= pmcRfMaxParts() && pmcTune("PMC_RF_ATOMICS") == nullptr;
-        if (D.rf_store && P.octree && rfParts > pmcRfMaxParts())
+        // ---- the logs of the radiation field and of the statistics (pmcLogPlan).  Radiation field: 128 entries per slot (config 2: 60 per
+        // propagation walk on average); a wave that finds the log full falls back to atomic adds into the table.
+        const LogPlan logs = pmcLogPlan(ctx);
+        P.rfLogged = logs.rfLogged;
+        if (D.rf_store && P.octree && logs.rfParts > pmcRfMaxParts())
         {
             // (a table beyond 2^26 entries: one atomic per contribution, several times slower -- said once, not silently)
             static std::atomic<bool> said{false};
             if (!said.exchange(true))
                 fprintf(stderr, "libpmc: the radiation field table has %lld entries, more than the log's counting sort partitions (%d x %d): contributions are added atomically\n",
-                        (long long)rfKeys, pmcRfMaxParts(), 1 << PMC_RF_BUCKET_BITS);
+                        (long long)logs.rfKeys, pmcRfMaxParts(), 1 << PMC_RF_BUCKET_BITS);
         }
-        P.rfBuckets = P.rfLogged ? int(rfParts) : 0;
+        P.rfBuckets = P.rfLogged ? int(logs.rfParts) : 0;
         P.rfPadKey = uint32_t(P.rfBuckets) << PMC_RF_BUCKET_BITS;
         P.rfLogPerSlot = 128ull;
         if (const char* env = pmcTune("PMC_RF_LOG_PER_SLOT")) P.rfLogPerSlot = std::max(1, atoi(env));  // (tests: a log that overflows)
-        // ---- statistics: the contributions of ended histories go to a log per slot group (pmc_device.h StatLogArgs), which is partitioned by
-        // record range and summed in LDS when it has filled up, and at the end of the segment
-        const int statBits = pmcStatBucketBits();
-        P.statParts = int((D.stat_acc_records + (int64_t(1) << statBits) - 1) >> statBits);
-        P.statLogged = D.any_stats && D.stat_acc_records > 0 && P.statParts <= pmcRfMaxParts() && pmcTune("PMC_STAT_ATOMICS") == nullptr;
+        P.statParts = int(logs.statParts);
+        P.statLogged = logs.statLogged;
         // (3.7 entries per history on configs[1]: the log of a group holds a segment of 1e8 packets; it is flushed when half full)
         unsigned long long entries = (128ull << 20);
         if (const char* env = pmcTune("PMC_STAT_LOG_ENTRIES")) entries = std::max(1, atoi(env));  // (tests: a log that overflows)

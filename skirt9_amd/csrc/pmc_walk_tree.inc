@@ -1459,7 +1459,7 @@
             while (start[b + 1u] <= pos) ++b;  // (empty partitions)
             const unsigned long long end = start[b + 1u] < last ? start[b + 1u] : last;
             const int64_t partBase = (int64_t)b << PMC_RF_BUCKET_BITS;
-            if (end - pos < 4096ull)
+            if (end - pos < (unsigned long long)PMC_RF_SHORT_RUN)
             {
                 // a short run (the sparse outskirts; tables with many wavelength bins): not worth clearing and flushing 64 KB
                 for (unsigned long long i = pos + tid; i < end; i += RF_REDUCE_BLOCK)
@@ -1523,7 +1523,7 @@
             while (start[b + 1u] <= pos) ++b;  // (empty partitions)
             const unsigned long long end = start[b + 1u] < last ? start[b + 1u] : last;
             const int64_t partBase = (int64_t)b << PMC_STAT_BUCKET_BITS;
-            if (end - pos < 1024ull)
+            if (end - pos < (unsigned long long)PMC_STAT_SHORT_RUN)
             {
                 // a short run (the outskirts of the image): not worth clearing and flushing 80 KB
                 for (unsigned long long i = pos + tid; i < end; i += RF_REDUCE_BLOCK)

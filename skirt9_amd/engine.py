@@ -24,7 +24,8 @@ SYMBOLS = ["pmc_abi_version", "pmc_build_info", "pmc_last_error", "pmc_frame_lay
            "pmc_sampler_density", "pmc_sampler_destroy", "pmc_history_range", "pmc_comm_init_all", "pmc_comm_unique_id",
            "pmc_comm_init_rank", "pmc_comm_size", "pmc_comm_destroy", "pmc_reduce_frames", "pmc_allreduce_radiation_field",
            "pmc_debug_tables", "pmc_tuning_set", "pmc_tuning_clear", "pmc_tune_dipole_cosines", "pmc_tune_source_velocities",
-           "pmc_launch_flavour"]
+           "pmc_launch_flavour", "pmc_tune_log_geometry", "pmc_tune_log_partition", "pmc_tune_rf_log_flush", "pmc_tune_stat_log_flush",
+           "pmc_tune_cell_numbering"]
 
 _lib = None
 
@@ -38,6 +39,13 @@ class WalkWork(C.Structure):
     """pmc_walk_work_values (include/pmc_tuning.h)"""
     _fields_ = [(n, C.c_uint64) for n in ("peel_wave_steps", "peel_lane_steps", "peel_rounds", "prop_wave_steps",
                                           "prop_lane_steps", "prop_rounds")]
+
+
+class LogGeometry(C.Structure):
+    """pmc_log_geometry_values (include/pmc_tuning.h)"""
+    _fields_ = [(n, C.c_int64) for n in ("cell_slots", "rf_num_lambda", "rf_keys", "rf_parts", "rf_logged", "stat_records", "stat_parts", "stat_logged",
+                                         "chunk", "rf_bucket_bits", "stat_bucket_bits", "scan_threads", "sort_block", "max_parts", "reduce_span",
+                                         "rf_short_run", "stat_short_run", "max_entries")]
 
 
 def lib():
@@ -109,6 +117,13 @@ def lib():
         if hasattr(L, "pmc_tuning_set"):
             L.pmc_tuning_set.argtypes = [C.c_char_p, C.c_char_p]
             L.pmc_tuning_clear.restype = None
+        if hasattr(L, "pmc_tune_log_geometry"):  # (absent from engines built from an older commit and loaded through PMC_LIBRARY)
+            L.pmc_tune_log_geometry.argtypes = [C.c_void_p, C.POINTER(LogGeometry)]
+            L.pmc_tune_log_partition.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
+            L.pmc_tune_rf_log_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+            L.pmc_tune_stat_log_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+            L.pmc_tune_cell_numbering.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -144,6 +159,11 @@ def tuning_from_environment():
     for key, value in os.environ.items():
         if key.startswith("PMC_") and key not in ENVIRONMENT_SETTINGS and key != "PMC_LIBRARY":
             set_tuning(key, value)
+
+
+def _ptr(array):
+    """the address of a numpy array for a void* argument; None: a null pointer"""
+    return None if array is None else array.ctypes.data_as(C.c_void_p)
 
 
 def _check(rc):
@@ -363,6 +383,56 @@ class Engine:
         out = np.empty_like(r)
         _check(lib().pmc_tune_source_velocities(self._h, int(source), r.ctypes.data_as(C.c_void_p), r.shape[0], out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def log_geometry(self):
+        """test aid (pmc_tune_log_geometry): the geometry of this context's radiation-field and statistics logs and the constants their
+        kernels are built with, as a dict of ints (the members of include/pmc_tuning.h pmc_log_geometry_values)"""
+        g = LogGeometry()
+        _check(lib().pmc_tune_log_geometry(self._h, C.byref(g)))
+        return {n: int(getattr(g, n)) for n, _ in g._fields_}
+
+    def _log_arrays(self, keys, vals, fills):
+        """a host log as the aids take it: n = len(keys); None stays a null pointer (the library refuses it)"""
+        keys = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+        vals = None if vals is None else np.ascontiguousarray(vals, dtype=np.float64).reshape(-1)
+        fills = None if fills is None else np.ascontiguousarray(fills, dtype=np.uint32).reshape(-1)
+        n = 0 if keys is None else keys.size
+        if vals is not None and keys is not None and vals.size != n:
+            raise ValueError("keys and vals differ in length")
+        if keys is None and vals is not None:
+            n = vals.size
+        if fills is not None and fills.size * self.log_geometry()["chunk"] < n:
+            raise ValueError("fills has fewer entries than the log has chunks")
+        return n, keys, vals, fills
+
+    def log_partition(self, stat, num_parts, keys, vals, fills=None):
+        """test aid (pmc_tune_log_partition): the counting sort of the logs alone, on a host-supplied log of len(keys) entries and `num_parts`
+        partitions; stat: the statistics log's instantiation.  Returns (sorted_keys, sorted_vals, start[num_parts + 1])"""
+        n, keys, vals, fills = self._log_arrays(keys, vals, fills)
+        sorted_keys, sorted_vals = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.float64)
+        start = np.zeros(max(int(num_parts), 0) + 1, dtype=np.uint64)
+        _check(lib().pmc_tune_log_partition(self._h, int(stat), int(num_parts), _ptr(keys), _ptr(vals), _ptr(fills), n, _ptr(sorted_keys), _ptr(sorted_vals),
+                                            _ptr(start)))
+        return sorted_keys, sorted_vals, start
+
+    def rf_log_flush(self, keys, vals):
+        """test aid (pmc_tune_rf_log_flush): a host-supplied radiation-field log through the sort and rfReduceKernel into the context's table"""
+        n, keys, vals, _ = self._log_arrays(keys, vals, None)
+        _check(lib().pmc_tune_rf_log_flush(self._h, _ptr(keys), _ptr(vals), n))
+
+    def stat_log_flush(self, keys, vals, fills=None):
+        """test aid (pmc_tune_stat_log_flush): a host-supplied statistics log through the sort and statReduceKernel; returns the accumulator,
+        [stat_records][5] = count, sums of w, w^2, w^3, w^4 per record, and leaves it cleared"""
+        n, keys, vals, fills = self._log_arrays(keys, vals, fills)
+        acc = np.empty((self.log_geometry()["stat_records"], 5), dtype=np.float64)
+        _check(lib().pmc_tune_stat_log_flush(self._h, _ptr(keys), _ptr(vals), _ptr(fills), n, _ptr(acc)))
+        return acc
+
+    def cell_numbering(self):
+        """test aid (pmc_tune_cell_numbering): the caller's cell index of every cell of the device numbering of a tree grid, -1: a padding slot"""
+        ext = np.empty(self.log_geometry()["cell_slots"], dtype=np.int32)
+        _check(lib().pmc_tune_cell_numbering(self._h, _ptr(ext)))
+        return ext
 
     def trace_ray(self, r, k, cap=4096):
         r = np.ascontiguousarray(r, dtype=np.float64)

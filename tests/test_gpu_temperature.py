@@ -16,6 +16,7 @@ import pytest
 import probe_checks as P
 import temperature_checks as T
 from conftest import ROOT, ski
+from scene_variants import with_field_grid
 from skirt9_amd import host
 from skirt9_amd.engine import INTEGRATE_PASS_VALUES, Engine, clear_tuning, lib, set_tuning
 from skirt9_amd.host import Simulation, scene_head
@@ -40,11 +41,6 @@ else:
     else:
         TORCH_PROBLEM = "torch sees no GPU"
 
-FIELD_GRID = ('<RadiationFieldOptions storeRadiationField="true"><radiationFieldWLG type="DisjointWavelengthGrid">%s</radiationFieldWLG>'
-              "</RadiationFieldOptions>")
-LOG_GRID = '<LogWavelengthGrid minWavelength="0.15 micron" maxWavelength="8 micron" numWavelengths="%d"/>'
-ONE_BIN = '<ListWavelengthGrid wavelengths="1 micron" relativeHalfWidth="0.3" log="true"/>'
-
 
 def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
@@ -52,17 +48,6 @@ def _bits(a):
 
 def _same_bits(a, b):
     return np.array_equal(_bits(a), _bits(b))
-
-
-def _with_field_grid(tmp_path, base, bins):
-    """tests/ski/<base>.ski storing the radiation field on `bins` bins (a text replacement of its radiationFieldOptions)"""
-    text = open(ski(base + ".ski")).read()
-    a = text.index("<RadiationFieldOptions")
-    b = text.index("</radiationFieldOptions>")
-    text = text[:a] + FIELD_GRID % (ONE_BIN if bins == 1 else LOG_GRID % bins) + text[b:]
-    path = tmp_path / f"{base}_{bins}.ski"
-    path.write_text(text)
-    return str(path)
 
 
 def _bound_field(eng, rf):
@@ -84,7 +69,7 @@ def test_kernel_equals_the_host_restatement(base, bins, components, tmp_path):
     64 an all-zero row (T = 0), a row above the table (exactly 5000 K), a row below its first node and a row that hits a node exactly; which
     kinds sit in cell 0 and in the last cell turns from case to case, so that over the cases every kind has been in both"""
     turn = KERNEL_CASES.index((base, bins, components))
-    sim = Simulation(_with_field_grid(tmp_path, base, bins), num_packets=100).setup()
+    sim = Simulation(with_field_grid(tmp_path, base, bins), num_packets=100).setup()
     cells = scene_head(sim).grid.num_cells
     assert sim.radiation_field_size == cells * bins
     tables = T.random_tables(cells, bins, components, seed=bins * 10 + components)
@@ -240,7 +225,7 @@ def test_results_do_not_depend_on_what_device_memory_held(tmp_path):
     set_tuning("PMC_POISON_ALLOCATIONS")
     try:
         for base, bins, components in (("cfg1temp", 65, 4), ("cfg5small", 6, 2)):
-            sim = Simulation(_with_field_grid(tmp_path, base, bins), num_packets=100).setup()
+            sim = Simulation(with_field_grid(tmp_path, base, bins), num_packets=100).setup()
             cells = scene_head(sim).grid.num_cells
             tables = T.random_tables(cells, bins, components, seed=bins * 10 + components)
             rf, _ = T.special_rows(tables, np.random.default_rng(bins).random(cells * bins) * 1e30, seed=components)
