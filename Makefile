@@ -50,7 +50,9 @@ clean:
 .PHONY: all oracle host clean
 
 # tuning aid: a variant of the engine with extra definitions (tools/sweep.py picks it by file name), e.g.
-#   make variant NAME=pert_valu_48 DEFS=-DPMC_PERTURB_VALU=48     -> skirt9_amd/lib/libpmc_pert_valu_48.so
+#   make variant NAME=refill32 DEFS=-DPMC_PROP_REFILL=32     -> skirt9_amd/lib/libpmc_refill32.so
+# (the perturbation, ablation and fold-octant variants are not in the tree: apply their patch from profiles/experiments
+# first -- perturb_octree_step, ablate_walk_side, ablate_transition_side, fold_octant; each names its DEFS in its header)
 variant:
 	@mkdir -p skirt9_amd/lib
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -shared $(wildcard skirt9_amd/csrc/*.hip) -lrccl -o skirt9_amd/lib/libpmc_$(NAME).so

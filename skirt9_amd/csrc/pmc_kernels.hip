@@ -132,9 +132,6 @@
     #define PMC_TRANSITION_MIN_WAVES 2  // likewise for the transition and launch kernels (256 registers: two waves per SIMD; left to
                                         // itself the compiler takes 262 and halves the occupancy)
 #endif
-#ifndef PMC_VORO_PAIRS
-    #define PMC_VORO_PAIRS 1  // Voronoi walk reads the per-(cell, neighbour) table DevScene::vpair instead of index -> site
-#endif
 #ifndef PMC_VORO_UNROLL
     #define PMC_VORO_UNROLL 8  // Voronoi walk: neighbours whose gathers are in flight together (pmc_walk.inc voroEnter)
 #endif
@@ -182,12 +179,9 @@ static_assert(PMC_TRANSITION_BLOCK <= 256 && PMC_TRANSITION_BLOCK % 64 == 0,
                                 // 623 ms per 1e8 packets, profiles/sweeps/r03_batch32_sweep.txt, r03_batch33_sweep.txt)
 #endif
 
-// Builds with an ablation / perturbation / experiment macro (tuning aids: they change results or add work) identify themselves:
-// pmc_create prints a warning for such a library (pmc_api.hip)
-#if defined(PMC_ABLATE_REFINE) || defined(PMC_ABLATE_SLOW) || defined(PMC_ABLATE_RF_MATH) || defined(PMC_ABLATE_RF_LOG) || defined(PMC_ABLATE_FRAMEADD)      \
-    || defined(PMC_ABLATE_HOTBINS) || defined(PMC_ABLATE_DETECT) || defined(PMC_ABLATE_STATS) || defined(PMC_ABLATE_LAUNCH_DUST)                             \
-    || defined(PMC_ABLATE_LAUNCH_BINS) || defined(PMC_ABLATE_LAUNCH_FLUSH) || defined(PMC_EXPERIMENT_FOLD_OCTANT) || defined(PMC_EXPERIMENT_PROP_SGN0) || defined(PMC_PERTURB_VALU)               \
-    || defined(PMC_PERTURB_GATHER) || defined(PMC_PERTURB_LDS)
+// A tree with one of the experiment patches of profiles/experiments applied (tuning aids: they change results or add work)
+// identifies itself: every such patch defines the macro below, and pmc_create prints a warning for such a library (pmc_api.hip)
+#ifdef PMC_EXPERIMENT_BUILD
 extern "C" int pmcExperimentBuild(void) { return 1; }
 #else
 extern "C" int pmcExperimentBuild(void) { return 0; }

@@ -191,13 +191,6 @@
     // accumulate into a detector bin: hot-bin table in LDS first (claim once per workgroup), HBM otherwise
     __device__ __forceinline__ void frameAdd(const DevScene& S, const DustLds& L, int64_t offset, double value)
     {
-#ifdef PMC_ABLATE_FRAMEADD
-        return;  // (tuning experiment only: no flux is recorded)
-#endif
-#ifdef PMC_ABLATE_HOTBINS
-        unsafeAtomicAdd(S.frames + offset, value);  // (tuning experiment only: every addition straight to HBM)
-        return;
-#endif
         const unsigned long long key = (unsigned long long)offset + 1ull;
         const int h = (int)((key * 0x9E3779B97F4A7C15ull) >> 56);  // 8 bits
         unsigned long long k = L.hotKey[h];
@@ -261,16 +254,12 @@
     {
         const DevInstrument& I = S.inst[inst];
         const SlotArrays& A = S.slots;
-#ifdef PMC_ABLATE_DETECT
-        return;  // (tuning experiment only)
-#endif
         // the head record of the history's contribution list (requested first: it arrives with the slot's other state)
         const int64_t ni = (int64_t)inst * A.num_slots + slot;
         char* const head = reinterpret_cast<char*>(A.statHead) + ni * 64;
         int4 headBin = make_int4(-1, -1, -1, -1);
         double2 headW01 = make_double2(0., 0.), headW23 = make_double2(0., 0.);
         int2 headN = make_int2(0, -1);
-#ifndef PMC_ABLATE_STATS
         // (an emission peel-off is the first contribution of its history: the list is empty, as the launch kernel left it)
         if (I.record_stats && numScatt > 0)
         {
@@ -279,7 +268,6 @@
             headW23 = *reinterpret_cast<const double2*>(head + 32);
             headN = *reinterpret_cast<const int2*>(head + 48);
         }
-#endif
         int l = pixelOnDetector(I, rx, ry, rz);
         if (!I.include_sed && l < 0) return;
         if (!insideAperture(I, rx, ry, rz)) return;
@@ -332,11 +320,7 @@
                 }
             }
         }
-#ifdef PMC_ABLATE_STATS
-        if (false)
-#else
         if (I.record_stats)
-#endif
         {
             // The list of a history holds ONE entry per distinct bin: a contribution to a bin that is already listed is added
             // to that entry (FluxRecorder.cpp:962-1014 sums the contributions of a history to the same bin before it takes
@@ -1266,11 +1250,6 @@
                 directionAbout(rng, seed, kx, ky, kz, costheta, kxn, kyn, kzn);
             }
         }
-#ifdef PMC_EXPERIMENT_FOLD_OCTANT
-        // (tuning experiment only, wrong physics: every propagation walk heads into the +++ octant, so that the L2 of every XCD
-        // sees the part of the grid that a walk list binned by direction octant would leave it with)
-        kxn = fabs(kxn), kyn = fabs(kyn), kzn = fabs(kzn);
-#endif
         A.kx[slot] = kxn, A.ky[slot] = kyn, A.kz[slot] = kzn;
         A.nscatt[slot] = nscatt + 1;
         cnt.scatterings += 1;
@@ -1506,9 +1485,6 @@
         }
         else
             randomDirection(rng, seed, kx, ky, kz);
-#ifdef PMC_EXPERIMENT_FOLD_OCTANT
-        kx = fabs(kx), ky = fabs(ky), kz = fabs(kz);
-#endif
         const double Lw = Q.packet_luminosity * w;
         const double W = Lw * lambda;
         const double lambda0 = lambda;
@@ -1527,11 +1503,7 @@
         A.nscatt[slot] = 0;
         A.mint[slot] = -1;  // (no hint for the first cell of the first cycle's walks)
         // dust properties at this wavelength (DustMix::indexForLambda, DustMix.cpp:276-279)
-#ifdef PMC_ABLATE_LAUNCH_DUST
-        const int il = 0;  // (tuning experiment only)
-#else
         const int il = locateClip(L.lamb, S.num_lambda, lambda);
-#endif
         const double sext = L.sext[il], asym = L.asym[il];
         if (!S.mono)
         {
@@ -1549,11 +1521,7 @@
         {
             const DevInstrument& I = S.inst[i];
             const double lambdaObs = lambda * I.zp1;  // the packet's redshifted wavelength (FluxRecorder.cpp:309-310)
-#ifdef PMC_ABLATE_LAUNCH_BINS
-            int lo = 1, hi = 1;  // (tuning experiment only)
-#else
             int lo = 0, hi = S.mono ? 0 : I.num_border;  // upper_bound (one wavelength for every history: DevInstrument::mono_ell)
-#endif
             while (lo < hi)
             {
                 int mid = (lo + hi) >> 1;
@@ -1927,9 +1895,7 @@
                     h = h0 + (unsigned long long)(c + lane);
                 }
                 const bool ended = slot >= 0;
-#ifndef PMC_ABLATE_LAUNCH_FLUSH
                 if (!initial && S.any_stats) flushStatistics<KIN>(S, L, cnt, slot, ended, lane, group, true, statLog, logWave);
-#endif
                 PMC_T_STAMP(2);
                 int event = ended ? EV_LAUNCH : EV_NONE;
                 // (first generation, and the rare zero-luminosity packet whose life cycle the reference skips: the index is drawn

@@ -78,12 +78,10 @@
     __device__ __forceinline__ double exactQuotient(double d, double k, double y)
     {
         double q = d * y;
-#ifndef PMC_ABLATE_REFINE
         double r = __builtin_fma(-k, q, d);
         q = __builtin_fma(r, y, q);
         r = __builtin_fma(-k, q, d);
         q = __builtin_fma(r, y, q);
-#endif
         return fmin(q, DBL_MAX);
     }
 
@@ -514,7 +512,6 @@
         const int s0 = bounds.x;
         const int e = bounds.y;
         int q = s0;
-#if PMC_VORO_PAIRS
         if (S.vcull)
         {
             // ---- the first 32 neighbours through the cone's mask: the ones that lie behind the direction are not read.
@@ -551,14 +548,12 @@
             }
             q = s0 + 32;  // (a cell with more neighbours -- two in 10^5 cells of a 10^6-site grid: the rest without a mask)
         }
-#endif
-        // UNROLL neighbours per round: their indices first, then their sites -- the gathers of a round are in flight
-        // together instead of one dependent index -> site chain per neighbour; the candidates are compared in list order
+        // UNROLL neighbours per round: their records of the pair table (site and index in one entry) are gathered
+        // together, so that the loads of a round are in flight at once; the candidates are compared in list order
         for (; q < e; q += UNROLL)
         {
             int mi[UNROLL];
             double pix[UNROLL], piy[UNROLL], piz[UNROLL];
-#if PMC_VORO_PAIRS
 #pragma unroll
             for (int j = 0; j < UNROLL; ++j)
             {
@@ -569,17 +564,6 @@
                 pix[j] = xy.x, piy[j] = xy.y, piz[j] = zi.x;
                 mi[j] = (q + j < e) ? (int)__double_as_longlong(zi.y) : -7;  // -7: no neighbour
             }
-#else
-#pragma unroll
-            for (int j = 0; j < UNROLL; ++j) mi[j] = (q + j < e) ? S.vnbr_list[q + j] : -7;  // -7: no neighbour
-#pragma unroll
-            for (int j = 0; j < UNROLL; ++j)
-            {
-                const double* site = S.vsite + 4 * (int64_t)max(mi[j], 0);  // (a wall reads site 0 and ignores it)
-                const double2 xy = *reinterpret_cast<const double2*>(site);
-                pix[j] = xy.x, piy[j] = xy.y, piz[j] = site[2];
-            }
-#endif
 #pragma unroll
             for (int j = 0; j < UNROLL; ++j) voroCandidate(S, rx, ry, rz, kx, ky, kz, prx, pry, prz, mi[j], pix[j], piy[j], piz[j], sq, mq);
         }
@@ -635,9 +619,6 @@
                 const int before = mq;
                 voroCandidate(S, rx, ry, rz, kx, ky, kz, prx, pry, prz, (q + j < cnt) ? mi[j] : -7, pix[j], piy[j], piz[j], sq, mq);
                 if (mq != before) runq = ri[j];
-#if PMC_VORO_RUN_SERIAL
-                __builtin_amdgcn_sched_barrier(0);  // (one candidate at a time: their temporaries -- a division each -- share registers)
-#endif
             }
             q += FIRST;
         } while (q < cnt);
@@ -1037,13 +1018,8 @@
     __device__ __forceinline__ double rfSegment(double rfL, double rfExtBeg, double tau0, double tabs0, double tau1, double tabs1, double ds, double& extEnd)
     {
         const double lnExtEnd = EA ? -(tau1 + tabs1) : -tau1;
-#ifdef PMC_ABLATE_RF_MATH
-        extEnd = lnExtEnd;  // (tuning experiment only: wrong values)
-        return rfL * (extEnd + rfExtBeg) * ds;
-#else
         extEnd = exp(lnExtEnd);
         return rfL * lnmean(extEnd, rfExtBeg, lnExtEnd, EA ? -(tau0 + tabs0) : -tau0) * ds;
-#endif
     }
 
     // findInteractionPoint (SpatialGridPath.cpp:177-196) in the segment in which the walk stops, the first one with tau > target: its cell,

@@ -67,30 +67,6 @@
     #define PMC_WPROF_PASS
 #endif
 
-
-// Perturbation builds (tuning aid, profiles/r03_perturb_*): known extra work of ONE kind is added to every step of the octree walk
-// kernels and the change of the kernel time read off -- the sensitivity says which resource bounds the step.  Results are
-// unchanged (the extra work feeds a sink that is never stored).
-//   PMC_PERTURB_VALU=n    n more independent f64 FMAs per step (four accumulators)
-//   PMC_PERTURB_GATHER=1  a second record of the SAME 64-byte sector per step (cell ^ 1); =2: of a random other line of the
-//                         table; =3: of a random line of its first 128 KB (cache hits); =4: of a line within 4 KB behind the cell
-//   PMC_PERTURB_LDS=n     n more 8-byte LDS reads per step at lane-dependent addresses of the coordinate table
-#if defined(PMC_PERTURB_VALU) || defined(PMC_PERTURB_GATHER) || defined(PMC_PERTURB_LDS)
-    #define PMC_PERTURB 1
-    struct Perturb
-    {
-        double a0, a1, a2, a3;
-        uint4 ga, gb;
-        uint32_t sink;
-    };
-    #define PMC_PERTURB_DECL Perturb pg = {1., 1., 1., 1., make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), 0u}
-    #define PMC_PERTURB_FINISH                                                                                          \
-        if (pg.sink == 0x12345678u || pg.a0 + pg.a1 + pg.a2 + pg.a3 == 1.2345) S.counters[PMC_NUM_COUNTERS - 1] = 1ull
-#else
-    #define PMC_PERTURB_DECL
-    #define PMC_PERTURB_FINISH
-#endif
-
     template<bool WIDE> struct Pack;
     template<> struct Pack<false>
     {
@@ -307,9 +283,6 @@
     // 1.7x slower here even though the call is never taken -- profiles/README.md, r02 experiment 4)
     template<bool WIDE> __device__ __forceinline__ bool treeSlowStep(const DevScene& S, const GridLds& L, const Dir& d, TWalk<WIDE>& w)
     {
-#ifdef PMC_ABLATE_SLOW
-        return false;  // (tuning experiment only: wrong results for the few walks that need the literal algorithm)
-#endif
         Walk g;
         g.rx = w.rx, g.ry = w.ry, g.rz = w.rz;
         g.kx = d.kx, g.ky = d.ky, g.kz = d.kz;
@@ -589,7 +562,6 @@
         unsigned long long poolNext = 0, poolEnd = 0;
         unsigned long long visits = 0, waveSteps = 0, services = 0;
         const unsigned long long below = (1ull << lane) - 1ull;
-        PMC_PERTURB_DECL;
 #ifdef PMC_PROFILE
         WalkProf prof = {{0, 0, 0, 0, 0, 0, 0, 0}, clock64(), {0, 0, 0, 0, 0, 0, 0, 0}};
 #endif
@@ -714,9 +686,6 @@
                 {
                     const double step = w.ds + eps;
                     const double nrx = w.rx + d.kx * step, nry = w.ry + d.ky * step, nrz = w.rz + d.kz * step;
-#ifdef PMC_PERTURB_GATHER
-                    pg.sink ^= pg.ga.x ^ pg.gb.w;
-#endif
 #ifndef PMC_EXP_NARROW_LOADS
                     cellLanded(g);
 #endif
@@ -734,42 +703,13 @@
                         if (st == ST_ACTIVE)
                         {
                             cellIssue(C, cell2, g);
-#ifdef PMC_PERTURB_GATHER
-                            {
-                                const uint32_t h2 = (cell2 * 2654435761u) >> 12;  // (20 bits)
-                                const uint32_t c2 = PMC_PERTURB_GATHER == 1 ? (cell2 ^ 1u) : PMC_PERTURB_GATHER == 3 ? (h2 & 4095u) : PMC_PERTURB_GATHER == 4 ? (cell2 + (h2 & 127u)) : (h2 < C.numCells ? h2 : h2 >> 1);
-                                const char* p2 = C.cellTab + ((uint64_t)(c2 < C.numCells ? c2 : cell2) << 5);
-                                pg.ga = *reinterpret_cast<const uint4*>(p2);
-                                pg.gb = *reinterpret_cast<const uint4*>(p2 + 16);
-                            }
-#endif
                             st = treeEnterBox<WIDE, SGNX>(C, d, w PMC_WPROF_PASS);
                             if (st == ST_ACTIVE) w.cell = cell2;
-#ifdef PMC_PERTURB_VALU
-#pragma unroll
-                            for (int q = 0; q < PMC_PERTURB_VALU / 4; ++q)
-                            {
-                                asm volatile("v_fma_f64 %0, %1, %2, %0" : "+v"(pg.a0) : "v"(w.rx), "v"(w.ry));
-                                asm volatile("v_fma_f64 %0, %1, %2, %0" : "+v"(pg.a1) : "v"(w.ry), "v"(w.rz));
-                                asm volatile("v_fma_f64 %0, %1, %2, %0" : "+v"(pg.a2) : "v"(w.rz), "v"(w.rx));
-                                asm volatile("v_fma_f64 %0, %1, %2, %0" : "+v"(pg.a3) : "v"(w.rx), "v"(w.rz));
-                            }
-#endif
-#ifdef PMC_PERTURB_LDS
-#pragma unroll
-                            for (int q = 0; q < PMC_PERTURB_LDS; ++q)
-                            {
-                                typedef __attribute__((address_space(3))) const volatile double LdsVolatile;
-                                const uint32_t at = (q & 1 ? w.by : w.bx) & 0x1ff8u;
-                                pg.a0 += *reinterpret_cast<LdsVolatile*>(static_cast<uintptr_t>(at + 8u * (uint32_t)(q >> 1)));
-                            }
-#endif
                         }
                     }
                 }
             }
         }
-        PMC_PERTURB_FINISH;
         if (lane == 0 && visits)
         {
             atomicAdd(S.counters + 2, visits);
@@ -806,11 +746,7 @@
                                                                             const int cursor, const uint64_t seed, const int ckptOffset,
                                                                             const RfLogArgs rfLog, const int* const list)
     {
-#ifdef PMC_EXPERIMENT_PROP_SGN0
-        constexpr int SGNX = 0;   // (tuning experiment with PMC_EXPERIMENT_FOLD_OCTANT only: every direction lies in the +++ octant, its signs are compile-time)
-#else
         constexpr int SGNX = -1;  // (per-lane directions)
-#endif
         const DevScene& S = c_scene[sceneSlot];
         extern __shared__ double lds[];
         const int tid = threadIdx.x;
@@ -859,7 +795,6 @@
         unsigned long long logBase = 0;
         uint32_t logFill = PMC_RF_LOG_CHUNK;  // (no chunk yet)
         const unsigned long long laneBelow = (1ull << lane) - 1ull;
-        PMC_PERTURB_DECL;
         bool exhausted = false;
         unsigned long long poolNext = 0, poolEnd = 0;  // wave-uniform
         unsigned long long waveSteps = 0, laneSteps = 0, services = 0;
@@ -1065,9 +1000,6 @@
                     const double step = w.ds + eps;
                     const double nrx = w.rx + d.kx * step, nry = w.ry + d.ky * step, nrz = w.rz + d.kz * step;
                     // the record of the current cell: density and the link through the exit wall
-#ifdef PMC_PERTURB_GATHER
-                    pg.sink ^= pg.ga.x ^ pg.gb.w;
-#endif
                     const uint32_t link = cellLink<SGNX>(g, d, w.axis);
                     w.dens = cellDensity(g);
                     PMC_WSTAMP(0);
@@ -1115,36 +1047,8 @@
                         {
                             // the next cell's record is requested BEFORE the arithmetic that enters the cell
                             cellIssue(C, cell2, g);
-#ifdef PMC_PERTURB_GATHER
-                            {
-                                const uint32_t h2 = (cell2 * 2654435761u) >> 12;  // (20 bits)
-                                const uint32_t c2 = PMC_PERTURB_GATHER == 1 ? (cell2 ^ 1u) : PMC_PERTURB_GATHER == 3 ? (h2 & 4095u) : PMC_PERTURB_GATHER == 4 ? (cell2 + (h2 & 127u)) : (h2 < C.numCells ? h2 : h2 >> 1);
-                                const char* p2 = C.cellTab + ((uint64_t)(c2 < C.numCells ? c2 : cell2) << 5);
-                                pg.ga = *reinterpret_cast<const uint4*>(p2);
-                                pg.gb = *reinterpret_cast<const uint4*>(p2 + 16);
-                            }
-#endif
                             st = treeEnterBox<WIDE, SGNX>(C, d, w PMC_WPROF_PASS);
                             if (st == ST_ACTIVE) w.cell = cell2;
-#ifdef PMC_PERTURB_VALU
-#pragma unroll
-                            for (int q = 0; q < PMC_PERTURB_VALU / 4; ++q)
-                            {
-                                asm volatile("v_fma_f64 %0, %1, %2, %0" : "+v"(pg.a0) : "v"(w.rx), "v"(w.ry));
-                                asm volatile("v_fma_f64 %0, %1, %2, %0" : "+v"(pg.a1) : "v"(w.ry), "v"(w.rz));
-                                asm volatile("v_fma_f64 %0, %1, %2, %0" : "+v"(pg.a2) : "v"(w.rz), "v"(w.rx));
-                                asm volatile("v_fma_f64 %0, %1, %2, %0" : "+v"(pg.a3) : "v"(w.rx), "v"(w.rz));
-                            }
-#endif
-#ifdef PMC_PERTURB_LDS
-#pragma unroll
-                            for (int q = 0; q < PMC_PERTURB_LDS; ++q)
-                            {
-                                typedef __attribute__((address_space(3))) const volatile double LdsVolatile;
-                                const uint32_t at = (q & 1 ? w.by : w.bx) & 0x1ff8u;
-                                pg.a0 += *reinterpret_cast<LdsVolatile*>(static_cast<uintptr_t>(at + 8u * (uint32_t)(q >> 1)));
-                            }
-#endif
                             PMC_WSTAMP(4);
                         }
                     }
@@ -1155,12 +1059,7 @@
                     // wave's chunk is wave-uniform).  They go to the group's log -- coalesced stores; partitioned by key range
                     // and summed in LDS after the generation: as atomics into the table (238 per history, every lane on a sector
                     // of its own) they cost 0.95 s per 1e8 packets, more than the walks themselves.
-#ifdef PMC_ABLATE_RF_LOG
-                    if (rfValue == 1.2345e-300) S.rf[0] = rfValue;  // (tuning experiment only: no contribution is stored)
-                    const unsigned long long m = 0ull;
-#else
                     const unsigned long long m = __ballot(rfPending);
-#endif
                     if (m != 0ull)
                     {
                         bool logged = false;
@@ -1207,7 +1106,6 @@
         // (RF) the unused rest of the wave's last chunk
         if (RF && rfLog.cap != 0ull)
             for (uint32_t i = logFill + (uint32_t)lane; i < (uint32_t)PMC_RF_LOG_CHUNK; i += 64u) rfLog.keys[logBase + i] = rfLog.padKey;
-        PMC_PERTURB_FINISH;
         flushWalkCounters(S, lane, paths, visits, rewalks);
         if (lane == 0 && waveSteps)
         {

@@ -1,6 +1,8 @@
 #!/bin/bash
 # tuning aid: builds engine variants skirt9_amd/lib/libpmc_<name>.so (make variant) in parallel
-#   tools/build_variants.sh "pert_valu_48 -DPMC_PERTURB_VALU=48" "trim8 -DPMC_PROP_TRIM=8" ...
+#   tools/build_variants.sh "refill32 -DPMC_PROP_REFILL=32" "steps4 -DPMC_WALK_STEPS=4" ...
+# (the perturbation, ablation and fold-octant variants need their patch from profiles/experiments applied first:
+#  git apply profiles/experiments/perturb_octree_step.patch, ablate_walk_side, ablate_transition_side, fold_octant)
 cd "$(dirname "$0")/.."
 n=0
 for v in "$@"; do
