@@ -21,7 +21,8 @@
 //                     kernel) the peel-off walks towards one observer: the direction lives in scalar registers, every
 //                     wave keeps a queue of task records in LDS from which a lane takes its next walk by itself.
 //                     (walkKernel in pmc_walk.inc is the generic form for Cartesian and Voronoi grids: all walks of a
-//                     slot one after the other in one lane.)
+//                     slot one after the other in one lane; voroPeelKernel and voroPropKernel in pmc_walk_voro_run.inc
+//                     take the walks of a Voronoi grid that has tables of runs, two lanes per walk.)
 //   transitionKernel  (pmc_transition.inc) one lane per live slot, every wave working through its own compacted list:
 //                     detection of the cycle's peel-off packets (FluxRecorder::detect: privatised SED bins and a
 //                     claim-once hot-bin table in LDS in front of f64 atomics, per-history statistics lists), the
@@ -133,7 +134,7 @@
                                         // itself the compiler takes 262 and halves the occupancy)
 #endif
 #ifndef PMC_VORO_UNROLL
-    #define PMC_VORO_UNROLL 8  // Voronoi walk: neighbours whose gathers are in flight together (pmc_walk.inc voroEnter)
+    #define PMC_VORO_UNROLL 8  // Voronoi walk: neighbours whose gathers are in flight together (pmc_walk_voro.inc voroEnter)
 #endif
 #ifndef PMC_VPEEL_MIN_WAVES
     #define PMC_VPEEL_MIN_WAVES 4  // waves per SIMD the Voronoi peel-off kernel's register budget must allow
@@ -267,6 +268,7 @@ namespace
     }
 
 #include "pmc_walk.inc"
+#include "pmc_walk_voro_run.inc"
 #include "pmc_walk_tree.inc"
 #include "pmc_transition.inc"
 #include "pmc_ray.inc"

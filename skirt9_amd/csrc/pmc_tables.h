@@ -737,7 +737,7 @@ namespace
         return cull;
     }
 
-    // the cone of a direction: as voroCone (pmc_walk.inc)
+    // the cone of a direction: as voroCone (pmc_walk_voro.inc)
     inline int voroConeOf(double kx, double ky, double kz)
     {
         const int sgn = (kx < 0. ? 1 : 0) | (ky < 0. ? 2 : 0) | (kz < 0. ? 4 : 0);

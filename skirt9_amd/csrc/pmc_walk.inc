@@ -1,4 +1,5 @@
-// pmc_walk.inc -- grid traversal and the walk kernel (included by pmc_kernels.hip inside its anonymous namespace).
+// pmc_walk.inc -- grid traversal and the walk kernel (included by pmc_kernels.hip inside its anonymous namespace).  The step of a Voronoi
+// grid is in pmc_walk_voro.inc, that of a binary tree in pmc_walk_bin.inc; the Voronoi kernels of their own in pmc_walk_voro_run.inc.
 //
 // The hot loop of the engine is ONE straight-line step per cell visit (no data-dependent branch except the rare
 // descent to a much finer neighbour): add the pending segment, test the stop condition, advance the position, follow
@@ -341,352 +342,7 @@
         return true;
     }
 
-    // ------------------------------------------------------------------------------------------------
-    // Voronoi helpers (VoronoiMeshSnapshot.cpp:1006-1040, 1058-1188).  A walk on a Voronoi grid keeps, as its pending
-    // segment, the cell w.cell, the exit distance w.ds and -- in w.ci -- the neighbour through whose bisecting plane (or
-    // the domain wall -1..-6 through which) the path leaves the cell.
-
-    // VoronoiMeshSnapshot::cellIndex: nearest site among the cells listed for the block of the position; -1 outside
-    __device__ __forceinline__ int voroCellIndex(const DevScene& S, double x, double y, double z)
-    {
-        if (!(x >= S.gx0 && x <= S.gx1 && y >= S.gy0 && y <= S.gy1 && z >= S.gz0 && z <= S.gz1)) return -1;
-        const int nb = S.vblock_n;
-        const int i = max(0, min(nb - 1, (int)(nb * (x - S.gx0) / (S.gx1 - S.gx0))));
-        const int j = max(0, min(nb - 1, (int)(nb * (y - S.gy0) / (S.gy1 - S.gy0))));
-        const int k = max(0, min(nb - 1, (int)(nb * (z - S.gz0) / (S.gz1 - S.gz0))));
-        const int64_t b = ((int64_t)i * nb + j) * nb + k;
-        int best = -1;
-        double mdist = DBL_MAX;
-        const int e = S.vblock_start[b + 1];
-        for (int q = S.vblock_start[b]; q < e; ++q)
-        {
-            const int id = S.vblock_list[q];
-            const double2 pxy = *reinterpret_cast<const double2*>(S.vsite + 4 * (int64_t)id);
-            const double pz = S.vsite[4 * (int64_t)id + 2];
-            const double dx = x - pxy.x, dy = y - pxy.y, dz = z - pz;
-            const double idist = dx * dx + dy * dy + dz * dz;
-            if (idist < mdist)
-            {
-                best = id;
-                mdist = idist;
-            }
-        }
-        return best;
-    }
-
-    // true if site m is certainly the nearest site of the position, i.e. cellIndex would return m: the position is
-    // closer to it than to every Voronoi neighbour of m, with a relative margin far above the rounding of the squared
-    // distances (a position that close to a face goes through the full search).  Used for the interaction point of a
-    // propagation walk, whose cell the walk already knows.
-    __device__ __forceinline__ bool voroIsNearest(const DevScene& S, int m, double x, double y, double z)
-    {
-        if (!(x >= S.gx0 && x <= S.gx1 && y >= S.gy0 && y <= S.gy1 && z >= S.gz0 && z <= S.gz1)) return false;
-        const double2 pxy = *reinterpret_cast<const double2*>(S.vsite + 4 * (int64_t)m);
-        const double pz = S.vsite[4 * (int64_t)m + 2];
-        const double dx = x - pxy.x, dy = y - pxy.y, dz = z - pz;
-        const double bound = (dx * dx + dy * dy + dz * dz) * (1. + 1e-9);
-        const int e = S.vnbr_start[m + 1];
-        bool nearest = true;
-        for (int q = S.vnbr_start[m]; q < e; q += 4)
-        {
-            double d[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-            {
-                const double* pair = S.vpair + 4 * (int64_t)min(q + j, e - 1);
-                const double2 xy = *reinterpret_cast<const double2*>(pair);
-                const double2 zi = *reinterpret_cast<const double2*>(pair + 2);
-                const double ex = x - xy.x, ey = y - xy.y, ez = z - zi.x;
-                const bool site = (q + j < e) && (int)__double_as_longlong(zi.y) >= 0;
-                d[j] = site ? ex * ex + ey * ey + ez * ez : DBL_MAX;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (!(d[j] > bound)) nearest = false;
-        }
-        return nearest;
-    }
-
-    // the exit of cell m for the position and direction of w (MySegmentGenerator::next, State::Inside, :1088-1150):
-    // smallest positive intersection distance with the bisecting planes towards the neighbours and with the domain walls.
-    // Returns false (w untouched) if no exit is found.
-    // UNROLL neighbours per round (the walk kernel's hot step: 4; the start of a walk in the transition / launch kernels,
-    // whose register budget is spent elsewhere: 1)
-    // one candidate of the exit search (:1100-1140): neighbour mi (site pix, piy, piz; -1..-6: a domain wall; -7: none)
-    __device__ __forceinline__ void voroCandidate(const DevScene& S, double rx, double ry, double rz, double kx, double ky, double kz, double prx,
-                                                  double pry, double prz, int mi, double pix, double piy, double piz, double& sq, int& mq)
-    {
-        double si = 0.;
-        if (mi >= 0)
-        {
-            const double nx = pix - prx, ny = piy - pry, nz = piz - prz;
-            const double ndotk = nx * kx + ny * ky + nz * kz;
-            if (ndotk > 0)
-            {
-                const double px = 0.5 * (pix + prx), py = 0.5 * (piy + pry), pz = 0.5 * (piz + prz);
-                si = (nx * (px - rx) + ny * (py - ry) + nz * (pz - rz)) / ndotk;
-            }
-        }
-        else if (mi == -1)
-            si = (S.gx0 - rx) / kx;
-        else if (mi == -2)
-            si = (S.gx1 - rx) / kx;
-        else if (mi == -3)
-            si = (S.gy0 - ry) / ky;
-        else if (mi == -4)
-            si = (S.gy1 - ry) / ky;
-        else if (mi == -5)
-            si = (S.gz0 - rz) / kz;
-        else if (mi == -6)
-            si = (S.gz1 - rz) / kz;
-        if (si > 0 && si < sq)
-        {
-            sq = si;
-            mq = mi;
-        }
-    }
-
-    // the same candidate for the kernels with lane pairs: ONE branch around all six domain walls (a cell at the boundary has one or two of them; the
-    // chain of six tests above costs every candidate of every cell six skipped branches)
-    __device__ __forceinline__ void voroCandidatePair(const DevScene& S, double rx, double ry, double rz, double kx, double ky, double kz, double prx,
-                                                      double pry, double prz, int mi, double pix, double piy, double piz, double& sq, int& mq)
-    {
-        double si = 0.;
-        if (mi >= 0)
-        {
-            const double nx = pix - prx, ny = piy - pry, nz = piz - prz;
-            const double ndotk = nx * kx + ny * ky + nz * kz;
-            if (ndotk > 0)
-            {
-                const double px = 0.5 * (pix + prx), py = 0.5 * (piy + pry), pz = 0.5 * (piz + prz);
-                si = (nx * (px - rx) + ny * (py - ry) + nz * (pz - rz)) / ndotk;
-            }
-        }
-        else if (mi > -7)
-        {
-            // wall -1 .. -6: x0, x1, y0, y1, z0, z1 (:1128-1140): (wall coordinate - position) / direction of its axis
-            const int a = -1 - mi;
-            const int axis = a >> 1;
-            const double lo = axis == 0 ? S.gx0 : axis == 1 ? S.gy0 : S.gz0, hi = axis == 0 ? S.gx1 : axis == 1 ? S.gy1 : S.gz1;
-            si = (((a & 1) ? hi : lo) - (axis == 0 ? rx : axis == 1 ? ry : rz)) / (axis == 0 ? kx : axis == 1 ? ky : kz);
-        }
-        if (si > 0 && si < sq)
-        {
-            sq = si;
-            mq = mi;
-        }
-    }
-
-    // direction cone of DevScene::vcull: sign pattern (bit a: k_a < 0) * 6 + order of |k_x|, |k_y|, |k_z| (pmc_api.hip `perm`)
-    __device__ __forceinline__ int voroCone(double kx, double ky, double kz)
-    {
-        const int sgn = (kx < 0. ? 1 : 0) | (ky < 0. ? 2 : 0) | (kz < 0. ? 4 : 0);
-        const double ax = fabs(kx), ay = fabs(ky), az = fabs(kz);
-        int p;
-        if (ax >= ay)
-            p = ay >= az ? 0 : ax >= az ? 1 : 4;
-        else
-            p = ax >= az ? 2 : ay >= az ? 3 : 5;
-        if (PMC_VORO_CONES == 48) return sgn * 6 + p;
-        // the sub-cone: k = a e1 + b e2 + c e3 with x >= y >= z the sorted magnitudes, a = x - y, b = y - z, c = z
-        const double x = fmax(ax, fmax(ay, az)), z = fmin(ax, fmin(ay, az)), y = (ax + ay + az) - x - z;
-        const double a = x - y, b = y - z, c = z;
-        const int sub = a >= b + c ? 0 : b >= a + c ? 1 : c >= a + b ? 2 : 3;
-        return (sgn * 6 + p) * 4 + sub;
-    }
-
-    template<int UNROLL> __device__ __forceinline__ bool voroEnter(const DevScene& S, Walk& w, int m)
-    {
-        // the cell's header record: site, density and list bounds in one 64-byte sector
-        const double* const heads = S.vhead;
-        const double* const pairs = S.vpair;
-        const double* head = heads + 8 * (int64_t)m;
-        const double2 prxy = *reinterpret_cast<const double2*>(head);
-        const double2 przn = *reinterpret_cast<const double2*>(head + 2);
-        const int2 bounds = *reinterpret_cast<const int2*>(head + 4);
-        const double prx = prxy.x, pry = prxy.y, prz = przn.x;
-        const double rx = w.rx, ry = w.ry, rz = w.rz, kx = w.kx, ky = w.ky, kz = w.kz;
-        double sq = DBL_MAX;
-        const int NO_INDEX = -99;
-        int mq = NO_INDEX;
-        const int s0 = bounds.x;
-        const int e = bounds.y;
-        int q = s0;
-        if (S.vcull)
-        {
-            // ---- the first 32 neighbours through the cone's mask: the ones that lie behind the direction are not read.
-            // The mask comes in the same round trip as the list bounds; the candidates keep their list order.
-            uint32_t keep = ~S.vcull[(int64_t)voroCone(kx, ky, kz) * S.num_cells + m];
-            const int cnt = e - s0;
-            if (cnt < 32) keep &= (1u << cnt) - 1u;
-            // rounds of PMC_VORO_CULL_ROUND neighbours whose gathers are in flight together (written out here: as a function
-            // with the mask and the running minimum by reference the kernel got scratch memory and ran 30 % slower)
-            while (keep != 0u)
-            {
-                constexpr int N = UNROLL > 1 ? PMC_VORO_CULL_ROUND : 1;  // (the transition / launch kernels: one at a time, their registers are spent)
-                int mi[N];
-                double pix[N], piy[N], piz[N];
-                int last = 0;
-#pragma unroll
-                for (int j = 0; j < N; ++j)
-                {
-                    // (slots beyond the kept neighbours read the last one again and are ignored)
-                    const bool have = keep != 0u;
-                    if (have)
-                    {
-                        last = __ffs((int)keep) - 1;
-                        keep &= keep - 1u;
-                    }
-                    const double* pair = pairs + 4 * (int64_t)(s0 + last);
-                    const double2 xy = *reinterpret_cast<const double2*>(pair);
-                    const double2 zi = *reinterpret_cast<const double2*>(pair + 2);
-                    pix[j] = xy.x, piy[j] = xy.y, piz[j] = zi.x;
-                    mi[j] = have ? (int)__double_as_longlong(zi.y) : -7;
-                }
-#pragma unroll
-                for (int j = 0; j < N; ++j) voroCandidate(S, rx, ry, rz, kx, ky, kz, prx, pry, prz, mi[j], pix[j], piy[j], piz[j], sq, mq);
-            }
-            q = s0 + 32;  // (a cell with more neighbours -- two in 10^5 cells of a 10^6-site grid: the rest without a mask)
-        }
-        // UNROLL neighbours per round: their records of the pair table (site and index in one entry) are gathered
-        // together, so that the loads of a round are in flight at once; the candidates are compared in list order
-        for (; q < e; q += UNROLL)
-        {
-            int mi[UNROLL];
-            double pix[UNROLL], piy[UNROLL], piz[UNROLL];
-#pragma unroll
-            for (int j = 0; j < UNROLL; ++j)
-            {
-                // (entries beyond the list read the last one and are ignored)
-                const double* pair = pairs + 4 * (int64_t)min(q + j, e - 1);
-                const double2 xy = *reinterpret_cast<const double2*>(pair);
-                const double2 zi = *reinterpret_cast<const double2*>(pair + 2);
-                pix[j] = xy.x, piy[j] = xy.y, piz[j] = zi.x;
-                mi[j] = (q + j < e) ? (int)__double_as_longlong(zi.y) : -7;  // -7: no neighbour
-            }
-#pragma unroll
-            for (int j = 0; j < UNROLL; ++j) voroCandidate(S, rx, ry, rz, kx, ky, kz, prx, pry, prz, mi[j], pix[j], piy[j], piz[j], sq, mq);
-        }
-        if (mq == NO_INDEX) return false;
-        w.cell = m;
-        w.ds = sq;
-        w.ci = mq;
-        w.cj = -1;  // (the next cell's run in an observer's table: not known from here, voroAdvance)
-        w.dens = przn.y;
-        return true;
-    }
-
-    // The same for a peel-off walk towards the observer with table `tab` (DevScene::vobs_run): the cell's header and its kept entries are one run
-    // of memory that starts at unit `run`; header and the first FIRST entries are requested together (entries beyond the cell's own are read
-    // and ignored: they belong to the next run or the padding), further rounds of FIRST follow only for cells with more.  The winner's entry
-    // names the next cell AND its run (w.ci, w.cj).
-    template<int FIRST> __device__ __forceinline__ bool voroEnterRun(const DevScene& S, Walk& w, int m, uint32_t run, int tab)
-    {
-        const double* const runs = tab == 0 ? S.vobs_run[0] : tab == 1 ? S.vobs_run[1] : tab == 2 ? S.vobs_run[2] : S.vobs_run[3];
-        const double* const rec = runs + 8 * (int64_t)(run & PMC_VORO_RUN_UNIT_MASK);  // (the link's count is for the kernels with lane pairs)
-        const double2 prxy = *reinterpret_cast<const double2*>(rec);
-        const double2 przn = *reinterpret_cast<const double2*>(rec + 2);
-        const int cnt = *reinterpret_cast<const int*>(rec + 4);
-        const double prx = prxy.x, pry = prxy.y, prz = przn.x;
-        const double rx = w.rx, ry = w.ry, rz = w.rz, kx = w.kx, ky = w.ky, kz = w.kz;
-        double sq = DBL_MAX;
-        const int NO_INDEX = -99;
-        int mq = NO_INDEX;
-        uint32_t runq = 0u;
-        int q = 0;
-        do
-        {
-            int mi[FIRST];
-            uint32_t ri[FIRST];
-            double pix[FIRST], piy[FIRST], piz[FIRST];
-#pragma unroll
-            for (int j = 0; j < FIRST; ++j)
-            {
-                // (first round: whatever lies behind the header; later rounds: entries beyond the list read the last one and are ignored;
-                // entry e: group e / LANES, {x, y} at word e % LANES of the group, {z, tag} LANES words on)
-                const int e = q == 0 ? j : min(q + j, cnt - 1);
-                const double* pair = rec + 8 + 4 * PMC_VORO_RUN_LANES * (int64_t)(e / PMC_VORO_RUN_LANES) + 2 * (e % PMC_VORO_RUN_LANES);
-                const double2 xy = *reinterpret_cast<const double2*>(pair);
-                const double2 zi = *reinterpret_cast<const double2*>(pair + 2 * PMC_VORO_RUN_LANES);
-                const long long tag = __double_as_longlong(zi.y);
-                pix[j] = xy.x, piy[j] = xy.y, piz[j] = zi.x;
-                mi[j] = (int)tag;
-                ri[j] = (uint32_t)((unsigned long long)tag >> 32);
-            }
-#pragma unroll
-            for (int j = 0; j < FIRST; ++j)
-            {
-                const int before = mq;
-                voroCandidate(S, rx, ry, rz, kx, ky, kz, prx, pry, prz, (q + j < cnt) ? mi[j] : -7, pix[j], piy[j], piz[j], sq, mq);
-                if (mq != before) runq = ri[j];
-            }
-            q += FIRST;
-        } while (q < cnt);
-        if (mq == NO_INDEX) return false;
-        w.cell = m;
-        w.ds = sq;
-        w.ci = mq;
-        w.cj = (int)runq;
-        w.dens = przn.y;
-        return true;
-    }
-
-    // cell of the position of w and its exit; while no exit is found the position moves on by eps (:1153-1164).
-    // Returns false when the position leaves the domain that way.
-    // known: the cell of the position if the caller has located it already (every walk of a cycle starts at the same
-    // position), -2 otherwise
-    __device__ __forceinline__ bool voroLocateAndEnter(const DevScene& S, Walk& w, int known = -2)
-    {
-        int m = known != -2 ? known : voroCellIndex(S, w.rx, w.ry, w.rz);
-        while (true)
-        {
-            if (m < 0) return false;
-            if (voroEnter<1>(S, w, m)) return true;
-            w.rx += w.kx * S.eps;
-            w.ry += w.ky * S.eps;
-            w.rz += w.kz * S.eps;
-            m = voroCellIndex(S, w.rx, w.ry, w.rz);
-        }
-    }
-
-    // after the pending segment: propagate to just beyond the exit (:1169) and prepare the next cell's segment
-    // RUNS_ONLY: the caller's walks all have a table (the Voronoi peel-off kernel)
-    template<bool RUNS_ONLY = false> __device__ __forceinline__ int voroEnterNext(const DevScene& S, Walk& w, int next, int tab = -1)
-    {
-        if (tab >= 0 || RUNS_ONLY)
-        {
-            // (w.cj: the run of the next cell, named by the entry the walk left through; -1 in the first visit of a walk, whose task record
-            // knows the cell only)
-            uint32_t run = (uint32_t)w.cj;
-            if (run == 0xFFFFFFFFu)
-                run = (tab == 0 ? S.vobs_start[0] : tab == 1 ? S.vobs_start[1] : tab == 2 ? S.vobs_start[2] : S.vobs_start[3])[next];
-            return voroEnterRun<PMC_VORO_RUN_FIRST>(S, w, next, run, tab) ? ST_ACTIVE : ST_SLOW;
-        }
-        return voroEnter<PMC_VORO_UNROLL>(S, w, next) ? ST_ACTIVE : ST_SLOW;
-    }
-    __device__ __forceinline__ void voroMove(const DevScene& S, Walk& w)
-    {
-        const double step = w.ds + S.eps;
-        w.rx += w.kx * step;
-        w.ry += w.ky * step;
-        w.rz += w.kz * step;
-    }
-    template<bool RUNS_ONLY = false> __device__ __forceinline__ int voroAdvance(const DevScene& S, Walk& w, int tab = -1)
-    {
-        voroMove(S, w);
-        const int next = w.ci;
-        if (next < 0) return ST_EXIT;
-        return voroEnterNext<RUNS_ONLY>(S, w, next, tab);
-    }
-    // a cell without exit (ST_SLOW): :1153-1164
-    __device__ __forceinline__ bool voroStepSlow(const DevScene& S, Walk& w)
-    {
-        w.rx += w.kx * S.eps;
-        w.ry += w.ky * S.eps;
-        w.rz += w.kz * S.eps;
-        return voroLocateAndEnter(S, w);
-    }
-
+#include "pmc_walk_voro.inc"
 #include "pmc_walk_bin.inc"
 
     // ------------------------------------------------------------------------------------------------
@@ -1412,750 +1068,4 @@
             }
         }
         flushWalkCounters(S, lane, paths, visits, rewalks);
-    }
-
-    // ================================================================================================
-    //  Voronoi: the peel-off walks towards ONE observer that has a table of runs (DevScene::vobs_run) as a kernel of their own.
-    //  Of the generic kernel's lane state (three kinds of walks, two passes, sampling, records of a slot: 168 registers and scratch) such a
-    //  walk needs position, depth, the pending segment and the next cell's run; the direction and the table are wave-uniform.  The walks
-    //  come as the observer's list of slots in tile order (cycle start kernel), taken with the XCD affinity of the generic stream.
-    //  MediumSystem::getExtinctionOpticalDepth (MediumSystem.cpp:1192-1260) on VoronoiMeshSnapshot::MySegmentGenerator (:1058-1188).
-    // ================================================================================================
-    // quad permutations of the lanes that share a walk: the value of lane ^ 1 / lane ^ 2
-    __device__ __forceinline__ int quadXor1(int v) { return __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false); }
-    __device__ __forceinline__ int quadXor2(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false); }
-    template<int MASK> __device__ __forceinline__ int quadXor(int v) { return MASK == 1 ? quadXor1(v) : quadXor2(v); }
-    template<int MASK> __device__ __forceinline__ double quadXor(double v)
-    {
-        const long long b = __double_as_longlong(v);
-        const uint32_t lo = (uint32_t)quadXor<MASK>((int)(uint32_t)b), hi = (uint32_t)quadXor<MASK>((int)(uint32_t)((unsigned long long)b >> 32));
-        return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-    }
-
-    // MM: several medium components (round 6): the extinction optical depth of a segment is summed over the components in order
-    // (MediumSystem.cpp:1225-1242); the walk keeps the index of its cell for the densities of components 1.. (the header holds component 0's)
-    template<bool MM>
-    __global__ __launch_bounds__(256, PMC_VPEEL_MIN_WAVES) void voroPeelKernel(const int sceneSlot, const int rec, const int tab, const int32_t* __restrict__ list,
-                                                                                const unsigned long long* __restrict__ count, unsigned long long* xcdCursor,
-                                                                                const int segments)
-    {
-        const DevScene& S = c_scene[sceneSlot];
-        const SlotArrays& A = S.slots;
-        const TaskArrays& K = S.tasks;
-        const int lane = threadIdx.x & 63;
-        constexpr int LANES = PMC_VORO_RUN_LANES;  // lanes per walk: what bounds this kernel is the rate at which a CU's vector memory unit takes
-        static_assert(LANES == 2 || LANES == 4, "lanes per walk");
-        const int sub = lane & (LANES - 1);        // addresses (one per lane and load unless neighbouring lanes read neighbouring words): the lanes of
-        const bool leader = sub == 0;              // a walk read a group of entries with two coalesced loads and look at one entry each
-        const unsigned long long numTasks = *count;
-        const DevInstrument& I = S.inst[rec - 1];
-        const double kx = I.kx, ky = I.ky, kz = I.kz;  // (what the cycle start kernel wrote into every task record of this observer)
-        const double* const runs = tab == 0 ? S.vobs_run[0] : tab == 1 ? S.vobs_run[1] : tab == 2 ? S.vobs_run[2] : S.vobs_run[3];
-        const uint32_t* const starts = tab == 0 ? S.vobs_start[0] : tab == 1 ? S.vobs_start[1] : tab == 2 ? S.vobs_start[2] : S.vobs_start[3];
-        constexpr int NO_INDEX = -99;
-        constexpr int ROWS = PMC_VPEEL_ROWS;
-        // the lanes of a walk all carry the walk (position just inside the cell it scans, depth so far) and their part of the scan of that cell's
-        // run (DevScene::vobs_run): one group of entries per step, every walk at its own place in its own cell -- no walk waits for the longest
-        // list of the wave
-        double rx = 0., ry = 0., rz = 0., tau = 0., target = 0., sext = 0.;
-        double prx = 0., pry = 0., prz = 0., dens = 0., sq = DBL_MAX;
-        int mq = NO_INDEX, iq = 0x7fffffff, q = 0, cnt = 0;
-        uint32_t run = 0u, runq = 0u;
-        int slot = -1;
-        int cell = -1;  // (MM) the cell of the pending segment
-        double mx[PMC_MAX_MEDIA] = {0., 0., 0., 0.}, msc[PMC_MAX_MEDIA] = {0., 0., 0., 0.}, mab[PMC_MAX_MEDIA] = {0., 0., 0., 0.};  // (MM) per component
-        int st = ST_IDLE;
-        uint32_t nseg = 0, visits = 0;
-        uint32_t xcdSeg = 0u, xcdTried = 0u;
-        if (segments > 1)
-        {
-            uint32_t v;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-            xcdSeg = v & 7u;
-        }
-        bool exhausted = false;
-        unsigned long long poolNext = 0, poolEnd = 0;  // wave-uniform
-        const unsigned long long leaders = LANES == 4 ? 0x1111111111111111ull : 0x5555555555555555ull;
-
-        // the pending segment (length ds through a cell of density `dens`, left through neighbour or wall ci) joins the path
-        // (MediumSystem.cpp:1207-1219: stop once tau >= taumax; every segment the generator emits counts), and the position moves to just beyond
-        // its end (VoronoiMeshSnapshot.cpp:1169)
-#define PMC_VPEEL_SEGMENT(ds_, ci_, run_)                        \
-    {                                                            \
-        double tau1_ = tau + sext * dens * (ds_);                \
-        if (MM)                                                  \
-        {                                                        \
-            double none_ = 0.;                                   \
-            tau1_ = tau;                                         \
-            mediaSegment<false>(S, cell, dens, (ds_), false, mx, msc, mab, tau1_, none_); \
-        }                                                        \
-        if (tau1_ > target)                                      \
-            st = ST_HIT;                                         \
-        else                                                     \
-        {                                                        \
-            tau = tau1_;                                         \
-            nseg += 1;                                           \
-            const double step_ = (ds_) + S.eps;                  \
-            rx += kx * step_, ry += ky * step_, rz += kz * step_; \
-            if ((ci_) < 0)                                       \
-                st = ST_EXIT;                                    \
-            else                                                 \
-            {                                                    \
-                if (MM) cell = (ci_);                            \
-                run = (run_);                                    \
-                q = 0;                                           \
-                st = ST_ACTIVE;                                  \
-            }                                                    \
-        }                                                        \
-    }
-
-        while (true)
-        {
-            const unsigned long long activeMask = __ballot(st == ST_ACTIVE);
-            const unsigned long long pendingMask = __ballot(st != ST_ACTIVE && st != ST_IDLE);
-            if (exhausted && !activeMask && !pendingMask) break;
-            // ---------------- service: cells without an exit, finished walks, new walks (as the generic kernel's, for one kind of walk)
-            if (exhausted ? (pendingMask != 0ull) : (64 - __popcll(activeMask) >= PMC_VPEEL_REFILL))
-            {
-                bool pending = false;  // a walk with a pending segment whose next cell's run has to be looked up
-                double pds = 0.;
-                int pci = -1;
-                if (st == ST_SLOW)
-                {
-                    // no exit from the position in the cell the walk entered: the literal algorithm (:1153-1164) on the plain tables
-                    // (every lane of the walk for itself: the same result)
-                    Walk w;
-                    w.rx = rx, w.ry = ry, w.rz = rz, w.kx = kx, w.ky = ky, w.kz = kz;
-                    if (voroStepSlow(S, w))
-                    {
-                        rx = w.rx, ry = w.ry, rz = w.rz;
-                        dens = w.dens, pds = w.ds, pci = w.ci;
-                        if (MM) cell = w.cell;
-                        pending = true;
-                    }
-                    else
-                        st = ST_EXIT;
-                }
-                if (st == ST_HIT || st == ST_EXIT)
-                {
-                    // tau >= taumax: the packet does not arrive (MediumSystem.cpp:1215-1218); else the depth of the whole path
-                    if (leader)
-                    {
-                        A.ptau[(int64_t)(rec - 1) * A.num_slots + slot] = st == ST_HIT ? (double)INFINITY : tau;
-                        visits += nseg + (st == ST_HIT ? 1u : 0u);
-                    }
-                    st = ST_IDLE;
-                }
-                if (!exhausted)
-                {
-                    const unsigned long long idle = __ballot(st == ST_IDLE) & leaders;
-                    const int nidle = __popcll(idle);
-                    while (nidle && poolNext >= poolEnd && !exhausted)
-                    {
-                        if (xcdTried >= (uint32_t)segments)
-                        {
-                            poolNext = poolEnd = 0;
-                            exhausted = true;
-                            break;
-                        }
-                        const unsigned long long lo = (numTasks * xcdSeg) / (uint32_t)segments, hi = (numTasks * (xcdSeg + 1u)) / (uint32_t)segments;
-                        unsigned long long got = 0;
-                        if (lane == 0) got = atomicAdd(xcdCursor + xcdSeg, (unsigned long long)PMC_TASK_CHUNK);
-                        got = __shfl(got, 0, 64);
-                        if (lo + got < hi)
-                        {
-                            poolNext = lo + got;
-                            poolEnd = lo + got + PMC_TASK_CHUNK < hi ? lo + got + PMC_TASK_CHUNK : hi;
-                        }
-                        else
-                        {
-                            xcdSeg = xcdSeg + 1u < (uint32_t)segments ? xcdSeg + 1u : 0u;
-                            xcdTried += 1u;
-                        }
-                    }
-                    const unsigned long long base = poolNext;
-                    const unsigned long long avail = poolEnd - poolNext;
-                    poolNext += (unsigned long long)nidle < avail ? (unsigned long long)nidle : avail;
-                    if (st == ST_IDLE && !exhausted)
-                    {
-                        // (the idle walks before this one in the wave: the lanes of a walk find the same rank)
-                        const unsigned long long rank = __popcll(idle & ((1ull << (lane - sub)) - 1ull));
-                        if (rank < avail)
-                        {
-                            slot = list[base + rank];
-                            const int64_t t = (int64_t)rec * A.num_slots + slot;
-                            if (K.bits[t] != PMC_TASK_NONE)
-                            {
-                                // the start state of the walk: position in its first cell, that cell's exit (cycle start kernel)
-                                rx = K.rx[t], ry = K.ry[t], rz = K.rz[t];
-                                pci = K.cijk[t];
-                                target = K.target[t];
-                                const int cell0 = K.cell[t];
-                                if (MM)
-                                {
-                                    cell = cell0;
-                                    for (int h = 0; h < S.num_media; ++h) mediumSections(S, A, slot, h, mx[h], msc[h], mab[h]);
-                                }
-                                sext = S.mono ? S.mono_ext : A.dustExt[slot];
-                                tau = 0.;
-                                nseg = 0;
-                                if (pci == PMC_VORO_FIRST_SCAN)
-                                {
-                                    // (the cycle start kernel has located the first cell only: its scan is the first step of the walk)
-                                    run = starts[cell0];
-                                    q = 0;
-                                    st = ST_ACTIVE;
-                                }
-                                else
-                                {
-                                    pds = K.ds[t];
-                                    dens = S.vsite[4 * (int64_t)cell0 + 3];
-                                    pending = true;
-                                }
-                            }
-                        }
-                    }
-                }
-                if (pending) PMC_VPEEL_SEGMENT(pds, pci, starts[pci])
-            }
-            // ---------------- scan steps: one group of entries of the walk's cell each, an entry per lane; the last one of a cell ends its segment
-            // and enters the next cell
-#pragma unroll 1
-            for (int it = 0; it < PMC_WALK_STEPS; ++it)
-            {
-                if (st == ST_ACTIVE)
-                {
-                    const double* const cellRun = runs + 8 * (int64_t)(run & PMC_VORO_RUN_UNIT_MASK);
-                    const uint32_t linked = run >> PMC_VORO_RUN_UNIT_BITS;  // the number of entries as the link names it
-                    if (q == 0)
-                    {
-                        // the header: site, density, number of entries -- requested together with the first group behind it
-                        const double2 prxy = *reinterpret_cast<const double2*>(cellRun);
-                        const double2 przn = *reinterpret_cast<const double2*>(cellRun + 2);
-                        cnt = (int)linked;
-                        if (linked == PMC_VORO_RUN_COUNT_UNKNOWN) cnt = *reinterpret_cast<const int*>(cellRun + 4);
-                        prx = prxy.x, pry = prxy.y, prz = przn.x, dens = przn.y;
-                        sq = DBL_MAX;
-                        mq = NO_INDEX;
-                        iq = 0x7fffffff;
-                    }
-                    // ROWS groups in one round trip (most cells have no more entries than that): lane `sub` looks at entry q + e LANES + sub
-                    const double* const group = cellRun + 8 + 4 * q;  // (q: a multiple of LANES; 4 doubles per entry)
-                    double2 xy[ROWS], zi[ROWS];
-#pragma unroll
-                    for (int e = 0; e < ROWS; ++e)
-                    {
-                        // (exactly the groups the cell has: the link named their number; a cell with more than 30 entries learns it from its header,
-                        // its first groups go out unconditionally)
-                        // (no value: a group that is not requested is not looked at -- its candidate is "no entry" whatever the registers hold)
-                        asm volatile("" : "=v"(xy[e].x), "=v"(xy[e].y), "=v"(zi[e].x), "=v"(zi[e].y));
-                        if ((q == 0 && linked == PMC_VORO_RUN_COUNT_UNKNOWN) || q + e * LANES < cnt)
-                        {
-                            xy[e] = *reinterpret_cast<const double2*>(group + 4 * LANES * e + 2 * sub);
-                            zi[e] = *reinterpret_cast<const double2*>(group + 4 * LANES * e + 2 * LANES + 2 * sub);
-                        }
-                    }
-#pragma unroll
-                    for (int e = 0; e < ROWS; ++e)
-                    {
-                        const long long tag = __double_as_longlong(zi[e].y);
-                        const int at = q + e * LANES + sub;
-                        const int before = mq;
-                        voroCandidatePair(S, rx, ry, rz, kx, ky, kz, prx, pry, prz, (at < cnt) ? (int)tag : -7, xy[e].x, xy[e].y, zi[e].x, sq, mq);
-                        if (mq != before) runq = (uint32_t)((unsigned long long)tag >> 32), iq = at;
-                    }
-                    q += ROWS * LANES;
-                    if (q >= cnt)
-                    {
-                        // the smallest distance of the lanes' own (equal distances: the earlier entry of the list, as the reference's loop keeps it)
-                        {
-                            const double osq = quadXor<1>(sq);
-                            const int oiq = quadXor<1>(iq), omq = quadXor<1>(mq), orun = quadXor<1>((int)runq);
-                            if (osq < sq || (osq == sq && oiq < iq)) sq = osq, iq = oiq, mq = omq, runq = (uint32_t)orun;
-                        }
-                        if (LANES == 4)
-                        {
-                            const double osq = quadXor<2>(sq);
-                            const int oiq = quadXor<2>(iq), omq = quadXor<2>(mq), orun = quadXor<2>((int)runq);
-                            if (osq < sq || (osq == sq && oiq < iq)) sq = osq, iq = oiq, mq = omq, runq = (uint32_t)orun;
-                        }
-                        if (mq == NO_INDEX)
-                            st = ST_SLOW;
-                        else
-                            PMC_VPEEL_SEGMENT(sq, mq, runq)
-                    }
-                }
-            }
-        }
-#undef PMC_VPEEL_SEGMENT
-        const unsigned long long v = waveSum(visits);
-        if (lane == 0 && v) atomicAdd(S.counters + 2, v);
-    }
-
-    // ================================================================================================
-    //  Voronoi: the PROPAGATION walks (record 0 of the slots in `list`: the slots that have one, sorted by the sign octant of their direction) in the
-    //  form of voroPeelKernel: two lanes per walk on the table of runs that holds ALL neighbours of a cell (DevScene::vgen_run: no mask, one run
-    //  of memory per visit), every walk at its own place in its own cell.  Pass 1 over the whole path (setExtinctionOpticalDepths,
-    //  MediumSystem.cpp:849-871), simulateForcedPropagation between the passes (MonteCarloSimulation.cpp:696-722), pass 2 from the start of the
-    //  path up to the sampled depth (findInteractionPoint, SpatialGridPath.cpp:164-206); without forced scattering one walk up to the drawn depth.
-    //  Flavours (round 6; rounds 4-5 ran them in walkKernel), as in the octree's propagation kernel: RF stores the radiation field along pass 1
-    //  (MonteCarloSimulation.cpp:638-662; f64 atomics into the table: a Voronoi grid has no log), EA is the explicit-absorption cycle (scattering and
-    //  absorption depths apart, MediumSystem.cpp:905-932, 1075-1110; no pass-1 checkpoints), MM sums a segment over several medium components
-    //  (MediumSystem.cpp:874-887, 934-955; no checkpoints either).
-    // ================================================================================================
-    template<bool RF, bool EA, bool MM>
-    __global__ __launch_bounds__(256, PMC_VPROP_MIN_WAVES) void voroPropKernel(const int sceneSlot, const int32_t* __restrict__ list,
-                                                                                const unsigned long long* __restrict__ count, unsigned long long* xcdCursor,
-                                                                                const int segments, const uint64_t seed)
-    {
-        const DevScene& S = c_scene[sceneSlot];
-        const SlotArrays& A = S.slots;
-        const TaskArrays& K = S.tasks;
-        const int lane = threadIdx.x & 63;
-        constexpr int LANES = PMC_VORO_RUN_LANES;
-        static_assert(LANES == 2 || LANES == 4, "lanes per walk");
-        const int sub = lane & (LANES - 1);
-        const bool leader = sub == 0;
-        const unsigned long long numTasks = *count;
-        // (the table of the walk's direction cone, or the one with all neighbours)
-        const double* runs = S.vgen_run;
-        const uint32_t* starts = S.vgen_start;
-        const bool coneTables = S.vcone_run[0] != nullptr;
-        const bool force = S.force_scattering != 0;
-        constexpr int NO_INDEX = -99;
-        constexpr int ROWS = PMC_VPROP_ROWS;
-        double rx = 0., ry = 0., rz = 0., kx = 0., ky = 0., kz = 1., tau = 0., s = 0., ds = 0., target = 0., sext = 0.;
-        double prx = 0., pry = 0., prz = 0., dens = 0., sq = DBL_MAX;
-        int mq = NO_INDEX, iq = 0x7fffffff, q = 0, cnt = 0;
-        uint32_t run = 0u, runq = 0u;
-        int slot = -1, cell = -1, lastm = -1;
-        int st = ST_IDLE;
-        uint32_t mode = MODE_NONE;
-        uint32_t nseg = 0, visits = 0, rewalks = 0, paths = 0;
-        uint32_t xcdSeg = 0u, xcdTried = 0u;
-        if (segments > 1)
-        {
-            uint32_t v;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-            xcdSeg = v & 7u;
-        }
-        bool exhausted = false;
-        unsigned long long poolNext = 0, poolEnd = 0;  // wave-uniform
-        const unsigned long long leaders = LANES == 4 ? 0x1111111111111111ull : 0x5555555555555555ull;
-        // pass 2 without walking the whole path again: the two walker states of the octree's propagation kernel (pmc_walk_tree.inc, there with the
-        // derivation) -- A certainly at or before the interaction point, B a later candidate, advanced on a lower bound of the depth that will be
-        // sampled (the uniforms are drawn before the walk) on a wave-uniform tick; pass 2 resumes from the later one that is valid for the depth
-        // actually sampled.  A state = the walk between two cells (position in the cell it is about to scan, depth and length so far, that cell
-        // and its run, the last cell of the path): valid at any moment, since a scan changes none of it.  In LDS, per walk.
-        constexpr int WALKS = 256 / LANES;
-        __shared__ double ckState[2 * 7 * WALKS];
-        __shared__ double ckUniform[WALKS];
-        const int walkIndex = (int)threadIdx.x / LANES;
-        uint32_t ck = 0u;  // CK_SEL: the slot of the candidate; CK_HASA / CK_HASB; CK_LIN: the uniform branch of the path-length bias
-        constexpr uint32_t CK_SEL = 1u, CK_HASA = 2u, CK_HASB = 4u, CK_LIN = 8u;
-        const bool checkpoints = force && S.voro_prop_checkpoints != 0 && !EA && !MM;
-        double ssca = 0., sabs = 0., tabs = 0.;  // (EA) cross sections of the walk, cumulative absorption optical depth
-        double mx[PMC_MAX_MEDIA] = {0., 0., 0., 0.}, msc[PMC_MAX_MEDIA] = {0., 0., 0., 0.}, mab[PMC_MAX_MEDIA] = {0., 0., 0., 0.};  // (MM) per component
-        double rfL = 0., rfExtBeg = 1.;  // (RF) the packet's luminosity on this path, exp(-tau) at the start of the pending segment
-        int rfEll = -1;
-
-        // the pending segment (length ds_ through `cell`, density `dens`, left through neighbour or wall ci_): MediumSystem.cpp:863-871 (pass 1),
-        // SpatialGridPath.cpp:177-196 (pass 2: stop in the first segment with tau > target), MediumSystem.cpp:988-1008 (non-forced); then the
-        // position moves to just beyond its end (VoronoiMeshSnapshot.cpp:1169).  SpatialGridPath::addSegment keeps segments with ds > 0 only; the
-        // non-forced loop runs over every segment the generator emits
-#define PMC_VPROP_SEGMENT(ds_, ci_, run_)                        \
-    {                                                            \
-        ds = (ds_);                                              \
-        double tau1_ = tau + sext * dens * ds, tabs1_ = 0.;      \
-        if (MM)                                                  \
-        {                                                        \
-            tau1_ = tau, tabs1_ = tabs;                          \
-            mediaSegment<EA>(S, cell, dens, ds, true, mx, msc, mab, tau1_, tabs1_); \
-        }                                                        \
-        else if (EA)                                             \
-        {                                                        \
-            const double ns_ = dens * ds;                        \
-            tau1_ = force ? tau + ssca * ns_ : tau + ssca * dens * ds; \
-            tabs1_ = tabs + sabs * ns_;                          \
-        }                                                        \
-        if (tau1_ > target)                                      \
-            st = ST_HIT;                                         \
-        else                                                     \
-        {                                                        \
-            const double tau0_ = tau, tabs0_ = tabs;             \
-            tau = tau1_;                                         \
-            if (EA) tabs = tabs1_;                               \
-            s += ds;                                             \
-            if (ds > 0. || !force)                               \
-            {                                                    \
-                lastm = cell;                                    \
-                nseg += 1;                                       \
-            }                                                    \
-            if (RF && mode == MODE_PASS1 && ds > 0.)             \
-            {                                                    \
-                const double lnExtEnd_ = EA ? -(tau1_ + tabs1_) : -tau1_; \
-                const double extEnd_ = exp(lnExtEnd_);           \
-                if (rfEll >= 0 && leader)                        \
-                    unsafeAtomicAdd(S.rf + ((int64_t)cell * S.rf_num_lambda + rfEll),       \
-                                    rfL * lnmean(extEnd_, rfExtBeg, lnExtEnd_, EA ? -(tau0_ + tabs0_) : -tau0_) * ds); \
-                rfExtBeg = extEnd_;                              \
-            }                                                    \
-            const double step_ = ds + S.eps;                     \
-            rx += kx * step_, ry += ky * step_, rz += kz * step_; \
-            if ((ci_) < 0)                                       \
-                st = ST_EXIT;                                    \
-            else                                                 \
-            {                                                    \
-                cell = (ci_);                                    \
-                run = (run_);                                    \
-                q = 0;                                           \
-                st = ST_ACTIVE;                                  \
-            }                                                    \
-        }                                                        \
-    }
-
-        while (true)
-        {
-            const unsigned long long activeMask = __ballot(st == ST_ACTIVE);
-            const unsigned long long pendingMask = __ballot(st != ST_ACTIVE && st != ST_IDLE);
-            if (exhausted && !activeMask && !pendingMask) break;
-            // ---------------- service: cells without an exit, finished walks (results; pass 1 -> pass 2), new walks
-            if (exhausted ? (pendingMask != 0ull) : (64 - __popcll(activeMask) >= PMC_VPROP_REFILL))
-            {
-                bool pending = false;  // a walk with a pending segment whose next cell's run has to be looked up
-                double pds = 0.;
-                int pci = -1;
-                if (st == ST_SLOW)
-                {
-                    // no exit from the position in the cell the walk entered: the literal algorithm (:1153-1164) on the plain tables
-                    Walk w;
-                    w.rx = rx, w.ry = ry, w.rz = rz, w.kx = kx, w.ky = ky, w.kz = kz;
-                    if (voroStepSlow(S, w))
-                    {
-                        rx = w.rx, ry = w.ry, rz = w.rz;
-                        cell = w.cell, dens = w.dens, pds = w.ds, pci = w.ci;
-                        pending = true;
-                    }
-                    else
-                        st = ST_EXIT;
-                }
-                bool again = false;
-                double taupath = 0.;
-                if (st == ST_HIT || st == ST_EXIT)
-                {
-                    if (st == ST_HIT)
-                    {
-                        // findInteractionPoint (SpatialGridPath.cpp:177-196): first segment with tau > target
-                        nseg += 1;
-                        if (leader)
-                        {
-                            const double s1 = s + ds;
-                            A.mint[slot] = cell;
-                            if (MM)
-                            {
-                                double tau1 = tau, tabs1 = tabs;
-                                mediaSegment<EA>(S, cell, dens, ds, true, mx, msc, mab, tau1, tabs1);
-                                const double f = (target - tau) / (tau1 - tau);
-                                A.nint[slot] = EA ? tabs + f * (tabs1 - tabs) : dens;
-                                A.sint[slot] = s + f * (s1 - s);
-                            }
-                            else if (EA)
-                            {
-                                // (the absorption depth at the interaction point: as walkKernel forms it)
-                                const double ns = dens * ds;
-                                const double tau1 = force ? tau + ssca * ns : tau + ssca * dens * ds;
-                                const double f = (target - tau) / (tau1 - tau);
-                                A.nint[slot] = force ? tabs + f * ((tabs + sabs * ns) - tabs) : target * sabs / ssca;
-                                A.sint[slot] = s + f * (s1 - s);
-                            }
-                            else
-                            {
-                                const double tau1 = tau + sext * dens * ds;
-                                A.nint[slot] = dens;
-                                A.sint[slot] = s + ((target - tau) / (tau1 - tau)) * (s1 - s);
-                            }
-                        }
-                    }
-                    else if (mode == MODE_PASS1 && tau > 0.)
-                    {
-                        again = true;
-                        taupath = tau;
-                    }
-                    else if (leader)
-                    {
-                        if (mode != MODE_PASS1 && force && lastm >= 0)
-                        {
-                            // beyond the last segment (SpatialGridPath.cpp:198-204)
-                            A.mint[slot] = lastm;
-                            A.sint[slot] = s;
-                            A.nint[slot] = EA ? tabs : S.vsite[4 * (int64_t)lastm + 3];
-                        }
-                        else
-                            A.mint[slot] = -1;  // tau_path <= 0, or no forced scattering: the history ends / the packet escapes
-                    }
-                    if (leader)
-                    {
-                        if (mode == MODE_PASS2 && force)
-                            rewalks += nseg;
-                        else
-                            visits += nseg;
-                    }
-                    st = ST_IDLE;
-                }
-                // ---- new walks for the idle pairs
-                bool refill = false;
-                if (!exhausted)
-                {
-                    const unsigned long long idle = __ballot(st == ST_IDLE && !again) & leaders;
-                    const int nidle = __popcll(idle);
-                    while (nidle && poolNext >= poolEnd && !exhausted)
-                    {
-                        if (xcdTried >= (uint32_t)segments)
-                        {
-                            poolNext = poolEnd = 0;
-                            exhausted = true;
-                            break;
-                        }
-                        const unsigned long long lo = (numTasks * xcdSeg) / (uint32_t)segments, hi = (numTasks * (xcdSeg + 1u)) / (uint32_t)segments;
-                        unsigned long long got = 0;
-                        if (lane == 0) got = atomicAdd(xcdCursor + xcdSeg, (unsigned long long)PMC_TASK_CHUNK);
-                        got = __shfl(got, 0, 64);
-                        if (lo + got < hi)
-                        {
-                            poolNext = lo + got;
-                            poolEnd = lo + got + PMC_TASK_CHUNK < hi ? lo + got + PMC_TASK_CHUNK : hi;
-                        }
-                        else
-                        {
-                            xcdSeg = xcdSeg + 1u < (uint32_t)segments ? xcdSeg + 1u : 0u;
-                            xcdTried += 1u;
-                        }
-                    }
-                    const unsigned long long base = poolNext;
-                    const unsigned long long avail = poolEnd - poolNext;
-                    poolNext += (unsigned long long)nidle < avail ? (unsigned long long)nidle : avail;
-                    if (st == ST_IDLE && !again && !exhausted)
-                    {
-                        const unsigned long long rank = __popcll(idle & ((1ull << (lane - sub)) - 1ull));
-                        if (rank < avail)
-                        {
-                            slot = list[base + rank];
-                            refill = true;
-                        }
-                    }
-                }
-                // ---- the start state in task record 0: for a new walk, and again for pass 2 over the same path
-                if (again || refill)
-                {
-                    const int64_t t = slot;
-                    const uint32_t bits = K.bits[t];
-                    bool resumed = false;
-                    if (again)
-                    {
-                        // simulateForcedPropagation between the two passes: the whole path has been walked; the interaction optical depth follows
-                        // from the uniforms the transition kernel drew (startCycle), which wait in the result fields
-                        double drawn = 0.;
-                        if (leader) drawn = sampleForcedDepth(S, A, slot, seed, taupath, A.sint[slot], A.nint[slot]);
-                        const double other = quadXor<1>(drawn);
-                        target = (lane & 1) ? other : drawn;
-                        if (LANES == 4)
-                        {
-                            const double other2 = quadXor<2>(target);
-                            target = (lane & 2) ? other2 : target;
-                        }
-                        mode = MODE_PASS2;
-                        if (leader) paths += 1;
-                        // the later state that is valid for this depth: nothing before it can be the interaction segment if its depth has not
-                        // passed the sampled one
-                        int from = -1;
-                        if (ck & CK_HASB)
-                        {
-                            const int b = (int)(ck & CK_SEL);
-                            if (ckState[(b * 7 + 3) * WALKS + walkIndex] <= target) from = b;
-                        }
-                        if (from < 0 && (ck & CK_HASA))
-                        {
-                            const int a = (int)((ck & CK_SEL) ^ 1u);
-                            if (ckState[(a * 7 + 3) * WALKS + walkIndex] <= target) from = a;
-                        }
-                        if (from >= 0)
-                        {
-                            const double* const c = ckState + from * 7 * WALKS + walkIndex;
-                            rx = c[0 * WALKS], ry = c[1 * WALKS], rz = c[2 * WALKS];
-                            tau = c[3 * WALKS], s = c[4 * WALKS];
-                            const unsigned long long cr = (unsigned long long)__double_as_longlong(c[5 * WALKS]);
-                            cell = (int)(uint32_t)cr, run = (uint32_t)(cr >> 32);
-                            lastm = (int)(uint32_t)(unsigned long long)__double_as_longlong(c[6 * WALKS]);
-                            nseg = 0;
-                            q = 0;
-                            st = ST_ACTIVE;
-                            resumed = true;
-                        }
-                    }
-                    else
-                    {
-                        mode = bits & 3u;
-                        target = K.target[t];
-                        sext = S.mono ? S.mono_ext : A.dustExt[slot];
-                        ck = 0u;
-                        if (checkpoints && mode == MODE_PASS1 && bits != PMC_TASK_NONE)
-                        {
-                            // (the uniforms of this path's sampling wait in the result fields: startCycle)
-                            const double u1 = A.sint[slot], u2 = A.nint[slot];
-                            if (S.path_length_bias != 0. && u1 < S.path_length_bias) ck = CK_LIN;
-                            if (leader) ckUniform[walkIndex] = u2;
-                        }
-                    }
-                    if (EA)
-                    {
-                        ssca = S.mono ? S.mono_sca : A.dustSca[slot];
-                        sabs = S.mono ? S.mono_abs : A.dustAbs[slot];
-                        tabs = 0.;
-                    }
-                    if (MM)
-                        for (int h = 0; h < S.num_media; ++h) mediumSections(S, A, slot, h, mx[h], msc[h], mab[h]);
-                    if (RF && !again && mode == MODE_PASS1 && bits != PMC_TASK_NONE)
-                    {
-                        // the packet's luminosity and bin on this path (MonteCarloSimulation.cpp:638-662)
-                        rfL = A.W[slot] / (S.mono ? S.mono_lambda : A.lambda[slot]);
-                        rfEll = A.rfell[slot];
-                        rfExtBeg = 1.;
-                    }
-                    if (bits != PMC_TASK_NONE && !resumed)
-                    {
-                        rx = K.rx[t], ry = K.ry[t], rz = K.rz[t];
-                        kx = K.kx[t], ky = K.ky[t], kz = K.kz[t];
-                        if (coneTables)
-                        {
-                            const int c = voroCone(kx, ky, kz) >> 2;  // (the main cone of the four sub-cones of DevScene::vcull)
-                            runs = S.vcone_run[c];
-                            starts = S.vcone_start[c];
-                        }
-                        s = K.s0[t];
-                        pci = K.cijk[t];
-                        cell = K.cell[t];
-                        tau = 0.;
-                        lastm = -1;
-                        nseg = 0;
-                        if (pci == PMC_VORO_FIRST_SCAN)
-                        {
-                            // (the cycle start kernel has located the first cell only: its scan is the first step of the walk)
-                            run = starts[cell];
-                            q = 0;
-                            st = ST_ACTIVE;
-                        }
-                        else
-                        {
-                            pds = K.ds[t];
-                            dens = S.vsite[4 * (int64_t)cell + 3];
-                            pending = true;
-                        }
-                    }
-                }
-                if (pending) PMC_VPROP_SEGMENT(pds, pci, starts[pci])
-            }
-            // ---------------- checkpoints of the pass-1 walks (a wave-uniform tick, every PMC_VPROP_STEPS scan steps)
-            if (checkpoints)
-            {
-                const bool p1 = st == ST_ACTIVE && mode == MODE_PASS1 && tau > 0.;
-                bool save = p1 && !(ck & CK_HASB);
-                if (p1 && (ck & CK_HASB))
-                {
-                    // B is certain once the lower bound of the sampled depth has passed it: it becomes A, the current state the new B
-                    const double tauB = ckState[((int)(ck & CK_SEL) * 7 + 3) * WALKS + walkIndex];
-                    const double bound = ckUniform[walkIndex] * tau;
-                    const double need = (ck & CK_LIN) ? tauB : tauB * (1. + tau) * (1. + 1e-13);
-                    if (bound >= need)
-                    {
-                        ck = (ck ^ CK_SEL) | CK_HASA;
-                        save = true;
-                    }
-                }
-                if (save)
-                {
-                    if (leader)
-                    {
-                        double* const c = ckState + (int)(ck & CK_SEL) * 7 * WALKS + walkIndex;
-                        c[0 * WALKS] = rx, c[1 * WALKS] = ry, c[2 * WALKS] = rz;
-                        c[3 * WALKS] = tau, c[4 * WALKS] = s;
-                        c[5 * WALKS] = __longlong_as_double((long long)((unsigned long long)(uint32_t)cell | ((unsigned long long)run << 32)));
-                        c[6 * WALKS] = __longlong_as_double((long long)(unsigned long long)(uint32_t)lastm);
-                    }
-                    ck |= CK_HASB;
-                }
-            }
-            // ---------------- scan steps: ROWS groups of entries of the walk's cell each, ROWS entries per lane; the last one of a cell ends its
-            // segment and enters the next cell
-#pragma unroll 1
-            for (int it = 0; it < PMC_VPROP_STEPS; ++it)
-            {
-                if (st == ST_ACTIVE)
-                {
-                    const double* const cellRun = runs + 8 * (int64_t)(run & PMC_VORO_RUN_UNIT_MASK);
-                    const uint32_t linked = run >> PMC_VORO_RUN_UNIT_BITS;  // the number of entries as the link names it
-                    if (q == 0)
-                    {
-                        const double2 prxy = *reinterpret_cast<const double2*>(cellRun);
-                        const double2 przn = *reinterpret_cast<const double2*>(cellRun + 2);
-                        cnt = (int)linked;
-                        if (linked == PMC_VORO_RUN_COUNT_UNKNOWN) cnt = *reinterpret_cast<const int*>(cellRun + 4);
-                        prx = prxy.x, pry = prxy.y, prz = przn.x, dens = przn.y;
-                        sq = DBL_MAX;
-                        mq = NO_INDEX;
-                        iq = 0x7fffffff;
-                    }
-                    const double* const group = cellRun + 8 + 4 * q;  // (q: a multiple of LANES; 4 doubles per entry)
-                    double2 xy[ROWS], zi[ROWS];
-#pragma unroll
-                    for (int e = 0; e < ROWS; ++e)
-                    {
-                        // (exactly the groups the cell has -- the link named their number --: groups beyond the run would be lines of other cells,
-                        // fetched from beyond L2 for nothing; a cell with more than 30 entries learns its number from the header)
-                        // (no value: a group that is not requested is not looked at -- its candidate is "no entry" whatever the registers hold)
-                        asm volatile("" : "=v"(xy[e].x), "=v"(xy[e].y), "=v"(zi[e].x), "=v"(zi[e].y));
-                        if ((q == 0 && linked == PMC_VORO_RUN_COUNT_UNKNOWN) || q + e * LANES < cnt)
-                        {
-                            xy[e] = *reinterpret_cast<const double2*>(group + 4 * LANES * e + 2 * sub);
-                            zi[e] = *reinterpret_cast<const double2*>(group + 4 * LANES * e + 2 * LANES + 2 * sub);
-                        }
-                    }
-#pragma unroll
-                    for (int e = 0; e < ROWS; ++e)
-                    {
-                        const long long tag = __double_as_longlong(zi[e].y);
-                        const int at = q + e * LANES + sub;
-                        const int before = mq;
-                        voroCandidatePair(S, rx, ry, rz, kx, ky, kz, prx, pry, prz, (at < cnt) ? (int)tag : -7, xy[e].x, xy[e].y, zi[e].x, sq, mq);
-                        if (mq != before) runq = (uint32_t)((unsigned long long)tag >> 32), iq = at;
-                    }
-                    q += ROWS * LANES;
-                    if (q >= cnt)
-                    {
-                        {
-                            const double osq = quadXor<1>(sq);
-                            const int oiq = quadXor<1>(iq), omq = quadXor<1>(mq), orun = quadXor<1>((int)runq);
-                            if (osq < sq || (osq == sq && oiq < iq)) sq = osq, iq = oiq, mq = omq, runq = (uint32_t)orun;
-                        }
-                        if (LANES == 4)
-                        {
-                            const double osq = quadXor<2>(sq);
-                            const int oiq = quadXor<2>(iq), omq = quadXor<2>(mq), orun = quadXor<2>((int)runq);
-                            if (osq < sq || (osq == sq && oiq < iq)) sq = osq, iq = oiq, mq = omq, runq = (uint32_t)orun;
-                        }
-                        if (mq == NO_INDEX)
-                            st = ST_SLOW;
-                        else
-                            PMC_VPROP_SEGMENT(sq, mq, runq)
-                    }
-                }
-            }
-        }
-#undef PMC_VPROP_SEGMENT
-        unsigned long long v;
-        v = waveSum(paths);
-        if (lane == 0 && v) atomicAdd(S.counters + 1, v);
-        v = waveSum(visits);
-        if (lane == 0 && v) atomicAdd(S.counters + 2, v);
-        v = waveSum(rewalks);
-        if (lane == 0 && v) atomicAdd(S.counters + 6, v);
     }
