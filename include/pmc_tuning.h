@@ -120,6 +120,78 @@ int pmc_tune_stat_log_flush(pmc_ctx* ctx, const uint32_t* keys, const double* va
    PMC_ERR_INVALID on a grid without a device numbering. */
 int pmc_tune_cell_numbering(pmc_ctx* ctx, int32_t* ext_out);
 
+/* ---- Test aids: the scalar device functions of the transition, launch and walk kernels (skirt9_amd/csrc/pmc_transition.inc, pmc_walk.inc,
+   pmc_kernels.hip), run over n argument tuples that the HOST supplies, one lane per tuple: the kernels reach some of their branches with one history
+   in 10^5 or with none.  The lanes call the functions the kernels call.  Every aid checks its arguments and returns PMC_ERR_INVALID with a message
+   instead of launching (a null context or buffer, n < 0 or n > 2^20, an unknown function or kind, a table of fewer than 2 nodes, an instrument or
+   source the scene does not have); n = 0 does nothing.  It allocates the device buffers it needs and frees them, works on the context's stream, reads
+   no device memory but those buffers and the scene's own tables, returns when its results are on the host, and leaves the context as pmc_run_primary
+   expects it.  No reference counterpart. */
+
+/* The scene-free functions: args[n][width_in] doubles -> out[n][width_out] doubles, with the tuples
+     PMC_FN_HG_VALUE              (g, cos)                          -> PhaseHG::value
+     PMC_FN_HG_CONE_MEAN          (g, cos)                          -> PhaseHG::coneMean (the kernels use it for |g| > 0.95)
+     PMC_FN_PHASE_VALUE           (g, cos)                          -> phaseValue of a Henyey-Greenstein component: one of the two above
+     PMC_FN_HG_COSINE             (g, X)                            -> (PhaseHG::cosineFor, 1 if the scattering event takes the isotropic branch for
+                                                                       this g instead -- PhaseHG::isotropic -- else 0)
+     PMC_FN_DIPOLE_VALUE          (cos)                             -> PhaseDipole::value
+     PMC_FN_RANDOM_DIRECTION      (u1, u2)                          -> (kx, ky, kz): randomDirection with these two deviates
+     PMC_FN_DIRECTION_ABOUT       (kx, ky, kz, cos, u)              -> (kx', ky', kz'): directionAbout with this deviate
+     PMC_FN_LAMBERT_LOWER_BRANCH  (z)                               -> lambertLowerBranch
+     PMC_FN_GENERALIZED_EXP       (p, x)                            -> generalizedExp
+     PMC_FN_INTERPOLATE_LOGLOG    (x, x1, x2, f1, f2)               -> interpolateLogLog
+     PMC_FN_LNMEAN                (x1, x2, ln x1, ln x2)            -> lnmean
+     PMC_FN_PEEL_TAUMAX           (W, lambda)                       -> peelTaumax
+     PMC_FN_SHIFTED_WAVELENGTH    (lambda0, kx, ky, kz, vx, vy, vz) -> shiftedEmissionWavelength
+   No tuple is refused for its values: the functions are total (a value outside a function's domain gives what IEEE arithmetic makes of it). */
+enum
+{
+    PMC_FN_HG_VALUE = 0,
+    PMC_FN_HG_CONE_MEAN = 1,
+    PMC_FN_PHASE_VALUE = 2,
+    PMC_FN_HG_COSINE = 3,
+    PMC_FN_DIPOLE_VALUE = 4,
+    PMC_FN_RANDOM_DIRECTION = 5,
+    PMC_FN_DIRECTION_ABOUT = 6,
+    PMC_FN_LAMBERT_LOWER_BRANCH = 7,
+    PMC_FN_GENERALIZED_EXP = 8,
+    PMC_FN_INTERPOLATE_LOGLOG = 9,
+    PMC_FN_LNMEAN = 10,
+    PMC_FN_PEEL_TAUMAX = 11,
+    PMC_FN_SHIFTED_WAVELENGTH = 12,
+    PMC_FN_COUNT = 13
+};
+int pmc_tune_device_function(pmc_ctx* ctx, int32_t function, const double* args, int64_t n, double* out);
+/* width_in and width_out of a function (pure host code; ctx is not involved); PMC_ERR_INVALID for an unknown function */
+int pmc_tune_device_function_widths(int32_t function, int32_t* width_in, int32_t* width_out);
+
+/* The table searches on the ascending table nodes[num_nodes] (num_nodes >= 2) that the call passes: kind 0 locate (NR::locate: the last node belongs
+   to the last bin, -1 below the first node, num_nodes - 1 above the last), 1 locateClip (clipped to [0, num_nodes - 2]), 2 locateBasic (the index of the
+   last node <= x, -1 .. num_nodes - 1); index_out: n int32. */
+int pmc_tune_locate(pmc_ctx* ctx, int32_t kind, const double* nodes, int32_t num_nodes, const double* x, int64_t n, int32_t* index_out);
+
+/* What the scene-bound aids below work with: the constants of instrument `instrument` as the device holds them (every integer an int64_t;
+   include_ifu: it records frames, and only then do xpmin .. nyp describe one; include_sed: it records an SED), and its
+   wavelength grid -- border[num_border] and ellv[num_border + 1], each copied if the pointer is not NULL (call once with NULL for num_border). */
+typedef struct pmc_instrument_values
+{
+    double costheta, sintheta, cosphi, sinphi, cosomega, sinomega;
+    double xpmin, xpsiz, ypmin, ypsiz;
+    double aperture_r2, zp1;
+    int64_t nxp, nyp, num_border, num_lambda, include_sed, include_ifu;
+} pmc_instrument_values;
+int pmc_tune_instrument(pmc_ctx* ctx, int32_t instrument, pmc_instrument_values* out, double* border, int32_t* ellv);
+/* pixelOnDetector (pixel_out: i + nxp j, -1 off the frame) and insideAperture (inside_out: 1 or 0; 1 without an aperture) of instrument `instrument`
+   for n positions r[n][3] (m) */
+int pmc_tune_detector(pmc_ctx* ctx, int32_t instrument, const double* r, int64_t n, int32_t* pixel_out, int32_t* inside_out);
+/* the wavelength bin of instrument `instrument` for n rest wavelengths lambda[n] (m), as the launch kernel finds it: ellv[number of borders <=
+   lambda (1 + z)], -1 outside the grid */
+int pmc_tune_wavelength_bins(pmc_ctx* ctx, int32_t instrument, const double* lambda, int64_t n, int32_t* ell_out);
+/* angularProbability of source `source` (PMC_ANGULAR_LASER, _CONICAL or _NETZER; PMC_ERR_INVALID for an isotropic source, for which the kernels
+   never call it) for n directions k[n][3]; kind_out, axis_out[3], cos_delta_out: the source's distribution as the device holds it (each may be NULL) */
+int pmc_tune_angular_probabilities(pmc_ctx* ctx, int32_t source, const double* k, int64_t n, double* p_out, int32_t* kind_out, double* axis_out,
+                                   double* cos_delta_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@
 #include "../include/pmc.h"
 #include "../include/pmc_layout.h"
 #include "../include/pmc_philox.h"
+#include <atomic>
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -99,13 +100,21 @@ namespace
         }
         return f1 * exp(log(x / x1) / log(x2 / x1) * (log(f2 / f1)));
     }
+    // census of the rarely taken branches of the scalar functions below (oracle_census): calls since the last reset
+    enum Census : int { C_MEAN_HG, C_MEAN_HG_FORWARD, C_MEAN_HG_BACKWARD, C_LAMBERT, C_LAMBERT_SERIES, C_LAMBERT_ASYMPTOTIC, C_GEXP, C_GEXP_EXPANSION,
+                        C_LNMEAN, C_LNMEAN_SERIES, C_COUNT };
+    std::atomic<uint64_t> g_census[C_COUNT];
+    inline void census(int what) { g_census[what].fetch_add(1, std::memory_order_relaxed); }
+
     // SpecialFunctions::gexp (SpecialFunctions.cpp:822-836)
     double gexp(double p, double x)
     {
+        census(C_GEXP);
         const double q = 1.0 - p;
         if (q == 0.0) return exp(x);
         if (fabs(q) < 1e-3)
         {
+            census(C_GEXP_EXPANSION);
             double x2 = x * x;
             return exp(x)
                    * (1.0 - 0.5 * x2 * q + 1.0 / 24.0 * x * x2 * (8.0 + 3.0 * x) * q * q
@@ -136,6 +145,7 @@ namespace
                                      12.250753501314460424,
                                      -18.100697012472442755,
                                      27.029044799010561650};
+        census(C_LAMBERT);
         if (z == 0.0) return -DBL_MAX;
         double q = z + em1;
         double r = -sqrt(q);
@@ -143,12 +153,17 @@ namespace
         double t5 = c[5] + r * (c[6] + r * (c[7] + r * t8));
         double t1 = c[1] + r * (c[2] + r * (c[3] + r * (c[4] + r * t5)));
         double w0 = c[0] + r * t1;
-        if (q < 3.0e-3) return w0;
+        if (q < 3.0e-3)
+        {
+            census(C_LAMBERT_SERIES);
+            return w0;
+        }
         double w;
         if (z < -1e-6)
             w = w0;
         else
         {
+            census(C_LAMBERT_ASYMPTOTIC);
             double l1 = log(-z);
             double l2 = log(-l1);
             w = l1 - l2 + l2 / l1;
@@ -1058,8 +1073,10 @@ namespace
                 std::swap(x1, x2);
                 std::swap(lnx1, lnx2);
             }
+            census(C_LNMEAN);
             if (x1 <= 0) return 0.;
             double x = x2 / x1 - 1.;
+            if (x < 1e-3) census(C_LNMEAN_SERIES);
             if (x < 1e-3)
                 return x1
                        / (1. - 1. / 2. * x + 1. / 3. * x * x - 1. / 4. * x * x * x + 1. / 5. * x * x * x * x
@@ -1507,6 +1524,9 @@ namespace
             double theta = acos(costheta);
             double cosalpha = cos(theta - delta);
             double cosbeta = cos(theta + delta);
+            census(C_MEAN_HG);
+            if (theta < delta) census(C_MEAN_HG_FORWARD);
+            if (theta > M_PI - delta) census(C_MEAN_HG_BACKWARD);
             if (theta < delta) return (integralHG(g, 1., cosalpha) + integralHG(g, 1., cosbeta)) / (2. - cosalpha - cosbeta);
             if (theta > M_PI - delta)
                 return (integralHG(g, cosalpha, -1.) + integralHG(g, cosbeta, -1.)) / (2. + cosalpha + cosbeta);
@@ -1714,6 +1734,65 @@ int oracle_run_primary_rf(const pmc_scene* scene, uint64_t first, uint64_t count
 {
     if (!rf) return PMC_ERR_INVALID;
     return oracle_run_primary_ext(scene, nullptr, first, count, rng_kind, seed, skip_draws, frames, rf, counters);
+}
+
+// The oracle's own copies of the scalar functions, over n argument tuples: args[n][width_in] -> out[n][width_out], with the function numbers
+// and tuples of include/pmc_tuning.h (PMC_FN_*); the deviates of the direction functions come from the tuple.  PMC_ERR_UNSUPPORTED for a
+// function the oracle has no copy of its own of (the HG cosine, which is written out in its scattering event; peel-off depth; wavelength shift).
+int oracle_evaluate(int32_t function, const double* args, int64_t n, double* out)
+{
+    struct TupleRng : Rng
+    {
+        const double* next;
+        explicit TupleRng(const double* u) : next(u) {}
+        double uniform() override { return *next++; }
+    };
+    static const int widths[13][2] = {{2, 1}, {2, 1}, {2, 1}, {0, 0}, {1, 1}, {2, 3}, {5, 3}, {1, 1}, {2, 1}, {5, 1}, {4, 1}, {0, 0}, {0, 0}};
+    if (function < 0 || function >= 13 || n < 0 || (n > 0 && (!args || !out))) return PMC_ERR_INVALID;
+    if (widths[function][0] == 0) return PMC_ERR_UNSUPPORTED;
+    for (int64_t i = 0; i < n; ++i)
+    {
+        const double* a = args + i * widths[function][0];
+        double* o = out + i * widths[function][1];
+        switch (function)
+        {
+            case 0: o[0] = LifeCycle::valueHG(a[0], a[1]); break;
+            case 1: o[0] = LifeCycle::meanHG(a[0], a[1]); break;
+            case 2: o[0] = fabs(a[0]) > 0.95 ? LifeCycle::meanHG(a[0], a[1]) : LifeCycle::valueHG(a[0], a[1]); break;
+            case 4: o[0] = LifeCycle::valueDipole(a[0]); break;
+            case 5:
+            {
+                TupleRng rng(a);
+                const V3 k = randomDirection(rng);
+                o[0] = k.x, o[1] = k.y, o[2] = k.z;
+                break;
+            }
+            case 6:
+            {
+                TupleRng rng(a + 4);
+                const V3 k = randomDirectionAbout(rng, V3{a[0], a[1], a[2]}, a[3]);
+                o[0] = k.x, o[1] = k.y, o[2] = k.z;
+                break;
+            }
+            case 7: o[0] = lambertW1(a[0]); break;
+            case 8: o[0] = gexp(a[0], a[1]); break;
+            case 9: o[0] = interpolateLogLog(a[0], a[1], a[2], a[3], a[4]); break;
+            case 10: o[0] = LifeCycle::lnmean(a[0], a[1], a[2], a[3]); break;
+        }
+    }
+    return PMC_OK;
+}
+
+// The census of the scalar functions' branches since the last reset: out[10] = calls of meanHG, of them with the cone folded at the forward and at the
+// backward pole; calls of lambertW1, of them answered by the series and started from the asymptotic form; calls of gexp, of them through the
+// expansion; calls of lnmean, of them through the series.  reset != 0: the counters start again from zero after they are read.
+void oracle_census(uint64_t* out, int reset)
+{
+    for (int i = 0; i < C_COUNT; ++i)
+    {
+        if (out) out[i] = g_census[i].load(std::memory_order_relaxed);
+        if (reset) g_census[i].store(0, std::memory_order_relaxed);
+    }
 }
 
 int oracle_trace_ray(const pmc_scene* scene, const double r[3], const double k[3], int32_t* m, double* ds, int32_t cap,

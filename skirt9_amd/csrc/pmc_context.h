@@ -58,6 +58,11 @@ extern "C" size_t pmcRfTempBytes(int numParts);
 extern "C" int pmcRfMaxParts();
 extern "C" hipError_t pmcLaunchDipoleCosines(const double* u, int64_t n, double* out, hipStream_t stream);
 extern "C" hipError_t pmcLaunchSourceVelocities(int slot, int source, const double* r, int64_t n, double* out, hipStream_t stream);
+extern "C" hipError_t pmcLaunchDeviceFunction(int slot, int function, const double* args, int widthIn, int64_t n, double* out, int widthOut, hipStream_t stream);
+extern "C" hipError_t pmcLaunchLocate(int kind, const double* nodes, int numNodes, const double* x, int64_t n, int32_t* out, hipStream_t stream);
+extern "C" hipError_t pmcLaunchDetector(int slot, int instrument, const double* r, int64_t n, int32_t* pixel, int32_t* inside, hipStream_t stream);
+extern "C" hipError_t pmcLaunchWavelengthBins(int slot, int instrument, const double* lambda, int64_t n, int32_t* ell, hipStream_t stream);
+extern "C" hipError_t pmcLaunchAngularProbabilities(int slot, int source, const double* k, int64_t n, double* out, hipStream_t stream);
 extern "C" hipError_t pmcLaunchTransition(int slot, int flavour, int slotBase, int numSlots, int group, uint64_t seed, const int* list, int listLen, int maxBlocks,
                                           size_t ldsBytes, const StatLogArgs* statLog, uint64_t count, hipStream_t stream);
 extern "C" hipError_t pmcLaunchLaunch(int slot, int flavour, int slotBase, int numSlots, int group, uint64_t first, uint64_t count, uint64_t seed, int initial,

@@ -749,6 +749,102 @@ extern "C" hipError_t pmcLaunchSourceVelocities(int slot, int source, const doub
     return hipGetLastError();
 }
 
+// test aids (pmc_tuning.h pmc_tune_device_function, pmc_tune_locate, pmc_tune_detector, pmc_tune_wavelength_bins, pmc_tune_angular_probabilities):
+// the scalar device functions of the transition, launch and walk kernels, one lane per host-supplied argument tuple.  Every lane calls the
+// function the kernels call; nothing of it is restated here.
+namespace
+{
+    // args[n][widthIn] -> out[n][widthOut] (the widths of `function`: pmc_tuning.hip deviceFunctionWidths)
+    __global__ __launch_bounds__(256) void deviceFunctionKernel(const int sceneSlot, const int function, const double* __restrict__ args, const int widthIn,
+                                                                const int64_t n, double* __restrict__ out, const int widthOut)
+    {
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i >= n) return;
+        const double* a = args + i * widthIn;
+        double* o = out + i * widthOut;
+        switch (function)
+        {
+            case PMC_FN_HG_VALUE: o[0] = PhaseHG(a[0]).value(a[1]); break;
+            case PMC_FN_HG_CONE_MEAN: o[0] = PhaseHG(a[0]).coneMean(a[1]); break;
+            case PMC_FN_PHASE_VALUE: o[0] = phaseValue<false>(c_scene[sceneSlot], 0, a[0], a[1]); break;
+            case PMC_FN_HG_COSINE:
+                o[0] = PhaseHG::cosineFor(a[0], a[1]);
+                o[1] = PhaseHG::isotropic(a[0]) ? 1. : 0.;
+                break;
+            case PMC_FN_DIPOLE_VALUE: o[0] = PhaseDipole::value(a[0]); break;
+            case PMC_FN_RANDOM_DIRECTION: randomDirectionFor(a[0], a[1], o[0], o[1], o[2]); break;
+            case PMC_FN_DIRECTION_ABOUT: directionAboutFor(a[4], a[0], a[1], a[2], a[3], o[0], o[1], o[2]); break;
+            case PMC_FN_LAMBERT_LOWER_BRANCH: o[0] = lambertLowerBranch(a[0]); break;
+            case PMC_FN_GENERALIZED_EXP: o[0] = generalizedExp(a[0], a[1]); break;
+            case PMC_FN_INTERPOLATE_LOGLOG: o[0] = interpolateLogLog(a[0], a[1], a[2], a[3], a[4]); break;
+            case PMC_FN_LNMEAN: o[0] = lnmean(a[0], a[1], a[2], a[3]); break;
+            case PMC_FN_PEEL_TAUMAX: o[0] = peelTaumax(a[0], a[1]); break;
+            case PMC_FN_SHIFTED_WAVELENGTH: o[0] = shiftedEmissionWavelength(a[0], a[1], a[2], a[3], a[4], a[5], a[6]); break;
+            default: break;
+        }
+    }
+    // kind 0 locate, 1 locateClip, 2 locateBasic on the table nodes[numNodes] (numNodes >= 2)
+    __global__ __launch_bounds__(256) void locateKernel(const int kind, const double* __restrict__ nodes, const int numNodes, const double* __restrict__ x,
+                                                        const int64_t n, int32_t* __restrict__ out)
+    {
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i >= n) return;
+        out[i] = kind == 0 ? locate(nodes, numNodes, x[i]) : kind == 1 ? locateClip(nodes, numNodes, x[i]) : locateBasic(nodes, x[i], numNodes);
+    }
+    __global__ __launch_bounds__(256) void detectorKernel(const int sceneSlot, const int instrument, const double* __restrict__ r, const int64_t n,
+                                                          int32_t* __restrict__ pixel, int32_t* __restrict__ inside)
+    {
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i >= n) return;
+        const DevInstrument& I = c_scene[sceneSlot].inst[instrument];
+        pixel[i] = pixelOnDetector(I, r[3 * i], r[3 * i + 1], r[3 * i + 2]);
+        inside[i] = insideAperture(I, r[3 * i], r[3 * i + 1], r[3 * i + 2]) ? 1 : 0;
+    }
+    __global__ __launch_bounds__(256) void wavelengthBinKernel(const int sceneSlot, const int instrument, const double* __restrict__ lambda, const int64_t n,
+                                                               int32_t* __restrict__ ell)
+    {
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n) ell[i] = observedBin(c_scene[sceneSlot].inst[instrument], lambda[i]);
+    }
+    __global__ __launch_bounds__(256) void angularProbabilityKernel(const int sceneSlot, const int source, const double* __restrict__ k, const int64_t n,
+                                                                    double* __restrict__ out)
+    {
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n) out[i] = angularProbability(c_scene[sceneSlot].src[source], k[3 * i], k[3 * i + 1], k[3 * i + 2]);
+    }
+    unsigned blocksFor(int64_t n) { return (unsigned)((n + 255) / 256); }
+}
+extern "C" hipError_t pmcLaunchDeviceFunction(int slot, int function, const double* args, int widthIn, int64_t n, double* out, int widthOut, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(deviceFunctionKernel, dim3(blocksFor(n)), dim3(256), 0, stream, slot, function, args, widthIn, n, out, widthOut);
+    return hipGetLastError();
+}
+extern "C" hipError_t pmcLaunchLocate(int kind, const double* nodes, int numNodes, const double* x, int64_t n, int32_t* out, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(locateKernel, dim3(blocksFor(n)), dim3(256), 0, stream, kind, nodes, numNodes, x, n, out);
+    return hipGetLastError();
+}
+extern "C" hipError_t pmcLaunchDetector(int slot, int instrument, const double* r, int64_t n, int32_t* pixel, int32_t* inside, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(detectorKernel, dim3(blocksFor(n)), dim3(256), 0, stream, slot, instrument, r, n, pixel, inside);
+    return hipGetLastError();
+}
+extern "C" hipError_t pmcLaunchWavelengthBins(int slot, int instrument, const double* lambda, int64_t n, int32_t* ell, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(wavelengthBinKernel, dim3(blocksFor(n)), dim3(256), 0, stream, slot, instrument, lambda, n, ell);
+    return hipGetLastError();
+}
+extern "C" hipError_t pmcLaunchAngularProbabilities(int slot, int source, const double* k, int64_t n, double* out, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(angularProbabilityKernel, dim3(blocksFor(n)), dim3(256), 0, stream, slot, source, k, n, out);
+    return hipGetLastError();
+}
+
 // one ray through the grid; octree: `uniform` picks the flavour of the step the ray is traced with (direction in scalar
 // registers as in the peel-off kernel, or in vector registers as in the propagation kernel; kdev = the direction in
 // device memory)

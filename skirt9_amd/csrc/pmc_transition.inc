@@ -67,6 +67,15 @@
             if (theta > M_PI - halfAngle) return (between(cosInner, -1.) + between(cosOuter, -1.)) / (2. + cosInner + cosOuter);
             return between(cosInner, cosOuter) / (cosInner - cosOuter);
         }
+        // the scattering cosine that belongs to a uniform deviate X, for |g| >= 1e-6 (DustMix.cpp:490-511: the inverse of the cumulative
+        // distribution); next to |g| = 1e-6 and |g| = 1 the result can leave [-1, 1] by rounding, which directionAbout absorbs
+        // (below that asymmetry the scattering event draws an isotropic direction instead: DustMix.cpp:501)
+        static __device__ __forceinline__ bool isotropic(double g) { return fabs(g) < 1e-6; }
+        static __device__ __forceinline__ double cosineFor(double g, double X)
+        {
+            double f = ((1.0 - g) * (1.0 + g)) / (1.0 - g + 2.0 * g * X);
+            return (1.0 + g * g - f * f) / (2.0 * g);
+        }
     };
 
     // Dipole phase function of Thomson scattering by free electrons, unpolarized (DipolePhaseFunction.cpp:47-59): its value for a
@@ -92,10 +101,11 @@
     }
 
     // Direction(theta, phi) + Random::direction() (Direction.cpp:11-38, Random.cpp:121-126)
-    __device__ __forceinline__ void randomDirection(Rng& rng, uint64_t seed, double& kx, double& ky, double& kz)
+    // (the core: the direction that belongs to the two uniform deviates u1 (inclination) and u2 (azimuth))
+    __device__ __forceinline__ void randomDirectionFor(double u1, double u2, double& kx, double& ky, double& kz)
     {
-        double theta = acos(2.0 * rngUniform(rng, seed) - 1.0);
-        double phi = 2.0 * M_PI * rngUniform(rng, seed);
+        double theta = acos(2.0 * u1 - 1.0);
+        double phi = 2.0 * M_PI * u2;
         const double eps = 1e-8;
         if (theta <= eps)
         {
@@ -114,6 +124,12 @@
             ky = sintheta * sinphi;
             kz = costheta;
         }
+    }
+    __device__ __forceinline__ void randomDirection(Rng& rng, uint64_t seed, double& kx, double& ky, double& kz)
+    {
+        const double u1 = rngUniform(rng, seed);
+        const double u2 = rngUniform(rng, seed);
+        randomDirectionFor(u1, u2, kx, ky, kz);
     }
 
     __device__ __forceinline__ double interpolateLogLog(double x, double x1, double x2, double f1, double f2)
@@ -643,10 +659,10 @@
         }
     }
     // Random::direction(bfk, costheta) (Random.cpp:130-164): a direction at the given inclination to k, uniform in azimuth
-    __device__ __forceinline__ void directionAbout(Rng& rng, uint64_t seed, double kx, double ky, double kz, double costheta, double& kxn, double& kyn,
-                                                   double& kzn)
+    // (the core: the azimuth comes from the uniform deviate u)
+    __device__ __forceinline__ void directionAboutFor(double u, double kx, double ky, double kz, double costheta, double& kxn, double& kyn, double& kzn)
     {
-        double phi = 2.0 * M_PI * rngUniform(rng, seed);
+        double phi = 2.0 * M_PI * u;
         double sinphi, cosphi;
         sincos(phi, &sinphi, &cosphi);
         double sintheta = sqrt(fabs((1.0 - costheta) * (1.0 + costheta)));
@@ -669,6 +685,11 @@
             kyn = -sintheta / root * (ky * kz * cosphi + kx * sinphi) + ky * costheta;
             kzn = root * sintheta * cosphi + kz * costheta;
         }
+    }
+    __device__ __forceinline__ void directionAbout(Rng& rng, uint64_t seed, double kx, double ky, double kz, double costheta, double& kxn, double& kyn,
+                                                   double& kzn)
+    {
+        directionAboutFor(rngUniform(rng, seed), kx, ky, kz, costheta, kxn, kyn, kzn);
     }
     // probability of the direction k for the emission of a point source with an axisymmetric angular distribution, relative to isotropic
     // emission (AxAngularDistribution.cpp:27-30; LaserAngularDistribution.cpp:11-16, ConicalAngularDistribution.cpp:19-25,
@@ -1241,12 +1262,11 @@
                 const double costheta = PhaseDipole::cosineFor(rngUniform(rng, seed));
                 directionAbout(rng, seed, kx, ky, kz, costheta, kxn, kyn, kzn);
             }
-            else if (fabs(g) < 1e-6)
+            else if (PhaseHG::isotropic(g))
                 randomDirection(rng, seed, kxn, kyn, kzn);
             else
             {
-                double f = ((1.0 - g) * (1.0 + g)) / (1.0 - g + 2.0 * g * rngUniform(rng, seed));
-                double costheta = (1.0 + g * g - f * f) / (2.0 * g);
+                const double costheta = PhaseHG::cosineFor(g, rngUniform(rng, seed));
                 directionAbout(rng, seed, kx, ky, kz, costheta, kxn, kyn, kzn);
             }
         }
@@ -1298,6 +1318,27 @@
     __device__ __forceinline__ double shiftedEmissionWavelength(double lambda0, double kx, double ky, double kz, double vx, double vy, double vz)
     {
         return lambda0 * (1 - (kx * vx + ky * vy + kz * vz) / 2.99792458e8);
+    }
+    // the number of the n ascending borders that are <= lambda (std::upper_bound): the index into a wavelength grid's table of bins
+    // (DisjointWavelengthGrid::bin, DisjointWavelengthGrid.cpp:334-345)
+    __device__ __forceinline__ int bordersUpTo(const double* border, int n, double lambda)
+    {
+        int lo = 0, hi = n;
+        while (lo < hi)
+        {
+            int mid = (lo + hi) >> 1;
+            if (lambda < border[mid])
+                hi = mid;
+            else
+                lo = mid + 1;
+        }
+        return lo;
+    }
+    // the wavelength bin of instrument I for a packet of rest wavelength lambda, or -1: the bin of its redshifted wavelength lambda (1 + z)
+    // (FluxRecorder.cpp:309-310)
+    __device__ __forceinline__ int observedBin(const DevInstrument& I, double lambda)
+    {
+        return I.ellv[bordersUpTo(I.border, I.num_border, lambda * I.zp1)];
     }
 
     // KIN (a scene with a moving source): the packet's wavelength is Doppler-shifted by the source's velocity along the launch direction
@@ -1520,31 +1561,14 @@
         for (int i = 0; i < S.num_instruments; ++i)
         {
             const DevInstrument& I = S.inst[i];
-            const double lambdaObs = lambda * I.zp1;  // the packet's redshifted wavelength (FluxRecorder.cpp:309-310)
-            int lo = 0, hi = S.mono ? 0 : I.num_border;  // upper_bound (one wavelength for every history: DevInstrument::mono_ell)
-            while (lo < hi)
-            {
-                int mid = (lo + hi) >> 1;
-                if (lambdaObs < I.border[mid])
-                    hi = mid;
-                else
-                    lo = mid + 1;
-            }
-            if (!S.mono) A.ell[(int64_t)i * A.num_slots + slot] = I.ellv[lo];
+            // (one wavelength for every history: DevInstrument::mono_ell)
+            if (!S.mono) A.ell[(int64_t)i * A.num_slots + slot] = observedBin(I, lambda);
             if (KIN)
             {
                 // the emission peel-off packet towards this instrument's observer: wavelength, cross section there, bin
                 const double lambdaPeel = shiftedEmissionWavelength(lambda0, I.kx, I.ky, I.kz, vx, vy, vz);
                 const double lambdaPeelObs = lambdaPeel * I.zp1;
-                int plo = 0, phi = I.num_border;
-                while (plo < phi)
-                {
-                    int mid = (plo + phi) >> 1;
-                    if (lambdaPeelObs < I.border[mid])
-                        phi = mid;
-                    else
-                        plo = mid + 1;
-                }
+                const int plo = bordersUpTo(I.border, I.num_border, lambdaPeelObs);  // (observedBin, its load behind the stores)
                 A.obsLambda[(int64_t)i * A.num_slots + slot] = lambdaPeel;
                 A.obsExt[(int64_t)i * A.num_slots + slot] = L.sext[locateClip(L.lamb, S.num_lambda, lambdaPeel)];
                 A.obsEll[(int64_t)i * A.num_slots + slot] = I.ellv[plo];
@@ -1554,16 +1578,7 @@
         if (S.rf_store)
         {
             // bin of the radiation field wavelength grid (DisjointWavelengthGrid::bin)
-            int lo = 0, hi = S.rf_num_border;
-            while (lo < hi)
-            {
-                int mid = (lo + hi) >> 1;
-                if (lambda < S.rf_border[mid])
-                    hi = mid;
-                else
-                    lo = mid + 1;
-            }
-            A.rfell[slot] = S.rf_ellv[lo];
+            A.rfell[slot] = S.rf_ellv[bordersUpTo(S.rf_border, S.rf_num_border, lambda)];
         }
         // the photon cycle starts with the emission peel-offs and the first propagation walk
         A.Lthreshold[slot] = (W / lambda) / S.min_weight_reduction;  // MonteCarloSimulation.cpp:566

@@ -228,3 +228,170 @@ extern "C" int pmc_tune_cell_numbering(pmc_ctx* ctx, int32_t* ext_out)
     if (e != hipSuccess) return hipFail(e, "pmc_tune_cell_numbering");
     return PMC_OK;
 }
+
+// ---- test aids of the scalar device functions (include/pmc_tuning.h): one lane per host-supplied argument tuple
+namespace
+{
+    constexpr int64_t PRIMITIVE_MAX_TUPLES = int64_t(1) << 20;
+
+    // doubles per argument tuple and per result of every PMC_FN_*
+    const int DEVICE_FUNCTION_WIDTHS[PMC_FN_COUNT][2] = {{2, 1}, {2, 1}, {2, 1}, {2, 2}, {1, 1}, {2, 3}, {5, 3}, {1, 1}, {2, 1}, {5, 1}, {4, 1}, {2, 1}, {7, 1}};
+
+    // what is wrong with the tuple count and the buffers of an aid, or null
+    const char* tupleProblem(int64_t n, const void* in, const void* out)
+    {
+        if (n < 0 || n > PRIMITIVE_MAX_TUPLES) return "between 0 and 2^20 tuples";
+        if (n > 0 && (!in || !out)) return "null buffer";
+        return nullptr;
+    }
+
+    // `count` elements of a result brought to the host after everything enqueued on the context's stream
+    template<typename T> hipError_t fetch(pmc_ctx* ctx, hipError_t e, T* host, const T* device, size_t count)
+    {
+        if (e == hipSuccess) e = hipMemcpyAsync(host, device, sizeof(T) * count, hipMemcpyDeviceToHost, ctx->stream);
+        return e;
+    }
+    hipError_t finish(pmc_ctx* ctx, hipError_t e)
+    {
+        const hipError_t done = hipStreamSynchronize(ctx->stream);  // (whatever was enqueued has finished before the buffers go)
+        return e == hipSuccess ? done : e;
+    }
+}
+
+extern "C" int pmc_tune_device_function_widths(int32_t function, int32_t* width_in, int32_t* width_out)
+{
+    if (function < 0 || function >= PMC_FN_COUNT || !width_in || !width_out)
+        return fail(PMC_ERR_INVALID, "pmc_tune_device_function_widths: unknown function " + std::to_string(function) + ", or a null pointer");
+    *width_in = DEVICE_FUNCTION_WIDTHS[function][0];
+    *width_out = DEVICE_FUNCTION_WIDTHS[function][1];
+    return PMC_OK;
+}
+
+extern "C" int pmc_tune_device_function(pmc_ctx* ctx, int32_t function, const double* args, int64_t n, double* out)
+{
+    if (!ctx) return fail(PMC_ERR_INVALID, "pmc_tune_device_function: no context");
+    if (function < 0 || function >= PMC_FN_COUNT) return fail(PMC_ERR_INVALID, "pmc_tune_device_function: unknown function " + std::to_string(function));
+    if (const char* problem = tupleProblem(n, args, out)) return fail(PMC_ERR_INVALID, std::string("pmc_tune_device_function: ") + problem);
+    if (n == 0) return PMC_OK;
+    const int widthIn = DEVICE_FUNCTION_WIDTHS[function][0], widthOut = DEVICE_FUNCTION_WIDTHS[function][1];
+    HIP_TRY(hipSetDevice(ctx->device));
+    CallBuffers B;
+    double *dArgs = nullptr, *dOut = nullptr;
+    hipError_t e = B.get(size_t(n) * widthIn, &dArgs, args);
+    if (e == hipSuccess) e = B.get(size_t(n) * widthOut, &dOut);
+    if (e == hipSuccess) e = sceneUpToDate(ctx);
+    if (e == hipSuccess) e = pmcLaunchDeviceFunction(ctx->slot, function, dArgs, widthIn, n, dOut, widthOut, ctx->stream);
+    e = finish(ctx, fetch(ctx, e, out, dOut, size_t(n) * widthOut));
+    if (e != hipSuccess) return hipFail(e, "pmc_tune_device_function");
+    return PMC_OK;
+}
+
+extern "C" int pmc_tune_locate(pmc_ctx* ctx, int32_t kind, const double* nodes, int32_t num_nodes, const double* x, int64_t n, int32_t* index_out)
+{
+    if (!ctx) return fail(PMC_ERR_INVALID, "pmc_tune_locate: no context");
+    if (kind < 0 || kind > 2) return fail(PMC_ERR_INVALID, "pmc_tune_locate: unknown kind " + std::to_string(kind));
+    if (!nodes || num_nodes < 2) return fail(PMC_ERR_INVALID, "pmc_tune_locate: a table has at least 2 nodes");
+    if (const char* problem = tupleProblem(n, x, index_out)) return fail(PMC_ERR_INVALID, std::string("pmc_tune_locate: ") + problem);
+    if (n == 0) return PMC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CallBuffers B;
+    double *dNodes = nullptr, *dX = nullptr;
+    int32_t* dOut = nullptr;
+    hipError_t e = B.get(size_t(num_nodes), &dNodes, nodes);
+    if (e == hipSuccess) e = B.get(size_t(n), &dX, x);
+    if (e == hipSuccess) e = B.get(size_t(n), &dOut);
+    if (e == hipSuccess) e = pmcLaunchLocate(kind, dNodes, num_nodes, dX, n, dOut, ctx->stream);
+    e = finish(ctx, fetch(ctx, e, index_out, dOut, size_t(n)));
+    if (e != hipSuccess) return hipFail(e, "pmc_tune_locate");
+    return PMC_OK;
+}
+
+extern "C" int pmc_tune_instrument(pmc_ctx* ctx, int32_t instrument, pmc_instrument_values* out, double* border, int32_t* ellv)
+{
+    if (!ctx || !out) return fail(PMC_ERR_INVALID, "pmc_tune_instrument: invalid argument");
+    if (instrument < 0 || instrument >= ctx->dev.num_instruments) return fail(PMC_ERR_INVALID, "pmc_tune_instrument: no such instrument");
+    const DevInstrument& I = ctx->dev.inst[instrument];
+    out->costheta = I.costheta, out->sintheta = I.sintheta, out->cosphi = I.cosphi, out->sinphi = I.sinphi, out->cosomega = I.cosomega, out->sinomega = I.sinomega;
+    out->xpmin = I.xpmin, out->xpsiz = I.xpsiz, out->ypmin = I.ypmin, out->ypsiz = I.ypsiz;
+    out->aperture_r2 = I.aperture_r2, out->zp1 = I.zp1;
+    out->nxp = I.nxp, out->nyp = I.nyp, out->num_border = I.num_border, out->num_lambda = I.num_lambda;
+    out->include_sed = I.include_sed, out->include_ifu = I.include_ifu;
+    if (!border && !ellv) return PMC_OK;
+    if (!I.border || !I.ellv || I.num_border < 0) return fail(PMC_ERR_INVALID, "pmc_tune_instrument: the instrument has no wavelength grid on the device");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipError_t e = hipSuccess;
+    if (border && I.num_border > 0) e = fetch(ctx, e, border, I.border, size_t(I.num_border));
+    if (ellv) e = fetch(ctx, e, ellv, I.ellv, size_t(I.num_border) + 1);
+    e = finish(ctx, e);
+    if (e != hipSuccess) return hipFail(e, "pmc_tune_instrument");
+    return PMC_OK;
+}
+
+extern "C" int pmc_tune_detector(pmc_ctx* ctx, int32_t instrument, const double* r, int64_t n, int32_t* pixel_out, int32_t* inside_out)
+{
+    if (!ctx) return fail(PMC_ERR_INVALID, "pmc_tune_detector: no context");
+    if (instrument < 0 || instrument >= ctx->dev.num_instruments) return fail(PMC_ERR_INVALID, "pmc_tune_detector: no such instrument");
+    if (const char* problem = tupleProblem(n, r, pixel_out)) return fail(PMC_ERR_INVALID, std::string("pmc_tune_detector: ") + problem);
+    if (n > 0 && !inside_out) return fail(PMC_ERR_INVALID, "pmc_tune_detector: null buffer");
+    if (n == 0) return PMC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CallBuffers B;
+    double* dR = nullptr;
+    int32_t *dPixel = nullptr, *dInside = nullptr;
+    hipError_t e = B.get(size_t(3 * n), &dR, r);
+    if (e == hipSuccess) e = B.get(size_t(n), &dPixel);
+    if (e == hipSuccess) e = B.get(size_t(n), &dInside);
+    if (e == hipSuccess) e = sceneUpToDate(ctx);
+    if (e == hipSuccess) e = pmcLaunchDetector(ctx->slot, instrument, dR, n, dPixel, dInside, ctx->stream);
+    e = fetch(ctx, e, pixel_out, dPixel, size_t(n));
+    e = finish(ctx, fetch(ctx, e, inside_out, dInside, size_t(n)));
+    if (e != hipSuccess) return hipFail(e, "pmc_tune_detector");
+    return PMC_OK;
+}
+
+extern "C" int pmc_tune_wavelength_bins(pmc_ctx* ctx, int32_t instrument, const double* lambda, int64_t n, int32_t* ell_out)
+{
+    if (!ctx) return fail(PMC_ERR_INVALID, "pmc_tune_wavelength_bins: no context");
+    if (instrument < 0 || instrument >= ctx->dev.num_instruments) return fail(PMC_ERR_INVALID, "pmc_tune_wavelength_bins: no such instrument");
+    const DevInstrument& I = ctx->dev.inst[instrument];
+    if (!I.ellv || I.num_border < 0 || (I.num_border > 0 && !I.border))
+        return fail(PMC_ERR_INVALID, "pmc_tune_wavelength_bins: the instrument has no wavelength grid on the device");
+    if (const char* problem = tupleProblem(n, lambda, ell_out)) return fail(PMC_ERR_INVALID, std::string("pmc_tune_wavelength_bins: ") + problem);
+    if (n == 0) return PMC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CallBuffers B;
+    double* dLambda = nullptr;
+    int32_t* dEll = nullptr;
+    hipError_t e = B.get(size_t(n), &dLambda, lambda);
+    if (e == hipSuccess) e = B.get(size_t(n), &dEll);
+    if (e == hipSuccess) e = sceneUpToDate(ctx);
+    if (e == hipSuccess) e = pmcLaunchWavelengthBins(ctx->slot, instrument, dLambda, n, dEll, ctx->stream);
+    e = finish(ctx, fetch(ctx, e, ell_out, dEll, size_t(n)));
+    if (e != hipSuccess) return hipFail(e, "pmc_tune_wavelength_bins");
+    return PMC_OK;
+}
+
+extern "C" int pmc_tune_angular_probabilities(pmc_ctx* ctx, int32_t source, const double* k, int64_t n, double* p_out, int32_t* kind_out, double* axis_out,
+                                              double* cos_delta_out)
+{
+    if (!ctx) return fail(PMC_ERR_INVALID, "pmc_tune_angular_probabilities: no context");
+    if (source < 0 || source >= ctx->dev.num_sources) return fail(PMC_ERR_INVALID, "pmc_tune_angular_probabilities: no such source");
+    const DevSource& Q = ctx->dev.src[source];
+    if (Q.angular_kind != PMC_ANGULAR_LASER && Q.angular_kind != PMC_ANGULAR_CONICAL && Q.angular_kind != PMC_ANGULAR_NETZER)
+        return fail(PMC_ERR_INVALID, "pmc_tune_angular_probabilities: the source emits isotropically");
+    if (const char* problem = tupleProblem(n, k, p_out)) return fail(PMC_ERR_INVALID, std::string("pmc_tune_angular_probabilities: ") + problem);
+    if (kind_out) *kind_out = Q.angular_kind;
+    for (int a = 0; axis_out && a < 3; ++a) axis_out[a] = Q.angular_axis[a];
+    if (cos_delta_out) *cos_delta_out = Q.angular_cos_delta;
+    if (n == 0) return PMC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CallBuffers B;
+    double *dK = nullptr, *dP = nullptr;
+    hipError_t e = B.get(size_t(3 * n), &dK, k);
+    if (e == hipSuccess) e = B.get(size_t(n), &dP);
+    if (e == hipSuccess) e = sceneUpToDate(ctx);
+    if (e == hipSuccess) e = pmcLaunchAngularProbabilities(ctx->slot, source, dK, n, dP, ctx->stream);
+    e = finish(ctx, fetch(ctx, e, p_out, dP, size_t(n)));
+    if (e != hipSuccess) return hipFail(e, "pmc_tune_angular_probabilities");
+    return PMC_OK;
+}

@@ -25,7 +25,13 @@ SYMBOLS = ["pmc_abi_version", "pmc_build_info", "pmc_last_error", "pmc_frame_lay
            "pmc_comm_init_rank", "pmc_comm_size", "pmc_comm_destroy", "pmc_reduce_frames", "pmc_allreduce_radiation_field",
            "pmc_debug_tables", "pmc_tuning_set", "pmc_tuning_clear", "pmc_tune_dipole_cosines", "pmc_tune_source_velocities",
            "pmc_launch_flavour", "pmc_tune_log_geometry", "pmc_tune_log_partition", "pmc_tune_rf_log_flush", "pmc_tune_stat_log_flush",
-           "pmc_tune_cell_numbering"]
+           "pmc_tune_cell_numbering", "pmc_tune_device_function", "pmc_tune_device_function_widths", "pmc_tune_locate", "pmc_tune_instrument",
+           "pmc_tune_detector", "pmc_tune_wavelength_bins", "pmc_tune_angular_probabilities"]
+
+# the scene-free device functions of pmc_tune_device_function (include/pmc_tuning.h PMC_FN_*)
+DEVICE_FUNCTIONS = {"hg_value": 0, "hg_cone_mean": 1, "phase_value": 2, "hg_cosine": 3, "dipole_value": 4, "random_direction": 5, "direction_about": 6,
+                    "lambert_lower_branch": 7, "generalized_exp": 8, "interpolate_loglog": 9, "lnmean": 10, "peel_taumax": 11, "shifted_wavelength": 12}
+LOCATE_KINDS = {"locate": 0, "locate_clip": 1, "locate_basic": 2}
 
 _lib = None
 
@@ -39,6 +45,13 @@ class WalkWork(C.Structure):
     """pmc_walk_work_values (include/pmc_tuning.h)"""
     _fields_ = [(n, C.c_uint64) for n in ("peel_wave_steps", "peel_lane_steps", "peel_rounds", "prop_wave_steps",
                                           "prop_lane_steps", "prop_rounds")]
+
+
+class InstrumentValues(C.Structure):
+    """pmc_instrument_values (include/pmc_tuning.h)"""
+    _fields_ = ([(n, C.c_double) for n in ("costheta", "sintheta", "cosphi", "sinphi", "cosomega", "sinomega", "xpmin", "xpsiz", "ypmin", "ypsiz",
+                                           "aperture_r2", "zp1")]
+                + [(n, C.c_int64) for n in ("nxp", "nyp", "num_border", "num_lambda", "include_sed", "include_ifu")])
 
 
 class LogGeometry(C.Structure):
@@ -124,6 +137,15 @@ def lib():
             L.pmc_tune_rf_log_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
             L.pmc_tune_stat_log_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
             L.pmc_tune_cell_numbering.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "pmc_tune_device_function"):  # (likewise)
+            L.pmc_tune_device_function.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+            L.pmc_tune_device_function_widths.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+            L.pmc_tune_locate.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+            L.pmc_tune_instrument.argtypes = [C.c_void_p, C.c_int32, C.POINTER(InstrumentValues), C.c_void_p, C.c_void_p]
+            L.pmc_tune_detector.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+            L.pmc_tune_wavelength_bins.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+            L.pmc_tune_angular_probabilities.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
+                                                         C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -433,6 +455,61 @@ class Engine:
         ext = np.empty(self.log_geometry()["cell_slots"], dtype=np.int32)
         _check(lib().pmc_tune_cell_numbering(self._h, _ptr(ext)))
         return ext
+
+    def device_function(self, function, args, n=None):
+        """test aid (pmc_tune_device_function): the scalar device function `function` (a name of DEVICE_FUNCTIONS or a number) over the argument
+        tuples args[n][width_in]; returns out[n][width_out].  n: the number of tuples, where it is not len(args) (None args: a null pointer)"""
+        fn = DEVICE_FUNCTIONS.get(function, function)
+        win, wout = C.c_int32(1), C.c_int32(1)
+        lib().pmc_tune_device_function_widths(int(fn), C.byref(win), C.byref(wout))  # (an unknown function: the call below says so)
+        a = None if args is None else np.ascontiguousarray(args, dtype=np.float64).reshape(-1, win.value)
+        count = (0 if a is None else a.shape[0]) if n is None else int(n)
+        out = np.empty((max(count, 0), wout.value), dtype=np.float64)
+        _check(lib().pmc_tune_device_function(self._h, int(fn), _ptr(a), count, _ptr(out)))
+        return out
+
+    def locate(self, kind, nodes, x, num_nodes=None):
+        """test aid (pmc_tune_locate): locate / locate_clip / locate_basic (LOCATE_KINDS, or a number) of the values x in the table `nodes`"""
+        nodes = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1)
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        out = np.empty(x.size, dtype=np.int32)
+        count = (0 if nodes is None else nodes.size) if num_nodes is None else int(num_nodes)
+        _check(lib().pmc_tune_locate(self._h, int(LOCATE_KINDS.get(kind, kind)), _ptr(nodes), count, _ptr(x), x.size, _ptr(out)))
+        return out
+
+    def instrument_values(self, instrument):
+        """test aid (pmc_tune_instrument): the constants of an instrument as the device holds them (a dict), with its wavelength grid as
+        `border` and `ellv`"""
+        v = InstrumentValues()
+        _check(lib().pmc_tune_instrument(self._h, int(instrument), C.byref(v), None, None))
+        border, ellv = np.empty(v.num_border, dtype=np.float64), np.empty(v.num_border + 1, dtype=np.int32)
+        _check(lib().pmc_tune_instrument(self._h, int(instrument), C.byref(v), _ptr(border), _ptr(ellv)))
+        values = {n: getattr(v, n) for n, _ in v._fields_}
+        values.update(border=border, ellv=ellv)
+        return values
+
+    def detector(self, instrument, positions):
+        """test aid (pmc_tune_detector): (pixel, inside) of the positions [n][3] (m): pixelOnDetector (-1 off the frame) and insideAperture"""
+        r = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        pixel, inside = np.empty(r.shape[0], dtype=np.int32), np.empty(r.shape[0], dtype=np.int32)
+        _check(lib().pmc_tune_detector(self._h, int(instrument), _ptr(r), r.shape[0], _ptr(pixel), _ptr(inside)))
+        return pixel, inside
+
+    def wavelength_bins(self, instrument, wavelengths):
+        """test aid (pmc_tune_wavelength_bins): the launch kernel's wavelength bin of the instrument for the rest wavelengths (m)"""
+        lam = np.ascontiguousarray(wavelengths, dtype=np.float64).reshape(-1)
+        ell = np.empty(lam.size, dtype=np.int32)
+        _check(lib().pmc_tune_wavelength_bins(self._h, int(instrument), _ptr(lam), lam.size, _ptr(ell)))
+        return ell
+
+    def angular_probabilities(self, source, directions):
+        """test aid (pmc_tune_angular_probabilities): (p, kind, axis, cos_delta): angularProbability of the directions [n][3] for an anisotropic
+        point source, and its distribution as the device holds it"""
+        k = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        p, axis = np.empty(k.shape[0], dtype=np.float64), np.empty(3, dtype=np.float64)
+        kind, cos_delta = C.c_int32(0), C.c_double(0.)
+        _check(lib().pmc_tune_angular_probabilities(self._h, int(source), _ptr(k), k.shape[0], _ptr(p), C.byref(kind), _ptr(axis), C.byref(cos_delta)))
+        return p, kind.value, axis, cos_delta.value
 
     def trace_ray(self, r, k, cap=4096):
         r = np.ascontiguousarray(r, dtype=np.float64)

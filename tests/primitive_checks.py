@@ -1,0 +1,1001 @@
+"""References of the scalar device functions that the photon loop reaches rarely (skirt9_amd/csrc/pmc_transition.inc, pmc_walk.inc,
+pmc_kernels.hip), the argument lists that reach every branch of them, and the rule by which tests/test_gpu_primitives.py accepts what the
+device functions return (include/pmc_tuning.h: pmc_tune_device_function, pmc_tune_locate, pmc_tune_detector, pmc_tune_wavelength_bins,
+pmc_tune_angular_probabilities).  tests/test_primitive_checks.py checks all of it on the CPU.
+
+Every function has two references:
+
+  restate_<f>   the device code -- which is the reference's, SKIRT's -- restated in scalar Python: the same operations in the same order and the
+                same branches, IEEE doubles without contraction, exp / log / pow / acos / cos from the platform's libm (module math), and its sincos
+  exact_<f>     the SAME operation (same branch, same formula, the f64 inputs and constants converted exactly) evaluated with mpmath at
+                DIGITS digits; where a mathematical function stands behind the operation, math_<f> evaluates that one as well (the Lambert
+                function, the cone integral of the Henyey-Greenstein function, the generalised exponential, the logarithmic mean), which
+                would show a misreading of the reference
+
+The acceptance rule (admissible):
+
+  * a function with no libm call between its input and its output (sqrt and the four operations are correctly rounded): the device result
+    equals the restatement bit for bit;
+  * every other function: |device - exact| <= 4 envelope(function, branch) scale + 16 ulp(exact), where the envelope is the largest error of
+    the RESTATEMENT against the exact evaluation over the inputs of that (function, branch) below -- relative (scale = |exact|), or absolute
+    (scale = 1) where the value crosses zero: direction components, cosines, the peel-off depth.  The envelopes are measured when they are
+    asked for (envelopes()), never pasted; a "branch" is a branch of the code together with the listed parameter that decides how badly the
+    branch cancels (|g| of the cone mean, kz of directionAbout), which only makes the rule stricter than one envelope per branch of the code.
+
+Envelopes as measured on glibc 2.39's libm with mpmath 1.3.0 at 50 digits (tests/test_primitive_checks.py prints the table; r: relative, a: absolute;
+the functions marked = are compared bit for bit on the device, their envelopes only describe the formulation):
+
+    hg_cone_mean (r)         |g| = 0.95..    0.97     0.999    0.999999        (0.95..: the double above 0.95; 0.95 itself takes the plain value)
+        forward fold         1.4e-13   1.5e-13   8.4e-11   6.7e-05
+        general              4.7e-14   9.3e-14   4.1e-11   6.7e-05
+        backward fold        1.5e-13   1.5e-13   1.2e-10   7.1e-05
+                             the cancellation in rootFar - rootNear multiplies the last bits of acos and cos: u / (1 - |g|)^2
+    phase_value (r)          the cone mean's for |g| > 0.95; = value 1.4e-13 (at |g| = 0.95)
+    hg_value (r) =           2.0e-04 (at |g| = 0.999999, cos = +-1: the same cancellation)
+    hg_cosine (a) =          |g| = 1e-7 1.2e-09, 1e-6 2.6e-10, 1e-3 2.3e-13, 0.5 5.6e-16, 0.95 1.1e-15, 0.999999 4.4e-10
+    dipole_value (r) =       1.7e-16
+    random_direction (a)     general 4.2e-16, pole 0
+    direction_about (a)      pole|kz=1 1.9e-16, pole|kz=0.99999.. 1.9e-16, general|kz=0.99999 2.8e-16, general|kz=0.99998.. 3.3e-16,
+                             general|kz=0 1.9e-16, general|interior 4.0e-16
+    lambert_lower_branch (r) series 1.1e-16, iterated 8.9e-16, asymptotic 9.3e-17, zero 0
+    generalized_exp (r)      exp 1.1e-16, expansion 3.4e-16, pow 1.1e-13 (the rounding of the base 1 + (1 - p) x, raised to 1 / (1 - p) = 1000)
+    interpolate_loglog (r)   log 1.1e-15, zero 0
+    lnmean (r) =             series 1.9e-16, quotient 1.9e-16, zero 0
+    peel_taumax (a)          log 6.4e-14 (of a sum near 745), dead 0
+    shifted_wavelength (r) = 1.8e-16
+
+Truncation of the operation against the mathematical function behind it, measured the same way (test_primitive_checks.py bounds each from the formulation):
+    lambert_lower_branch     series 2.1e-09 a next to the branch point (the rounding of the constant 1/e under the square root), iterated 5e-35
+    generalized_exp          expansion 2.9e-10 r at x = 3 next to |1 - p| = 1e-3 (the fourth-order term), pow and exp 0
+    lnmean                   series 1.4e-19 r, quotient 2.8e-11 r (x1 = 1e-300: the rounding of the two logarithms it is handed, of size 690)
+    hg_cone_mean             7e-17 r: the operation is the closed-form integral, up to the rounding of pi in the half angle
+"""
+import math
+import struct
+
+import numpy as np
+
+DIGITS = 50
+DBL_MAX = 1.7976931348623157e308
+HALF_ANGLE = 4. * math.pi / 180.   # DustMix.cpp:30 (delta), as the device code forms it
+INVERSE_E = 0.3678794411714423215955237701614608
+LAMBERT_SERIES = (-1.0, 2.331643981597124203363536062168, -1.812187885639363490240191647568, 1.936631114492359755363277457668,
+                  -2.353551201881614516821543561516, 3.066858901050631912893148922704, -4.175335600258177138854984177460,
+                  5.858023729874774148815053846119, -8.401032217523977370984161688514, 12.250753501314460424, -18.100697012472442755,
+                  27.029044799010561650)
+LIGHT_SPEED = 2.99792458e8
+ANGULAR_LASER, ANGULAR_CONICAL, ANGULAR_NETZER = 1, 2, 3   # include/pmc.h PMC_ANGULAR_*
+TINY = 2.0 ** -53
+UP, DOWN = math.inf, -math.inf
+
+
+def _mp():
+    import mpmath
+    mpmath.mp.dps = DIGITS
+    return mpmath
+
+
+_libm_sincos = None
+
+
+def sincos(x):
+    """(sin x, cos x) from libm's sincos, which the device code calls and into which an optimising compiler merges the reference's and the
+    oracle's separate calls of sin and cos of one angle: glibc's sincos differs from its cos in the last bit at about one angle in a thousand"""
+    global _libm_sincos
+    if _libm_sincos is None:
+        import ctypes
+        import ctypes.util
+        _libm_sincos = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6").sincos
+        _libm_sincos.argtypes = [ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+        _libm_sincos.restype = None
+    import ctypes
+    s, c = ctypes.c_double(), ctypes.c_double()
+    _libm_sincos(x, ctypes.byref(s), ctypes.byref(c))
+    return s.value, c.value
+
+
+def bits(values):
+    """the doubles as their 64-bit patterns: equality of these is equality bit for bit (-0. differs from 0., a NaN equals the same NaN)"""
+    return np.ascontiguousarray(values, dtype=np.float64).view(np.uint64)
+
+
+def step(x, n):
+    """the double n places above (n > 0) or below x"""
+    for _ in range(abs(n)):
+        x = math.nextafter(x, UP if n > 0 else DOWN)
+    return x
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# restatements (scalar, f64)
+
+def restate_hg_value(g, c):
+    """PhaseHG::value = valueHG (DustMix.cpp:395-399)"""
+    t = (1. + g * g) - (2. * g) * c
+    return ((1. - g) * (1. + g)) / math.sqrt(t * t * t)
+
+
+def _between(g, near, far):
+    """PhaseHG::between = integralHG (DustMix.cpp:404-411)"""
+    root_near = math.sqrt((1. + g * g) - (2. * g) * near)
+    root_far = math.sqrt((1. + g * g) - (2. * g) * far)
+    scale = ((1. - g) * (1. + g)) / g
+    span = (root_far - root_near) / (root_far * root_near)
+    return scale * span
+
+
+def branch_hg_cone_mean(g, c):
+    theta = math.acos(c)
+    fold = "forward" if theta < HALF_ANGLE else "backward" if theta > math.pi - HALF_ANGLE else "general"
+    return f"{fold}|g={abs(g):.12g}"
+
+
+def restate_hg_cone_mean(g, c):
+    """PhaseHG::coneMean = meanHG (DustMix.cpp:415-425)"""
+    theta = math.acos(c)
+    inner = math.cos(theta - HALF_ANGLE)
+    outer = math.cos(theta + HALF_ANGLE)
+    if theta < HALF_ANGLE:
+        return (_between(g, 1., inner) + _between(g, 1., outer)) / (2. - inner - outer)
+    if theta > math.pi - HALF_ANGLE:
+        return (_between(g, inner, -1.) + _between(g, outer, -1.)) / (2. + inner + outer)
+    return _between(g, inner, outer) / (inner - outer)
+
+
+def branch_phase_value(g, c):
+    return branch_hg_cone_mean(g, c) if abs(g) > 0.95 else "value"
+
+
+def restate_phase_value(g, c):
+    """phaseValue of a Henyey-Greenstein component (DustMix.cpp:440)"""
+    return restate_hg_cone_mean(g, c) if abs(g) > 0.95 else restate_hg_value(g, c)
+
+
+def restate_hg_cosine(g, X):
+    """PhaseHG::cosineFor and PhaseHG::isotropic (DustMix.cpp:501-508): (cosine, 1. if the event scatters isotropically instead)"""
+    f = ((1.0 - g) * (1.0 + g)) / (1.0 - g + 2.0 * g * X)
+    return (1.0 + g * g - f * f) / (2.0 * g), (1. if abs(g) < 1e-6 else 0.)
+
+
+def restate_dipole_value(c):
+    """PhaseDipole::value (DipolePhaseFunction.cpp:47-50)"""
+    return 0.75 * (c * c + 1.)
+
+
+def branch_random_direction(u1, u2):
+    theta = math.acos(2.0 * u1 - 1.0)
+    return "pole" if theta <= 1e-8 or theta >= math.pi - 1e-8 else "general"
+
+
+def restate_random_direction(u1, u2):
+    """randomDirectionFor: Random::direction() with Direction(theta, phi) (Random.cpp:121-126, Direction.cpp:11-38)"""
+    theta = math.acos(2.0 * u1 - 1.0)
+    phi = 2.0 * math.pi * u2
+    if theta <= 1e-8:
+        return 0., 0., 1.
+    if theta >= math.pi - 1e-8:
+        return 0., 0., -1.
+    sintheta, costheta = sincos(theta)
+    sinphi, cosphi = sincos(phi)
+    return sintheta * cosphi, sintheta * sinphi, costheta
+
+
+def _kz_label(kz):
+    return f"kz={abs(kz):.17g}" if abs(kz) in DIRECTION_KZ else "kz=interior"
+
+
+def branch_direction_about(kx, ky, kz, c, u):
+    return ("pole|" if abs(kz) > 0.99999 else "general|") + _kz_label(kz) + ("|beyond" if abs(c) > 1. else "")
+
+
+def restate_direction_about(kx, ky, kz, costheta, u, given=None):
+    """directionAboutFor: Random::direction(bfk, costheta) (Random.cpp:130-164); given: (sin phi, cos phi) to use instead of libm's"""
+    phi = 2.0 * math.pi * u
+    sinphi, cosphi = sincos(phi) if given is None else given
+    sintheta = math.sqrt(abs((1.0 - costheta) * (1.0 + costheta)))
+    if kz > 0.99999:
+        return cosphi * sintheta, sinphi * sintheta, costheta
+    if kz < -0.99999:
+        return cosphi * sintheta, sinphi * sintheta, -costheta
+    root = math.sqrt((1.0 - kz) * (1.0 + kz))
+    return (sintheta / root * (-kx * kz * cosphi + ky * sinphi) + kx * costheta,
+            -sintheta / root * (ky * kz * cosphi + kx * sinphi) + ky * costheta,
+            root * sintheta * cosphi + kz * costheta)
+
+
+def lambert_trace(z):
+    """lambertLowerBranch = SpecialFunctions::LambertW1 (SpecialFunctions.cpp:578-625): (W, branch, rounds, converged)"""
+    if z == 0.0:
+        return -DBL_MAX, "zero", 0, True
+    from_branch_point = z + INVERSE_E
+    root = -math.sqrt(from_branch_point)
+    estimate = LAMBERT_SERIES[11]
+    for term in range(10, -1, -1):
+        estimate = LAMBERT_SERIES[term] + root * estimate
+    if from_branch_point < 3.0e-3:
+        return estimate, "series", 0, True
+    w, branch = estimate, "iterated"
+    if not z < -1e-6:
+        outer = math.log(-z)
+        inner = math.log(-outer)
+        w, branch = outer - inner + inner / outer, "asymptotic"
+    for rounds in range(1, 11):
+        ew = math.exp(w)
+        nxt = w + 1.0
+        correction = w * ew - z
+        correction /= ew * nxt - 0.5 * (nxt + 1.0) * correction / nxt
+        w -= correction
+        if abs(correction) < 1.0e-12 * (1.0 + abs(w)):
+            return w, branch, rounds, True
+    return w, branch, 10, False
+
+
+def branch_lambert(z):
+    return lambert_trace(z)[1]
+
+
+def restate_lambert(z):
+    return lambert_trace(z)[0]
+
+
+def branch_generalized_exp(p, x):
+    deficit = 1.0 - p
+    return "exp" if deficit == 0.0 else "pow" if not abs(deficit) < 1e-3 else "expansion"
+
+
+def restate_generalized_exp(p, x):
+    """generalizedExp = SpecialFunctions::gexp (SpecialFunctions.cpp:822-836)"""
+    deficit = 1.0 - p
+    if deficit == 0.0:
+        return math.exp(x)
+    if not abs(deficit) < 1e-3:
+        return math.pow(1.0 + deficit * x, 1.0 / deficit)
+    xx = x * x
+    first = 0.5 * xx * deficit
+    second = 1.0 / 24.0 * x * xx * (8.0 + 3.0 * x) * deficit * deficit
+    third = 1.0 / 48.0 * xx * xx * (12.0 + 8.0 * x + xx) * deficit * deficit * deficit
+    return math.exp(x) * (1.0 - first + second - third)
+
+
+def branch_interpolate_loglog(x, x1, x2, f1, f2):
+    return "zero" if f1 <= 0 or f2 <= 0 else "log"
+
+
+def restate_interpolate_loglog(x, x1, x2, f1, f2):
+    """NR::interpolateLogLog (NR.hpp:348-362)"""
+    if f1 <= 0 or f2 <= 0:
+        return f1 if x == x1 else f2 if x == x2 else 0.
+    return f1 * math.exp(math.log(x / x1) / math.log(x2 / x1) * (math.log(f2 / f1)))
+
+
+def branch_lnmean(x1, x2, lnx1, lnx2):
+    if x1 > x2:
+        x1, x2 = x2, x1
+    return "zero" if x1 <= 0 else "series" if x2 / x1 - 1. < 1e-3 else "quotient"
+
+
+def restate_lnmean(x1, x2, lnx1, lnx2):
+    """SpecialFunctions::lnmean(x1, x2, lnx1, lnx2) (SpecialFunctions.cpp:860-880)"""
+    if x1 > x2:
+        x1, x2, lnx1, lnx2 = x2, x1, lnx2, lnx1
+    if x1 <= 0:
+        return 0.
+    x = x2 / x1 - 1.
+    if x < 1e-3:
+        return x1 / (1. - 1. / 2. * x + 1. / 3. * x * x - 1. / 4. * x * x * x + 1. / 5. * x * x * x * x - 1. / 6. * x * x * x * x * x)
+    return (x2 - x1) / (lnx2 - lnx1)
+
+
+def branch_peel_taumax(W, lam):
+    return "dead" if W / lam <= 0 else "log"
+
+
+def restate_peel_taumax(W, lam):
+    """taumax of MediumSystem::getExtinctionOpticalDepth (MediumSystem.cpp:1195-1199)"""
+    lum = W / lam
+    return -math.inf if lum <= 0 else math.log(lum) + 745
+
+
+def restate_shifted_wavelength(lambda0, kx, ky, kz, vx, vy, vz):
+    """PhotonPacket::shiftedEmissionWavelength (PhotonPacket.cpp:133-136)"""
+    return lambda0 * (1 - (kx * vx + ky * vy + kz * vz) / LIGHT_SPEED)
+
+
+def restate_locate_basic(nodes, x, n):
+    """NR::locateBasic (NR.hpp:130-147), the loop as written"""
+    jl, ju = -1, n
+    while ju - jl > 1:
+        jm = (ju + jl) >> 1
+        if x < nodes[jm]:
+            ju = jm
+        else:
+            jl = jm
+    return jl
+
+
+def restate_locate(kind, nodes, x):
+    n = len(nodes)
+    if kind == "locate":
+        return n - 2 if x == nodes[n - 1] else restate_locate_basic(nodes, x, n)
+    if kind == "locate_clip":
+        return 0 if x < nodes[0] else restate_locate_basic(nodes, x, n - 1)
+    return restate_locate_basic(nodes, x, n)
+
+
+def reference_locate(kind, nodes, x):
+    """the same three searches through numpy.searchsorted (an array of x)"""
+    nodes, x = np.asarray(nodes, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    n = nodes.size
+    if kind == "locate":
+        return np.where(x == nodes[n - 1], n - 2, np.searchsorted(nodes, x, "right") - 1).astype(np.int32)
+    if kind == "locate_clip":
+        return np.where(x < nodes[0], 0, np.searchsorted(nodes[:n - 1], x, "right") - 1).astype(np.int32)
+    return (np.searchsorted(nodes, x, "right") - 1).astype(np.int32)
+
+
+def detector_plane(I, r):
+    """(xp, yp, xpp, ypp) of the positions r[n][3] for the instrument values I (FrameInstrument.cpp:45-58), the operations in the device's order"""
+    x, y, z = r[:, 0], r[:, 1], r[:, 2]
+    xpp = -I["sinphi"] * x + I["cosphi"] * y
+    ypp = -I["cosphi"] * I["costheta"] * x - I["sinphi"] * I["costheta"] * y + I["sintheta"] * z
+    xp = I["cosomega"] * xpp - I["sinomega"] * ypp
+    yp = I["sinomega"] * xpp + I["cosomega"] * ypp
+    return xp, yp, xpp, ypp
+
+
+def pixel_coordinates(I, r):
+    """the pixel coordinates before they are cut to the frame: floor towards minus infinity (as doubles)"""
+    xp, yp, _, _ = detector_plane(I, np.asarray(r, dtype=np.float64).reshape(-1, 3))
+    return np.floor((xp - I["xpmin"]) / I["xpsiz"]), np.floor((yp - I["ypmin"]) / I["ypsiz"])
+
+
+def reference_pixel(I, r):
+    """FrameInstrument::pixelOnDetector (FrameInstrument.cpp:45-65): i + nxp j, or -1"""
+    i, j = pixel_coordinates(I, r)
+    off = (i < 0) | (i >= I["nxp"]) | (j < 0) | (j >= I["nyp"])
+    return np.where(off, -1, np.where(off, 0, i) + I["nxp"] * np.where(off, 0, j)).astype(np.int32)
+
+
+def reference_inside(I, r):
+    """ApertureInstrument::isInsideAperture (ApertureInstrument.cpp:22-43): 1 or 0"""
+    r = np.asarray(r, dtype=np.float64).reshape(-1, 3)
+    if I["aperture_r2"] == 0.:
+        return np.ones(r.shape[0], dtype=np.int32)
+    _, _, xpp, ypp = detector_plane(I, r)
+    return (~(xpp * xpp + ypp * ypp > I["aperture_r2"])).astype(np.int32)
+
+
+def reference_bin(I, lam):
+    """DisjointWavelengthGrid::bin of the redshifted wavelength (DisjointWavelengthGrid.cpp:334-345, FluxRecorder.cpp:309-310)"""
+    lam = np.asarray(lam, dtype=np.float64)
+    return np.asarray(I["ellv"])[np.searchsorted(I["border"], lam * I["zp1"], "right")].astype(np.int32)
+
+
+def restate_angular_probability(kind, axis, cos_delta, k):
+    """angularProbability (LaserAngularDistribution.cpp:11-16, ConicalAngularDistribution.cpp:19-25, NetzerAngularDistribution.cpp:34-38)"""
+    costheta = axis[0] * k[0] + axis[1] * k[1] + axis[2] * k[2]
+    if kind == ANGULAR_LASER:
+        return math.inf if costheta > 0.99999 else 0.
+    if kind == ANGULAR_CONICAL:
+        return 1.0 / (1.0 - cos_delta) if abs(costheta) > cos_delta else 0.
+    sign = 1. if costheta > 0 else -1.
+    return (6. / 7.) * costheta * (2. * costheta + sign)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# exact evaluations of the same operations (mpmath); the branch is the restatement's
+
+def exact_hg_value(g, c):
+    mp = _mp()
+    g, c = mp.mpf(g), mp.mpf(c)
+    t = (1 + g * g) - 2 * g * c
+    return (1 - g) * (1 + g) / mp.sqrt(t * t * t)
+
+
+def _exact_between(mp, g, near, far):
+    root_near = mp.sqrt(1 + g * g - 2 * g * near)
+    root_far = mp.sqrt(1 + g * g - 2 * g * far)
+    return (1 - g) * (1 + g) / g * ((root_far - root_near) / (root_far * root_near))
+
+
+def exact_hg_cone_mean(g, c, half_angle=None, fold=None):
+    mp = _mp()
+    fold = branch_hg_cone_mean(g, c).split("|")[0] if fold is None else fold
+    half = mp.mpf(HALF_ANGLE) if half_angle is None else half_angle
+    g = mp.mpf(g)
+    theta = mp.acos(mp.mpf(c))
+    inner, outer = mp.cos(theta - half), mp.cos(theta + half)
+    if fold == "forward":
+        return (_exact_between(mp, g, 1, inner) + _exact_between(mp, g, 1, outer)) / (2 - inner - outer)
+    if fold == "backward":
+        return (_exact_between(mp, g, inner, -1) + _exact_between(mp, g, outer, -1)) / (2 + inner + outer)
+    return _exact_between(mp, g, inner, outer) / (inner - outer)
+
+
+def math_hg_cone_mean(g, c):
+    """the mean of the Henyey-Greenstein function over the cone of 4 degrees about theta, folded at a pole, from the antiderivative
+    (1 - g^2) / (g sqrt(1 + g^2 - 2 g mu)) of the function, with the true pi; the fold is decided exactly"""
+    mp = _mp()
+    half = 4 * mp.pi / 180
+    g = mp.mpf(g)
+    theta = mp.acos(mp.mpf(c))
+
+    def F(mu):
+        return (1 - g * g) / (g * mp.sqrt(1 + g * g - 2 * g * mu))
+    inner, outer = mp.cos(theta - half), mp.cos(theta + half)
+    if theta < half:
+        return (2 * F(1) - F(inner) - F(outer)) / (2 - inner - outer)
+    if theta > mp.pi - half:
+        return (F(inner) + F(outer) - 2 * F(-1)) / (2 + inner + outer)
+    return (F(inner) - F(outer)) / (inner - outer)
+
+
+def exact_phase_value(g, c):
+    return exact_hg_cone_mean(g, c) if abs(g) > 0.95 else exact_hg_value(g, c)
+
+
+def exact_hg_cosine(g, X):
+    mp = _mp()
+    g, X = mp.mpf(g), mp.mpf(X)
+    f = (1 - g) * (1 + g) / (1 - g + 2 * g * X)
+    return (1 + g * g - f * f) / (2 * g)
+
+
+def exact_dipole_value(c):
+    mp = _mp()
+    return mp.mpf("0.75") * (mp.mpf(c) * mp.mpf(c) + 1)
+
+
+def exact_random_direction(u1, u2):
+    mp = _mp()
+    if branch_random_direction(u1, u2) == "pole":
+        return tuple(mp.mpf(v) for v in restate_random_direction(u1, u2))
+    theta = mp.acos(2 * mp.mpf(u1) - 1)
+    phi = 2 * mp.mpf(math.pi) * mp.mpf(u2)
+    return mp.sin(theta) * mp.cos(phi), mp.sin(theta) * mp.sin(phi), mp.cos(theta)
+
+
+def exact_direction_about(kx, ky, kz, c, u):
+    mp = _mp()
+    pole = abs(kz) > 0.99999
+    kx, ky, kz, c = mp.mpf(kx), mp.mpf(ky), mp.mpf(kz), mp.mpf(c)
+    phi = 2 * mp.mpf(math.pi) * mp.mpf(u)
+    sinphi, cosphi = mp.sin(phi), mp.cos(phi)
+    sintheta = mp.sqrt(abs((1 - c) * (1 + c)))
+    if pole:
+        return cosphi * sintheta, sinphi * sintheta, (c if kz > 0 else -c)
+    root = mp.sqrt((1 - kz) * (1 + kz))
+    return (sintheta / root * (-kx * kz * cosphi + ky * sinphi) + kx * c, -sintheta / root * (ky * kz * cosphi + kx * sinphi) + ky * c,
+            root * sintheta * cosphi + kz * c)
+
+
+def exact_lambert(z):
+    """the series summed exactly, or as many exact Halley rounds as the restatement took from the exact start value"""
+    mp = _mp()
+    _, branch, rounds, _ = lambert_trace(z)
+    if branch == "zero":
+        return mp.mpf(-DBL_MAX)
+    z = mp.mpf(z)
+    root = -mp.sqrt(z + mp.mpf(INVERSE_E))
+    w = mp.mpf(LAMBERT_SERIES[11])
+    for term in range(10, -1, -1):
+        w = mp.mpf(LAMBERT_SERIES[term]) + root * w
+    if branch == "series":
+        return w
+    if branch == "asymptotic":
+        outer = mp.log(-z)
+        inner = mp.log(-outer)
+        w = outer - inner + inner / outer
+    for _ in range(rounds):
+        ew = mp.exp(w)
+        nxt = w + 1
+        correction = w * ew - z
+        correction /= ew * nxt - (nxt + 1) * correction / (2 * nxt)
+        w -= correction
+    return w
+
+
+def math_lambert(z):
+    mp = _mp()
+    return mp.lambertw(mp.mpf(z), -1).real
+
+
+def exact_generalized_exp(p, x):
+    mp = _mp()
+    branch = branch_generalized_exp(p, x)
+    d, x = 1 - mp.mpf(p), mp.mpf(x)
+    if branch == "exp":
+        return mp.exp(x)
+    if branch == "pow":
+        return mp.power(1 + d * x, 1 / d)
+    xx = x * x
+    return mp.exp(x) * (1 - xx * d / 2 + x * xx * (8 + 3 * x) * d * d / 24 - xx * xx * (12 + 8 * x + xx) * d * d * d / 48)
+
+
+def math_generalized_exp(p, x):
+    mp = _mp()
+    d, x = 1 - mp.mpf(p), mp.mpf(x)
+    return mp.exp(x) if d == 0 else mp.power(1 + d * x, 1 / d)
+
+
+def exact_interpolate_loglog(x, x1, x2, f1, f2):
+    mp = _mp()
+    if branch_interpolate_loglog(x, x1, x2, f1, f2) == "zero":
+        return mp.mpf(restate_interpolate_loglog(x, x1, x2, f1, f2))
+    x, x1, x2, f1, f2 = (mp.mpf(v) for v in (x, x1, x2, f1, f2))
+    return f1 * mp.exp(mp.log(x / x1) / mp.log(x2 / x1) * mp.log(f2 / f1))
+
+
+def exact_lnmean(x1, x2, lnx1, lnx2):
+    mp = _mp()
+    branch = branch_lnmean(x1, x2, lnx1, lnx2)
+    if x1 > x2:
+        x1, x2, lnx1, lnx2 = x2, x1, lnx2, lnx1
+    if branch == "zero":
+        return mp.mpf(0)
+    x1, x2, lnx1, lnx2 = (mp.mpf(v) for v in (x1, x2, lnx1, lnx2))
+    if branch == "quotient":
+        return (x2 - x1) / (lnx2 - lnx1)
+    x = x2 / x1 - 1
+    return x1 / (1 - x / 2 + x ** 2 / 3 - x ** 3 / 4 + x ** 4 / 5 - x ** 5 / 6)
+
+
+def math_lnmean(x1, x2):
+    """(x2 - x1) / ln(x2 / x1), x1 where the two are equal"""
+    mp = _mp()
+    x1, x2 = mp.mpf(min(x1, x2)), mp.mpf(max(x1, x2))
+    return x1 if x1 == x2 else (x2 - x1) / mp.log(x2 / x1)
+
+
+def exact_peel_taumax(W, lam):
+    mp = _mp()
+    if branch_peel_taumax(W, lam) == "dead":
+        return mp.mpf("-inf")
+    return mp.log(mp.mpf(W / lam)) + 745   # (the quotient is one correctly rounded operation; the log and the sum are what is evaluated exactly)
+
+
+def exact_shifted_wavelength(lambda0, kx, ky, kz, vx, vy, vz):
+    mp = _mp()
+    lambda0, kx, ky, kz, vx, vy, vz = (mp.mpf(v) for v in (lambda0, kx, ky, kz, vx, vy, vz))
+    return lambda0 * (1 - (kx * vx + ky * vy + kz * vz) / mp.mpf(LIGHT_SPEED))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# argument lists: the smallest that reach every branch, and a few hundred interior points per function from a fixed seed
+
+def _rng(tag):
+    return np.random.default_rng([20261019, tag])
+
+
+def _signed(values):
+    return [s * v for v in values for s in (1., -1.)]
+
+
+CONE_G = _signed([0.95, math.nextafter(0.95, 1.), 0.97, 0.999, 0.999999])
+DEG = math.pi / 180.
+CONE_COS = sorted(set(_signed([1., math.nextafter(1., 0.), 1. - 1e-12, math.cos(2. * DEG), math.cos(4. * DEG * (1. + 1e-9)), math.cos(4. * DEG * (1. - 1e-9)),
+                               math.cos(4. * DEG), 0.9, 0.3, 0.])))
+
+
+def inputs_hg_cone_mean():
+    """(g, cos): every listed g with every listed cosine, and per g 24 angles inside either fold and 48 between them"""
+    rng = _rng(1)
+    rows = [(g, c) for g in CONE_G for c in CONE_COS]
+    for g in CONE_G:
+        angles = np.concatenate((rng.uniform(0., HALF_ANGLE, 24), rng.uniform(math.pi - HALF_ANGLE, math.pi, 24), rng.uniform(HALF_ANGLE, math.pi - HALF_ANGLE, 48)))
+        rows += [(g, math.cos(a)) for a in angles]
+    return np.array(rows)
+
+
+def inputs_phase_value():
+    """(g, cos): the cone-mean list, and the asymmetries up to the switch |g| = 0.95 itself, which take the plain value"""
+    plain = _signed([0.95, math.nextafter(0.95, 0.), 0.5, 1e-6]) + [0.]
+    rows = [(g, c) for g in plain for c in CONE_COS] + [(g, c) for g in plain for c in _rng(2).uniform(-1., 1., 16)]
+    return np.concatenate((inputs_hg_cone_mean(), np.array(rows)))
+
+
+def inputs_hg_value():
+    gs = _signed([1e-6, 1e-3, 0.5, 0.95, 0.999999]) + [0.]
+    return np.array([(g, c) for g in gs for c in CONE_COS] + [(g, c) for g, c in zip(_rng(3).uniform(-0.95, 0.95, 300), _rng(4).uniform(-1., 1., 300))])
+
+
+HG_COSINE_G = _signed([1e-6, math.nextafter(1e-6, 1.), 1e-3, 0.5, 0.95, 0.999999])
+HG_COSINE_X = [0., TINY, 1e-9, 0.25, 0.5, 0.75, 1. - 1e-9, 1. - TINY]
+
+
+def inputs_hg_cosine():
+    """(g, X); |g| just below 1e-6 is there for the flag of the isotropic branch"""
+    below = _signed([math.nextafter(1e-6, 0.), 1e-7])
+    rows = [(g, X) for g in HG_COSINE_G + below for X in HG_COSINE_X]
+    rows += [(g, X) for g in HG_COSINE_G for X in _rng(5).uniform(0., 1., 25)]
+    return np.array(rows)
+
+
+def branch_hg_cosine(g, X):
+    return f"g={abs(g):.17g}"
+
+
+def inputs_dipole_value():
+    return np.array(CONE_COS + list(_rng(6).uniform(-1., 1., 200))).reshape(-1, 1)
+
+
+RANDOM_U1 = [0., 2. ** -54, TINY, 2. ** -52, 0.5, 1. - 2. ** -52, 1. - TINY, 1.]
+RANDOM_U2 = [0., TINY, 0.125, 0.25, 0.5, 0.75, 0.9, 1. - TINY]
+
+
+def inputs_random_direction():
+    """(u1, u2): theta = acos(2 u1 - 1) is 0 for u1 = 1 and 2.1e-8 for the next smaller u1, pi for u1 = 0 and pi - 1.5e-8 for 2^-54 (no double
+    gives an angle between 0 and 1e-8: 2 u1 - 1 has a spacing of 1.1e-16 below 1)"""
+    rows = [(u1, u2) for u1 in RANDOM_U1 for u2 in RANDOM_U2]
+    rows += list(zip(_rng(7).uniform(0., 1., 300), _rng(8).uniform(0., 1., 300)))
+    return np.array(rows)
+
+
+DIRECTION_KZ = [1., 0.99999, math.nextafter(0.99999, 1.), math.nextafter(0.99999, 0.), 0.]
+DIRECTION_COS = [1., -1., 0., 0.3]
+DIRECTION_U = [0., 0.25, 0.5, 1. - TINY]
+
+
+def _unit(kz, azimuth):
+    """a direction with this kz exactly, normalised in f64"""
+    s = math.sqrt((1. - kz) * (1. + kz))
+    return s * math.cos(azimuth), s * math.sin(azimuth), kz
+
+
+def inputs_direction_about(cosines=None):
+    """(kx, ky, kz, cos, u): every listed kz (three azimuths of k each) with every listed cosine and deviate, and 300 interior tuples; with
+    `cosines`, those instead of the listed ones and no interior tuples (the cosines that the HG sampler returns)"""
+    rows = []
+    for kz in sorted(set(_signed(DIRECTION_KZ))):
+        for azimuth in (0., 0.7, 4.):
+            k = _unit(kz, azimuth)
+            rows += [k + (c, u) for c in (DIRECTION_COS if cosines is None else cosines) for u in DIRECTION_U]
+    if cosines is None:
+        rng = _rng(9)
+        for kz, azimuth, c, u in zip(rng.uniform(-0.9999, 0.9999, 300), rng.uniform(0., 6.28, 300), rng.uniform(-1., 1., 300), rng.uniform(0., 1., 300)):
+            rows.append(_unit(kz, azimuth) + (c, u))
+    return np.array(rows)
+
+
+def lambert_z(X):
+    """the argument the launch kernel hands the function for the deviate X: (X - 1) / e (ExpDiskGeometry.cpp:47-51)"""
+    return (X - 1.0) / math.e
+
+
+def inputs_lambert():
+    X = [TINY] + list(np.logspace(-16, -1, 61)) + list(np.linspace(0.1, 0.9, 41)) + list(1. - np.logspace(-16, -1, 61)) + [1. - TINY]
+    z = [lambert_z(x) for x in X]
+    for switch in (3e-3 - INVERSE_E, -1e-6):
+        z += [step(switch, n) for n in range(-3, 4)]
+    z += [0., -INVERSE_E, step(-INVERSE_E, 1)]
+    z += list(-INVERSE_E * _rng(10).uniform(0., 1., 200))
+    return np.array(z).reshape(-1, 1)
+
+
+GEXP_DEFICIT = [0.] + _signed([1e-12, 1e-8, 1e-4, math.nextafter(1e-3, 0.), 1e-3, 2e-3, 1e-2]) + [0.5, -2.]
+GEXP_X = [-3., -1., -0.1, -1e-8, 0., 1e-8, 0.1, 0.5, 1., 3.]
+
+
+def inputs_generalized_exp():
+    """(p, x) with the p nearest to 1 - d for every listed d = 1 - p; only where 1 + (1 - p) x > 0.  The function forms 1 - p itself, which is a
+    multiple of 2^-53: next to the switch |1 - p| = 1e-3 the list holds the five doubles p about 1 -+ 1e-3, whose 1 - p are the nearest values
+    that a p can give on either side of 1e-3 (1e-3 itself and the double below it are not among them)"""
+    rows = [(1. - d, x) for d in GEXP_DEFICIT for x in GEXP_X]
+    rows += [(step(1. - d, n), x) for d in (1e-3, -1e-3) for n in (-2, -1, 1, 2) for x in GEXP_X]
+    rng = _rng(11)
+    rows += list(zip(1. - rng.uniform(-1e-3, 1e-3, 150), rng.uniform(-3., 3., 150)))
+    rows += list(zip(1. - rng.uniform(-0.3, 0.3, 150), rng.uniform(-3., 3., 150)))
+    return np.array([(p, x) for p, x in rows if 1.0 + (1.0 - p) * x > 0.])
+
+
+def inputs_interpolate_loglog():
+    rows = []
+    x1, x2 = 0.37, 4.1
+    for f1 in (2.5, 0., -1.):
+        for f2 in (0.4, 0., -3.):
+            rows += [(x, x1, x2, f1, f2) for x in (x1, x2, 1.9, math.nextafter(x1, 1.), math.nextafter(x2, 0.))]
+    rng = _rng(12)
+    for a, b, t, f1, f2 in zip(rng.uniform(0.1, 2., 200), rng.uniform(1.01, 30., 200), rng.uniform(0., 1., 200), rng.lognormal(0., 3., 200), rng.lognormal(0., 3., 200)):
+        rows.append((a * b ** t, a, a * b, f1, f2))
+    return np.array(rows)
+
+
+LNMEAN_RATIO = [0., 1e-16, 1e-12, 1e-8, 1e-4, math.nextafter(1e-3, 0.), 1e-3, math.nextafter(1e-3, 1.), 2e-3, 1e-2, 1., 10., 1e6]
+
+
+def inputs_lnmean():
+    """(x1, x2, ln x1, ln x2), the logarithms as the host computes them; both orders of the arguments"""
+    pairs = []
+    for x1 in (0.37, 1e-300):
+        pairs += [(x1, x1 * (1. + ratio)) for ratio in LNMEAN_RATIO]
+    rng = _rng(13)
+    pairs += [(a, a * (1. + r)) for a, r in zip(rng.lognormal(0., 5., 150), rng.uniform(0., 2e-3, 150))]
+    pairs += [(a, a * (1. + r)) for a, r in zip(rng.lognormal(0., 5., 150), rng.lognormal(0., 3., 150))]
+    rows = []
+    for a, b in pairs:
+        rows += [(a, b, math.log(a), math.log(b)), (b, a, math.log(b), math.log(a))]
+    for x1 in (0., -1.):   # (a non-positive argument: the logarithms are not looked at)
+        rows += [(x1, 0.37, -math.inf, math.log(0.37)), (0.37, x1, math.log(0.37), -math.inf), (x1, x1, 0., 0.)]
+    return np.array(rows)
+
+
+def inputs_peel_taumax():
+    lam = 5.5e-7
+    rows = [(3.2e30, lam), (0., lam), (-1.5, lam), (5e-324 * 3, 1.), (1e-315, 2.), (2.2250738585072014e-308, 1.)]
+    rows += [(w, l) for w, l in zip(_rng(14).lognormal(40., 30., 200), _rng(15).uniform(1e-7, 1e-4, 200))]
+    return np.array(rows)
+
+
+def inputs_shifted_wavelength():
+    rng = _rng(16)
+    rows = [(5.5e-7, 0., 0., 1., 0., 0., 0.), (5.5e-7, 0., 0., 1., 0., 0., LIGHT_SPEED), (5.5e-7, 0., 0., -1., 0., 0., 1e5), (1., 0.6, 0., 0.8, 3e5, -2e5, 1e3)]
+    for _ in range(200):
+        k = rng.normal(size=3)
+        k /= np.linalg.norm(k)
+        rows.append((rng.uniform(1e-7, 1e-4),) + tuple(k) + tuple(rng.normal(scale=3e5, size=3)))
+    return np.array(rows)
+
+
+def locate_tables():
+    """tables of 2, 3, 64 and 65 nodes, and a cumulative distribution with repeated nodes (zero density)"""
+    rng = _rng(17)
+    tables = {n: np.cumsum(rng.uniform(0.1, 1., n)) - 3. for n in (2, 3, 64, 65)}
+    tables["repeated"] = np.array([0., 0., 0.125, 0.125, 0.125, 0.5, 0.75, 0.75, 1., 1.])
+    return tables
+
+
+def locate_probes(nodes):
+    """below the first node, on every node and on the doubles next to it on either side, above the last node"""
+    x = [nodes[0] - 1., nodes[-1] + 1., -math.inf, math.inf]
+    for v in nodes:
+        x += [math.nextafter(v, DOWN), v, math.nextafter(v, UP)]
+    return np.array(x)
+
+
+def positions_from_plane(I, xp, yp):
+    """positions r[n][3] that project onto the detector coordinates (xp, yp), up to rounding: the inverse of detector_plane on the plane
+    through the origin"""
+    xp, yp = np.broadcast_arrays(np.asarray(xp, dtype=np.float64), np.asarray(yp, dtype=np.float64))
+    xpp = I["cosomega"] * xp + I["sinomega"] * yp
+    ypp = -I["sinomega"] * xp + I["cosomega"] * yp
+    e1 = np.array([-I["sinphi"], I["cosphi"], 0.])
+    e2 = np.array([-I["cosphi"] * I["costheta"], -I["sinphi"] * I["costheta"], I["sintheta"]])
+    return xpp.reshape(-1, 1) * e1 + ypp.reshape(-1, 1) * e2
+
+
+SWEEP = 6   # a border is approached in steps of a few ulp from either side: the projection of a position rounds, so that hitting a border
+            # takes a sweep of positions across it (test_primitive_checks.py asserts that either side of every border is reached)
+
+
+def _sweep(value, extent=0.):
+    """the value, the two doubles on either side of it, and SWEEP steps of an ulp of max(|value|, extent) on either side: `extent` is the size
+    of the coordinates that the projection mixes into this one, whose roundings decide on which side of the value a position lands"""
+    size = max(abs(value), extent)
+    near = [step(value, n) for n in (-2, -1, 0, 1, 2)]
+    return sorted(set(near + [value + n * size * 2. ** -52 for n in range(-SWEEP, SWEEP + 1)]))
+
+
+def frame_positions(I):
+    """positions about every pixel border of the frame in x (at three heights) and in y (at three abscissae), the far edges i = nxp, j = nyp
+    included; one pixel outside on each side; the four corners; a position 10^6 frame widths away in each direction"""
+    nxp, nyp = int(I["nxp"]), int(I["nyp"])
+    x_of = lambda i: I["xpmin"] + i * I["xpsiz"]   # noqa: E731
+    y_of = lambda j: I["ypmin"] + j * I["ypsiz"]   # noqa: E731
+    extent = max(abs(x_of(0)), abs(x_of(nxp)), abs(y_of(0)), abs(y_of(nyp)))
+    plane = []
+    for i in range(nxp + 1):
+        plane += [(x, y_of(j)) for x in _sweep(x_of(i), extent) for j in (0.5, nyp / 2., nyp - 0.5)]
+    for j in range(nyp + 1):
+        plane += [(x_of(i), y) for y in _sweep(y_of(j), extent) for i in (0.5, nxp / 2., nxp - 0.5)]
+    for i in (-1., -0.5, nxp + 0.5, nxp + 1.):
+        plane += [(x_of(i), y_of(j)) for j in (-0.5, 0.5, nyp - 0.5, nyp + 0.5)]
+    for j in (-1., -0.5, nyp + 0.5, nyp + 1.):
+        plane += [(x_of(i), y_of(j)) for i in (0.5, nxp - 0.5)]
+    for i in (0, nxp):
+        for j in (0, nyp):
+            plane += [(x, y) for x in (step(x_of(i), -1), x_of(i), step(x_of(i), 1)) for y in (step(y_of(j), -1), y_of(j), step(y_of(j), 1))]
+    far = 1e6 * max(nxp * I["xpsiz"], nyp * I["ypsiz"])
+    plane += [(far, 0.), (-far, 0.), (0., far), (0., -far), (far, far), (-far, -far)]
+    plane = np.array(plane)
+    return positions_from_plane(I, plane[:, 0], plane[:, 1])
+
+
+def aperture_positions(I):
+    """positions whose squared distance from the line of sight sweeps across aperture_r2, along four directions in the plane; the axis; far out"""
+    radius = math.sqrt(I["aperture_r2"])
+    plane = [(0., 0.), (10. * radius, 0.), (0., -10. * radius)]
+    for angle in (0., 0.5 * math.pi, 0.3, 2.):
+        plane += [(r * math.cos(angle), r * math.sin(angle)) for r in _sweep(radius)]
+    plane = np.array(plane)
+    return positions_from_plane(I, plane[:, 0], plane[:, 1])
+
+
+def bin_wavelengths(I):
+    """rest wavelengths whose redshifted value sweeps across every border of the instrument's grid; below the first border, above the last"""
+    border, zp1 = np.asarray(I["border"]), I["zp1"]
+    lam = [border[0] / zp1 * 0.5, border[-1] / zp1 * 2., 0., math.inf]
+    for b in border:
+        lam += _sweep(b / zp1)
+    return np.array(lam)
+
+
+def angular_directions(kind, axis, cos_delta):
+    """directions whose cosine to the axis sweeps across the switch of the distribution (0.99999 for the laser, +-cos delta for the cone, 0 for
+    Netzer's sign), the axis and its opposite, and 100 directions all over the sphere"""
+    axis = np.asarray(axis, dtype=np.float64)
+    other = np.cross(axis, [0.3, -0.5, 0.8])
+    other /= np.linalg.norm(other)
+    switch = {ANGULAR_LASER: [0.99999], ANGULAR_CONICAL: [cos_delta, -cos_delta], ANGULAR_NETZER: [0., 1e-300, 0.5, -0.5]}[kind]
+    cosines = [1., -1.]
+    for s in switch:
+        cosines += [min(1., max(-1., c)) for c in _sweep(s)]
+    rows = [c * axis + math.sqrt((1. - c) * (1. + c)) * other for c in cosines]
+    # ... and, where a few ulp in one component get there, a direction whose cosine as the function forms it IS the switch value
+    for s in switch:
+        start = s * axis + math.sqrt((1. - s) * (1. + s)) * other
+        hits = (k for n in range(0, 65) for m in (n, -n) for a in range(3)
+                for k in [np.array([step(float(start[b]), m) if b == a else float(start[b]) for b in range(3)])]
+                if axis[0] * k[0] + axis[1] * k[1] + axis[2] * k[2] == s)
+        rows += [hit for hit in [next(hits, None)] if hit is not None]
+    k = _rng(18).normal(size=(100, 3))
+    rows += list(k / np.linalg.norm(k, axis=1, keepdims=True))
+    return np.array(rows)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the table of functions, the envelopes and the acceptance rule
+
+class Function:
+    def __init__(self, name, restate, exact, branch, inputs, bitwise, absolute=False, outputs=1):
+        self.name, self.restate, self.exact, self.branch, self.inputs = name, restate, exact, branch, inputs
+        self.bitwise = bitwise      # no libm call between input and output: the device equals the restatement bit for bit
+        self.absolute = absolute    # the value crosses zero: absolute errors
+        self.outputs = outputs
+
+
+def _one(label):
+    return lambda *a: label
+
+
+FUNCTIONS = {f.name: f for f in (
+    Function("hg_value", restate_hg_value, exact_hg_value, _one("value"), inputs_hg_value, True),
+    Function("hg_cone_mean", restate_hg_cone_mean, exact_hg_cone_mean, branch_hg_cone_mean, inputs_hg_cone_mean, False),
+    Function("phase_value", restate_phase_value, exact_phase_value, branch_phase_value, inputs_phase_value, False),
+    Function("hg_cosine", lambda g, X: restate_hg_cosine(g, X)[0], exact_hg_cosine, branch_hg_cosine, inputs_hg_cosine, True, absolute=True),
+    Function("dipole_value", restate_dipole_value, exact_dipole_value, _one("value"), inputs_dipole_value, True),
+    Function("random_direction", restate_random_direction, exact_random_direction, branch_random_direction, inputs_random_direction, False, True, 3),
+    Function("direction_about", restate_direction_about, exact_direction_about, branch_direction_about, inputs_direction_about, False, True, 3),
+    Function("lambert_lower_branch", restate_lambert, exact_lambert, branch_lambert, inputs_lambert, False),
+    Function("generalized_exp", restate_generalized_exp, exact_generalized_exp, branch_generalized_exp, inputs_generalized_exp, False),
+    Function("interpolate_loglog", restate_interpolate_loglog, exact_interpolate_loglog, branch_interpolate_loglog, inputs_interpolate_loglog, False),
+    Function("lnmean", restate_lnmean, exact_lnmean, branch_lnmean, inputs_lnmean, True),
+    Function("peel_taumax", restate_peel_taumax, exact_peel_taumax, branch_peel_taumax, inputs_peel_taumax, False, absolute=True),
+    Function("shifted_wavelength", restate_shifted_wavelength, exact_shifted_wavelength, _one("value"), inputs_shifted_wavelength, True),
+)}
+# branches whose value is a constant or one of the arguments, whatever the function: bit for bit
+BITWISE_BRANCHES = {("phase_value", "value"), ("interpolate_loglog", "zero"), ("lambert_lower_branch", "zero"), ("peel_taumax", "dead"),
+                    ("random_direction", "pole")}
+
+
+def is_bitwise(name, branch):
+    return FUNCTIONS[name].bitwise or (name, branch) in BITWISE_BRANCHES
+
+
+def restated(name, inputs):
+    """the restatement over the tuples inputs[n][width]: [n][outputs]"""
+    f = FUNCTIONS[name]
+    return np.array([np.atleast_1d(f.restate(*(float(v) for v in row))) for row in inputs], dtype=np.float64).reshape(len(inputs), f.outputs)
+
+
+def branches(name, inputs):
+    f = FUNCTIONS[name]
+    return [f.branch(*(float(v) for v in row)) for row in inputs]
+
+
+_exact_cache = {}
+
+
+def exact(name, inputs):
+    """the exact evaluation over the tuples: a list of tuples of mpmath numbers (computed once per function and argument list)"""
+    key = (name, np.ascontiguousarray(inputs, dtype=np.float64).tobytes())
+    if key not in _exact_cache:
+        f = FUNCTIONS[name]
+        rows = []
+        for row in inputs:
+            value = f.exact(*(float(v) for v in row))
+            rows.append(tuple(value) if isinstance(value, tuple) else (value,))
+        _exact_cache[key] = rows
+    return _exact_cache[key]
+
+
+def errors(name, inputs, values):
+    """|values - exact| per tuple (the largest over the outputs), relative to |exact| unless the function is an absolute one; floats.  An
+    infinite exact value must be met exactly (error 0, else inf)"""
+    mp = _mp()
+    f = FUNCTIONS[name]
+    values = np.asarray(values, dtype=np.float64).reshape(len(inputs), f.outputs)
+    out = np.zeros(len(inputs))
+    for i, want in enumerate(exact(name, inputs)):
+        worst = mp.mpf(0)
+        for got, e in zip(values[i], want):
+            if mp.isinf(e) or not math.isfinite(got):
+                err = mp.mpf(0) if mp.isinf(e) and got == float(e) else mp.inf
+            else:
+                err = abs(mp.mpf(float(got)) - e)
+                if not f.absolute and e != 0:
+                    err /= abs(e)
+            worst = max(worst, err)
+        out[i] = float(worst)
+    return out
+
+
+_envelope_cache = {}
+
+
+def envelopes(name, inputs=None):
+    """{branch: the largest error of the restatement against the exact evaluation over the branch's tuples of the function's argument list}"""
+    inputs = FUNCTIONS[name].inputs() if inputs is None else inputs
+    key = (name, np.ascontiguousarray(inputs, dtype=np.float64).tobytes())
+    if key not in _envelope_cache:
+        err = errors(name, inputs, restated(name, inputs))
+        table = {}
+        for b, e in zip(branches(name, inputs), err):
+            table[b] = max(table.get(b, 0.), e)
+        _envelope_cache[key] = table
+    return _envelope_cache[key]
+
+
+def inadmissible(name, inputs, values, envelope=None):
+    """the tuples at which `values` [n][outputs] miss the acceptance rule, as a list of messages (empty: all pass).  Bit-for-bit functions and
+    branches: equality of the bit patterns with the restatement; the others: |value - exact| <= 4 envelope scale + 16 ulp(exact)."""
+    mp = _mp()
+    f = FUNCTIONS[name]
+    inputs = np.asarray(inputs, dtype=np.float64)
+    values = np.asarray(values, dtype=np.float64).reshape(len(inputs), f.outputs)
+    envelope = envelopes(name) if envelope is None else envelope
+    labels = branches(name, inputs)
+    want_bits = bits(restated(name, inputs))
+    got_bits = bits(values)
+    exact_rows = exact(name, inputs)
+    bad = []
+    for i, label in enumerate(labels):
+        if is_bitwise(name, label):
+            if not np.array_equal(want_bits[i], got_bits[i]):
+                bad.append(f"{name}{tuple(inputs[i])} [{label}]: {tuple(values[i])} is not the restatement's {tuple(restated(name, inputs[i:i + 1])[0])} bit for bit")
+            continue
+        assert label in envelope, f"{name}: no envelope for the branch {label}"
+        for got, e in zip(values[i], exact_rows[i]):
+            if mp.isinf(e) or not math.isfinite(got):
+                ok, err, room = mp.isinf(e) and got == float(e), math.inf, 0.
+            else:
+                err = abs(mp.mpf(float(got)) - e)
+                scale = 1 if f.absolute else abs(e)
+                room = 4 * mp.mpf(envelope[label]) * scale + 16 * mp.mpf(math.ulp(float(e)))
+                ok = err <= room
+            if not ok:
+                bad.append(f"{name}{tuple(inputs[i])} [{label}]: {float(got)!r} for {mp.nstr(e, 20)}: off by {float(err):.3g}, admissible {float(room):.3g} "
+                           f"(envelope {envelope[label]:.3g})")
+    return bad
+
+
+def norm_deviation(vectors):
+    """| |v| - 1 | of the vectors [n][3], the norm evaluated exactly (floats)"""
+    mp = _mp()
+    return np.array([float(abs(mp.sqrt(sum(mp.mpf(float(c)) ** 2 for c in v)) - 1)) for v in vectors])
+
+
+def dot_deviation(k, vectors, cosines):
+    """|k . v - cos| evaluated exactly (floats)"""
+    mp = _mp()
+    return np.array([float(abs(sum(mp.mpf(float(a)) * mp.mpf(float(b)) for a, b in zip(ki, v)) - mp.mpf(float(c)))) for ki, v, c in zip(k, vectors, cosines)])
+
+
+def grouped_max(labels, values):
+    table = {}
+    for label, v in zip(labels, values):
+        table[label] = max(table.get(label, 0.), float(v))
+    return table
+
+
+def float_bits(x):
+    return struct.unpack("<Q", struct.pack("<d", x))[0]
