@@ -192,6 +192,61 @@ int pmc_tune_wavelength_bins(pmc_ctx* ctx, int32_t instrument, const double* lam
 int pmc_tune_angular_probabilities(pmc_ctx* ctx, int32_t source, const double* k, int64_t n, double* p_out, int32_t* kind_out, double* axis_out,
                                    double* cos_delta_out);
 
+/* ---- Test aid: ONE cycle's walks of slot group 0 for n slots whose state the HOST supplies, through the code a generation of pmc_run_primary runs
+   (the cycle start kernel -- with the peel sort's count pass where the segment plan sorts --, then the walk kernels the plan selects for the context's
+   grid and flavour, on the context's streams, cursors and sort buffers), with the results as the walk kernels leave them, before any transition kernel.
+   Slot i of the call is slot i of the group.  Per slot (every array [n] unless said otherwise):
+     r, k            [n][3] position (finite) and propagation direction (a unit vector to 1e-12)
+     mask            the observer bits of the mode word (bits 8-23: bit 8 + i = a peel-off walk towards instrument i, which must lead an observer
+                     group); the aid adds the alive bit
+     ppW             [num_instruments][n] weight of the peel-off packet (read where the mask names the instrument; <= 0: no contribution)
+     u1, u2          forced scattering: the uniforms of simulateForcedPropagation, in [0, 1) (they travel in sint / nint as the transition kernel
+                     leaves them)
+     depth           no forced scattering: the drawn interaction depth (>= 0, inf allowed; it travels in tausample)
+     hint            -1, or a cell that may hold the position (device numbering of a tree grid: pmc_tune_cell_numbering; no padding slot)
+     nscatt          > 0 (the aid does not start emission cycles)
+     lambda, dust_ext, dust_sca, dust_abs, dust_idx[num_media][n]
+                     a scene with more than one wavelength: the packet's wavelength and the cross sections that travel with it (dust_abs with
+                     explicit absorption, dust_idx with several medium components: each component's wavelength index); NULL otherwise
+     W, rfell        a stored radiation field: the packet's weight and its bin of the field's grid (-1: outside); NULL otherwise.  The walks' contributions
+                     are ADDED to the context's table (through the log where the plan logs them: flushed before the call returns)
+   live_list = 0: the slots run as the group's slot range; 1 (an octree whose plan keeps lists of live slots): as the list of a sparse
+   generation, in the order list[n] gives (a permutation of 0 .. n - 1; NULL: ascending).
+   Out: ptau[num_instruments][n] (written by the walks the mask names; the others keep PMC_WALK_CYCLE_UNSET), sint, nint, mint (device numbering),
+   taupath, tausample [n] (forced scattering: PMC_WALK_CYCLE_UNSET where no second pass ran; sint and nint then still hold u1 and u2); visits, rewalks, paths: what the call added to the counters of pmc_counters (cell_visits, rewalk_visits, paths -- the
+   cycle start kernel counts one path per walk, the walk kernels one per second pass); internal_errors: what it added to the internal-error counter.
+   Everything is checked first: PMC_ERR_INVALID with a message instead of a launch (n against the slots of group 0 -- pmc_set_num_slots sets the pool --,
+   positions, directions, hints, masks, ranges of the other values, arrays the scene needs).  The counters of pmc_counters and pmc_walk_work are put back,
+   and a following pmc_run_primary gives the frames it gives without the call.  No reference counterpart. */
+#define PMC_WALK_CYCLE_UNSET (-1.)
+typedef struct pmc_walk_cycle_in
+{
+    int64_t n;
+    int32_t live_list;
+    const int32_t* list;
+    const double *r, *k;
+    const int32_t* mask;
+    const double* ppW;
+    const double *u1, *u2, *depth;
+    const int32_t *hint, *nscatt;
+    const double *lambda, *dust_ext, *dust_sca, *dust_abs;
+    const int32_t* dust_idx;
+    const double* W;
+    const int32_t* rfell;
+} pmc_walk_cycle_in;
+typedef struct pmc_walk_cycle_out
+{
+    double *ptau, *sint, *nint;
+    int32_t* mint;
+    double *taupath, *tausample;
+    uint64_t visits, rewalks, paths, internal_errors;
+} pmc_walk_cycle_out;
+int pmc_tune_walk_cycle(pmc_ctx* ctx, const pmc_walk_cycle_in* in, pmc_walk_cycle_out* out);
+/* the slots of group 0 under the segment plan of this context as it stands (the largest n of pmc_tune_walk_cycle), whether the plan keeps lists
+   of live slots (live_list = 1 is accepted), the instruments of the scene (rows of ppW and ptau) and its medium components (rows of dust_idx; 1 for
+   a scene with one medium); allocates the slot pool if it is not there yet */
+int pmc_tune_walk_cycle_limits(pmc_ctx* ctx, int64_t* max_slots, int32_t* live_lists, int32_t* num_instruments, int32_t* num_media);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1245,6 +1245,11 @@ namespace
         bool simulateNonForcedPropagation(Packet& pp)
         {
             double tauinteract = -log(rng.uniform());  // Random::expon
+            return propagateToDepth(pp, tauinteract);
+        }
+        // ... from the drawn interaction optical depth on (oracle_walk_result supplies the depth itself)
+        bool propagateToDepth(Packet& pp, double tauinteract)
+        {
             generator->start(pp.r, pp.k);
             counters.paths++;
             const bool explicitAbsorption = sc.options.explicit_absorption != 0;
@@ -1285,7 +1290,10 @@ namespace
                         pp.interactionCell = m;
                         pp.interactionDistance = interpolateLinLin(tauinteract, tau0, tau, s0, s);
                         if (explicitAbsorption)
-                            pp.W *= exp(-interpolateLinLin(tauinteract, tau0, tau, tauAbs0, tauAbs));
+                        {
+                            pp.interactionOpticalDepth = interpolateLinLin(tauinteract, tau0, tau, tauAbs0, tauAbs);
+                            pp.W *= exp(-pp.interactionOpticalDepth);
+                        }
                         else
                             pp.W *= albedoForScattering(pp);
                         double sd = pp.interactionDistance;
@@ -1328,6 +1336,7 @@ namespace
             {
                 // MediumSystem.cpp:1105-1106 and MonteCarloSimulation.cpp:751-766
                 double tauAbs = tauinteract * sc.medium.sigma_abs[ellmix] / sc.medium.sigma_sca[ellmix];
+                pp.interactionOpticalDepth = tauAbs;
                 pp.W *= exp(-tauAbs);
             }
             else
@@ -1793,6 +1802,88 @@ void oracle_census(uint64_t* out, int reset)
         if (out) out[i] = g_census[i].load(std::memory_order_relaxed);
         if (reset) g_census[i].store(0, std::memory_order_relaxed);
     }
+}
+
+// What ONE walk of the life cycle leaves behind, from the life cycle's own path code (no random number is drawn): the packet starts at r
+// with direction k and wavelength lambda; `value` and the results by kind
+//   0  peel-off walk: value = the packet's weight W; out[0] = getExtinctionOpticalDepth (inf: the contribution is dropped)
+//   1  forced propagation: value = the interaction optical depth (as simulateForcedPropagation samples it); setExtinctionOpticalDepths, then
+//      findInteractionPoint: out[0] = tau_path, out[1] = interaction distance, out[2] = absorption optical depth at the point (explicit
+//      absorption), *cell = interaction cell (-1: the path has no segment); tau_path <= 0 leaves out[1], out[2] and *cell as for no segment
+//   2  non-forced propagation: value = the drawn interaction optical depth; out[1], out[2], *cell as above, *cell = -1: the packet escapes
+// *visits: the cells the walk has visited (pmc_counter_values::cell_visits)
+int oracle_walk_result(const pmc_scene* scene, int32_t kind, const double r[3], const double k[3], double lambda, double value, double out[3],
+                       int32_t* cell, uint64_t* visits)
+{
+    struct NoRng : Rng
+    {
+        double uniform() override { std::abort(); }
+    };
+    if (!scene || !r || !k || !out || !cell || !visits || kind < 0 || kind > 2) return PMC_ERR_INVALID;
+    NoRng rng;
+    LifeCycle cycle(*scene, rng, nullptr);
+    Packet pp;
+    pp.r = V3{r[0], r[1], r[2]}, pp.k = V3{k[0], k[1], k[2]};
+    pp.lambda = lambda, pp.W = kind == 0 ? value : 1.;
+    out[0] = out[1] = out[2] = 0.;
+    *cell = -1;
+    if (kind == 0)
+        out[0] = cycle.getExtinctionOpticalDepth(pp, std::numeric_limits<double>::infinity());
+    else if (kind == 1)
+    {
+        cycle.setExtinctionOpticalDepths(pp);
+        out[0] = pp.segments.empty() ? 0. : pp.segments.back().tau;
+        if (out[0] > 0.)
+        {
+            cycle.findInteractionPoint(pp, value);
+            out[1] = pp.interactionDistance, out[2] = pp.interactionOpticalDepth, *cell = pp.interactionCell;
+        }
+    }
+    else if (cycle.propagateToDepth(pp, value))
+        out[1] = pp.interactionDistance, out[2] = pp.interactionOpticalDepth, *cell = pp.interactionCell;
+    *visits = cycle.counters.cell_visits;
+    return PMC_OK;
+}
+
+// What the walks read of medium component h at wavelength lambda: sections[3] = extinction, scattering and absorption cross section (the
+// absorption one 0 where the scene carries no table of it), density[num_cells] (or NULL) the component's number density per cell.
+// *lambda0: the first wavelength of the first source if it is oligochromatic, else 0; *index: the wavelength's index in the component's tables.
+int oracle_walk_medium(const pmc_scene* scene, int32_t h, double lambda, double sections[3], double* density, double* lambda0, int32_t* index)
+{
+    if (!scene || !sections || h < 0 || h >= (scene->num_media > 1 ? scene->num_media : 1)) return PMC_ERR_INVALID;
+    const pmc_medium& M = scene->num_media > 1 ? scene->media[h] : scene->medium;
+    const int ell = locateClip(M.lambda_border, M.num_lambda, lambda);
+    sections[0] = M.sigma_ext[ell], sections[1] = M.sigma_sca[ell], sections[2] = M.sigma_abs ? M.sigma_abs[ell] : 0.;
+    for (int m = 0; density && m < scene->grid.num_cells; ++m) density[m] = M.number_density[m];
+    const pmc_source& src = scene->num_sources > 1 ? scene->sources[0] : scene->source;
+    if (index) *index = ell;
+    if (lambda0) *lambda0 = (src.lambda_mode == PMC_LAMBDA_OLIGO && src.num_oligo > 0) ? src.oligo_lambda[0] : 0.;
+    return PMC_OK;
+}
+
+// What the walks read of the scene's options and observers: info[5] = instruments, medium components, forced scattering, explicit absorption,
+// stored radiation field; *xi = the path length bias; kobs[instruments][3] the observers' directions and leader[instruments] = 1 for an
+// instrument that leads an observer group (its peel-off walk serves the instruments behind it that share its observer).
+int oracle_walk_scene(const pmc_scene* scene, int32_t info[5], double* xi, double* kobs, int32_t* leader)
+{
+    if (!scene || !info || !xi) return PMC_ERR_INVALID;
+    info[0] = scene->num_instruments, info[1] = scene->num_media > 1 ? scene->num_media : 1, info[2] = scene->options.force_scattering;
+    info[3] = scene->options.explicit_absorption, info[4] = scene->radiation_field.store;
+    *xi = scene->options.path_length_bias;
+    for (int i = 0; i < scene->num_instruments; ++i)
+    {
+        for (int a = 0; kobs && a < 3; ++a) kobs[3 * i + a] = scene->instruments[i].kobs[a];
+        if (leader) leader[i] = scene->instruments[i].same_observer_as_preceding ? 0 : 1;
+    }
+    return PMC_OK;
+}
+
+// the bin of wavelength lambda in the grid of the stored radiation field (-1: outside, or no field stored), as storeRadiationField finds it
+int oracle_walk_field_bin(const pmc_scene* scene, double lambda)
+{
+    if (!scene || !scene->radiation_field.store) return -1;
+    const pmc_radiation_field& R = scene->radiation_field;
+    return R.ellv[std::upper_bound(R.border, R.border + R.num_border, lambda) - R.border];
 }
 
 int oracle_trace_ray(const pmc_scene* scene, const double r[3], const double k[3], int32_t* m, double* ds, int32_t cap,

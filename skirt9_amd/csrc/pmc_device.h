@@ -211,6 +211,7 @@ struct TaskArrays
                                             // derives the index of the history each of those slots takes up next
 };
 #define PMC_TASK_NONE 0xFFFFFFFFu
+#define PMC_MODE_ALIVE (1 << 5)  // SlotArrays::mode: the slot holds a live history (the host side sets it only in the test aid pmc_tune_walk_cycle)
 #define PMC_TASK_EXP_MASK 31u   // octree: bits 8-12 of TaskArrays::bits: size exponent of the first cell
 #define PMC_TASK_MOVED 0x2000u  // octree: bit 13 of TaskArrays::bits: PathSegmentGenerator::moveInside has moved the start of the walk (the
                                 // position was outside the grid): position and initial path length are in the record; otherwise the

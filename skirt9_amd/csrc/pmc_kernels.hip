@@ -196,7 +196,7 @@ namespace
 {
     enum Mode : int { MODE_PASS1 = 0, MODE_PASS2 = 1, MODE_PEEL = 2, MODE_NONE = 3 };
     enum Grid : int { GRID_CART = PMC_GRID_CARTESIAN, GRID_TREE = PMC_GRID_OCTREE, GRID_VORO = PMC_GRID_VORONOI, GRID_BIN = PMC_GRID_BINTREE };
-    constexpr int MODE_ALIVE = 1 << 5;
+    constexpr int MODE_ALIVE = PMC_MODE_ALIVE;
     constexpr int MODE_ENDED = 1 << 6;  // the history of the slot has ended: the launch kernel takes up the next one
 
     // ------------------------------------------------------------------------------------------------

@@ -951,9 +951,262 @@ namespace
         }
         return PMC_OK;
     }
+
+    // ---- test aid pmc_tune_walk_cycle (include/pmc_tuning.h): the cycle start and the walks of ONE generation of slot group 0 on slot states the
+    // host supplies.  The plan, the buffers and the enqueue functions are pmc_run_primary's; what is the aid's own is the upload of the slot
+    // state, the download of the walks' results and the bookkeeping around them.
+
+    // what is wrong with the arguments, or an empty string
+    std::string walkCycleProblem(const pmc_ctx* ctx, const pmc_walk_cycle_in& in, const pmc_walk_cycle_out& out, const std::vector<int32_t>& cellExt)
+    {
+        const DevScene& D = ctx->dev;
+        const int64_t n = in.n;
+        if (n < 1) return "at least one slot";
+        if (!in.r || !in.k || !in.mask || !in.ppW || !in.hint || !in.nscatt) return "null array (r, k, mask, ppW, hint, nscatt)";
+        if (!out.ptau || !out.sint || !out.nint || !out.mint || !out.taupath || !out.tausample) return "null result array";
+        if (D.force_scattering ? (!in.u1 || !in.u2) : !in.depth) return D.force_scattering ? "forced scattering needs u1 and u2" : "the scene needs the drawn depth";
+        if (!D.mono && (!in.lambda || !in.dust_ext || !in.dust_sca)) return "a scene with more than one wavelength needs lambda, dust_ext and dust_sca";
+        if (!D.mono && D.explicit_absorption && !in.dust_abs) return "explicit absorption needs dust_abs";
+        if (!D.mono && D.num_media > 1 && !in.dust_idx) return "several medium components need dust_idx";
+        if (D.rf_store && (!in.W || !in.rfell)) return "a stored radiation field needs W and rfell";
+        if (in.live_list != 0 && in.live_list != 1) return "live_list is 0 or 1";
+        const bool numbered = !cellExt.empty();
+        const int64_t cells = numbered ? int64_t(cellExt.size()) : int64_t(D.num_cells);
+        uint32_t leaders = 0;
+        for (int i = 0; i < D.num_instruments; ++i)
+            if (!D.inst[i].same_observer) leaders |= 1u << i;
+        for (int64_t i = 0; i < n; ++i)
+        {
+            const std::string at = " (slot " + std::to_string(i) + ")";
+            double k2 = 0.;
+            for (int a = 0; a < 3; ++a)
+            {
+                if (!std::isfinite(in.r[3 * i + a])) return "a position that is not finite" + at;
+                if (!std::isfinite(in.k[3 * i + a])) return "a direction that is not finite" + at;
+                k2 += in.k[3 * i + a] * in.k[3 * i + a];
+            }
+            if (!(std::fabs(std::sqrt(k2) - 1.) <= 1e-12)) return "a direction that is no unit vector" + at;
+            const uint32_t mask = (uint32_t)in.mask[i];
+            if (mask & ~0x00FFFF00u) return "a mask with bits outside 8-23" + at;
+            if ((mask >> 8) & ~leaders) return "a mask that names an instrument which leads no observer group" + at;
+            for (int q = 0; q < D.num_instruments; ++q)
+                if (((mask >> (8 + q)) & 1u) && std::isnan(in.ppW[int64_t(q) * n + i])) return "a peel-off weight that is not a number" + at;
+            if (in.hint[i] < -1 || in.hint[i] >= cells || (numbered && in.hint[i] >= 0 && cellExt[in.hint[i]] < 0)) return "a hint outside the cell table" + at;
+            if (in.nscatt[i] < 1) return "nscatt must be positive: the aid starts no emission cycle" + at;
+            if (D.force_scattering)
+            {
+                if (!(in.u1[i] >= 0. && in.u1[i] < 1.) || !(in.u2[i] >= 0. && in.u2[i] < 1.)) return "a uniform outside [0, 1)" + at;
+            }
+            else if (!(in.depth[i] >= 0.))
+                return "a drawn depth that is negative or not a number" + at;
+            if (!D.mono)
+            {
+                if (!(in.lambda[i] > 0.) || !std::isfinite(in.lambda[i])) return "a wavelength that is not positive and finite" + at;
+                if (!(in.dust_ext[i] >= 0.) || !std::isfinite(in.dust_ext[i]) || !(in.dust_sca[i] >= 0.) || !std::isfinite(in.dust_sca[i]))
+                    return "a cross section that is negative or not finite" + at;
+                if (D.explicit_absorption && (!(in.dust_abs[i] >= 0.) || !std::isfinite(in.dust_abs[i]))) return "an absorption cross section that is negative or not finite" + at;
+                for (int h = 0; D.num_media > 1 && h < D.num_media; ++h)
+                    if (in.dust_idx[int64_t(h) * n + i] < 0 || in.dust_idx[int64_t(h) * n + i] >= D.med[h].num_lambda) return "a wavelength index outside a component's tables" + at;
+            }
+            if (D.rf_store)
+            {
+                if (!std::isfinite(in.W[i])) return "a weight that is not finite" + at;
+                if (in.rfell[i] < -1 || in.rfell[i] >= D.rf_num_lambda) return "a bin outside the radiation field's grid" + at;
+            }
+        }
+        if (in.live_list && in.list)
+        {
+            std::vector<char> seen(size_t(n), 0);
+            for (int64_t i = 0; i < n; ++i)
+            {
+                if (in.list[i] < 0 || in.list[i] >= n || seen[in.list[i]]) return "the list is no permutation of the slots";
+                seen[in.list[i]] = 1;
+            }
+        }
+        return "";
+    }
+
+    // the plan of a segment over the whole pool, as pmc_run_primary makes it, with its buffers
+    int planWalkCycle(pmc_ctx* ctx, SegmentPlan& P)
+    {
+        int numSlots = 0;
+        if (int rc = provisionSlots(ctx, uint64_t(std::max<int64_t>(ctx->numSlots, 1)), &numSlots)) return rc;
+        P = planSegment(ctx, numSlots, 0, uint64_t(numSlots), 0);
+        if (int rc = provisionSortBuffers(ctx, P)) return rc;
+        return provisionLogs(ctx, P);
+    }
+
+    template<typename T> hipError_t putSlots(hipError_t e, T* device, int base, const T* host, size_t count, hipStream_t stream)
+    {
+        if (e == hipSuccess && host && device) e = hipMemcpyAsync(device + base, host, sizeof(T) * count, hipMemcpyHostToDevice, stream);
+        return e;
+    }
+    template<typename T> hipError_t getSlots(hipError_t e, T* host, const T* device, int base, size_t count, hipStream_t stream)
+    {
+        if (e == hipSuccess) e = hipMemcpyAsync(host, device + base, sizeof(T) * count, hipMemcpyDeviceToHost, stream);
+        return e;
+    }
+
+    // the segment's start, the slot states, the generation, the results; after[32]: the counters behind the walks.  Any failure returns at
+    // once: runWalkCycle abandons what is in flight
+    int enqueueWalkCycle(pmc_ctx* ctx, const SegmentPlan& P, const pmc_walk_cycle_in& in, pmc_walk_cycle_out& out, unsigned long long* after)
+    {
+        DevScene& D = ctx->dev;
+        const SlotArrays& A = D.slots;
+        const TaskArrays& K = D.tasks;
+        const int g = 0, base = P.base[g], size = P.size[g];
+        const size_t n = size_t(in.n);
+        const int64_t NS = A.num_slots;
+        hipStream_t sg = ctx->groupStream[g];
+        unsigned long long* ctr = D.counters;
+        if (int rc = startSegment(ctx, P)) return rc;
+        // ---- the group as the transition and launch kernels leave it when nothing is left to launch: no slot alive, no task record in use ...
+        HIP_TRY(hipMemsetAsync(A.mode + base, 0, sizeof(int32_t) * size_t(size), sg));
+        for (int r = 0; r <= D.num_instruments; ++r)
+            HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(K.bits + int64_t(r) * NS + base), (int)PMC_TASK_NONE, size_t(size), sg));
+        // ---- ... but for the first n slots, which hold what the host supplies: the state at the start of a cycle (announceCycle, onCycleDone)
+        std::vector<double> soa[6];
+        for (int a = 0; a < 3; ++a)
+        {
+            soa[a].resize(n), soa[3 + a].resize(n);
+            for (size_t i = 0; i < n; ++i) soa[a][i] = in.r[3 * i + a], soa[3 + a][i] = in.k[3 * i + a];
+        }
+        std::vector<int32_t> mode(n);
+        for (size_t i = 0; i < n; ++i) mode[i] = PMC_MODE_ALIVE | in.mask[i];
+        const std::vector<double> unset(n, PMC_WALK_CYCLE_UNSET), zeros(n, 0.);
+        std::vector<uint64_t> history(n);
+        for (size_t i = 0; i < n; ++i) history[i] = i;
+        const std::vector<uint32_t> noBlock(n, 0u);
+        hipError_t e = hipSuccess;
+        double* const pos[6] = {A.rx, A.ry, A.rz, A.kx, A.ky, A.kz};
+        for (int a = 0; a < 6; ++a) e = putSlots(e, pos[a], base, soa[a].data(), n, sg);
+        e = putSlots(e, A.mode, base, mode.data(), n, sg);
+        e = putSlots(e, A.nscatt, base, in.nscatt, n, sg);
+        e = putSlots(e, A.mint, base, in.hint, n, sg);
+        for (int q = 0; q < D.num_instruments; ++q)
+        {
+            e = putSlots(e, A.ppW + int64_t(q) * NS, base, in.ppW + size_t(q) * n, n, sg);
+            e = putSlots(e, A.ptau + int64_t(q) * NS, base, unset.data(), n, sg);
+        }
+        e = putSlots(e, A.sint, base, D.force_scattering ? in.u1 : unset.data(), n, sg);
+        e = putSlots(e, A.nint, base, D.force_scattering ? in.u2 : unset.data(), n, sg);
+        e = putSlots(e, A.tausample, base, D.force_scattering ? unset.data() : in.depth, n, sg);
+        e = putSlots(e, A.taupath, base, unset.data(), n, sg);
+        // (the random stream of a slot: read only by a rejection round of the exponential branch, which rounding alone can cause)
+        e = putSlots(e, A.history, base, history.data(), n, sg);
+        e = putSlots(e, A.rngBlock, base, noBlock.data(), n, sg);
+        e = putSlots(e, A.rngSpare, base, zeros.data(), n, sg);
+        if (!D.mono)
+        {
+            e = putSlots(e, A.lambda, base, in.lambda, n, sg);
+            e = putSlots(e, A.dustExt, base, in.dust_ext, n, sg);
+            e = putSlots(e, A.dustSca, base, in.dust_sca, n, sg);
+            e = putSlots(e, A.dustAbs, base, in.dust_abs, n, sg);
+            for (int h = 0; A.dustIdx && h < D.num_media; ++h) e = putSlots(e, A.dustIdx + int64_t(h) * NS, base, in.dust_idx + size_t(h) * n, n, sg);
+        }
+        if (D.rf_store)
+        {
+            e = putSlots(e, A.W, base, in.W, n, sg);
+            e = putSlots(e, A.rfell, base, in.rfell, n, sg);
+        }
+        // the list of a sparse generation, as the cycle start kernel of the generation before it would have left it in one half of liveList
+        SegmentRun S{};
+        std::vector<int32_t> list(n);
+        int* listIn = nullptr;
+        if (in.live_list)
+        {
+            for (size_t i = 0; i < n; ++i) list[i] = base + (in.list ? in.list[i] : int32_t(i));
+            listIn = K.liveList + int64_t(S.listHalf[g]) * NS + base;
+            e = putSlots(e, K.liveList + int64_t(S.listHalf[g]) * NS, base, list.data(), n, sg);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(sg);  // (the host buffers above live on this frame)
+        if (e != hipSuccess) return hipFail(e, "pmc_tune_walk_cycle: upload");
+        // ---- the generation, as enqueueGeneration orders it: cursors, cycle start (a group most of whose slots are live: no list is built unless
+        // the generation runs over one), walks
+        ctx->readback[g].live = (unsigned long long)size;
+        HIP_TRY(hipMemsetAsync(ctr + PMC_CTR_TASK(g, 0), 0, PMC_CTR_TASKS_PER_GROUP * sizeof(unsigned long long), sg));
+        if (ctx->xcdCursors) HIP_TRY(hipMemsetAsync(cursorSet(ctx, g, 0), 0, (PMC_SORT_OBS + 1) * 8 * sizeof(unsigned long long), sg));
+        if (int rc = enqueueCycleStart(ctx, P, S, g, false, listIn, listIn ? int(n) : 0)) return rc;
+        HIP_TRY(hipEventRecord(ctx->evA[g], sg));
+        if (int rc = P.octree ? enqueueOctreeWalks(ctx, P, S, g, listIn, listIn ? int(n) : 0) : enqueueGenericWalks(ctx, P, S, g)) return rc;
+        // (the radiation-field log of the generation: its size, then the flush of the generation after it)
+        unsigned long long rfFill = 0;
+        if (P.rfLogged)
+        {
+            HIP_TRY(hipMemcpyAsync(&rfFill, ctr + PMC_CTR_RFLOG(g), sizeof(rfFill), hipMemcpyDeviceToHost, sg));
+            HIP_TRY(hipStreamSynchronize(sg));
+            if (int rc = rfFlush(ctx, P, g, rfFill)) return rc;
+        }
+        // ---- the results as the walk kernels leave them
+        for (int q = 0; q < D.num_instruments; ++q) e = getSlots(e, out.ptau + size_t(q) * n, A.ptau + int64_t(q) * NS, base, n, sg);
+        e = getSlots(e, out.sint, A.sint, base, n, sg);
+        e = getSlots(e, out.nint, A.nint, base, n, sg);
+        e = getSlots(e, out.mint, A.mint, base, n, sg);
+        e = getSlots(e, out.taupath, A.taupath, base, n, sg);
+        e = getSlots(e, out.tausample, A.tausample, base, n, sg);
+        // (no slot stays alive, no record in use: nothing of the call is left for a kernel to find)
+        if (e == hipSuccess) e = hipMemsetAsync(A.mode + base, 0, sizeof(int32_t) * size_t(size), sg);
+        const hipError_t done = hipDeviceSynchronize();
+        if (e == hipSuccess) e = done;
+        if (e == hipSuccess) e = hipMemcpy(after, ctr, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hipFail(e, "pmc_tune_walk_cycle");
+        return PMC_OK;
+    }
+
+    int runWalkCycle(pmc_ctx* ctx, const SegmentPlan& P, const pmc_walk_cycle_in& in, pmc_walk_cycle_out& out)
+    {
+        // (the counters of pmc_counters and pmc_walk_work as they stand: put back at the end, whichever way the call ends)
+        unsigned long long before[32], after[32];
+        unsigned long long* ctr = ctx->dev.counters;
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(before, ctr, sizeof(before), hipMemcpyDeviceToHost));
+        int rc = enqueueWalkCycle(ctx, P, in, out, after);
+        // (a failure: nothing of the call may still be running when it returns, as in pmc_run_primary)
+        if (rc) abandon(ctx, rc);
+        ctx->timed = false;
+        const hipError_t e = hipMemcpy(ctr, before, sizeof(before), hipMemcpyHostToDevice);
+        if (rc) return rc;
+        if (e != hipSuccess) return hipFail(e, "pmc_tune_walk_cycle");
+        out.paths = after[1] - before[1], out.visits = after[2] - before[2], out.rewalks = after[6] - before[6], out.internal_errors = after[7] - before[7];
+        return PMC_OK;
+    }
 }
 
 extern "C" {
+
+int pmc_tune_walk_cycle_limits(pmc_ctx* ctx, int64_t* max_slots, int32_t* live_lists, int32_t* num_instruments, int32_t* num_media)
+{
+    if (!ctx || !max_slots || !live_lists || !num_instruments || !num_media) return fail(PMC_ERR_INVALID, "pmc_tune_walk_cycle_limits: invalid argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    SegmentPlan P;
+    if (int rc = planWalkCycle(ctx, P)) return rc;
+    *max_slots = P.size[0];
+    *live_lists = P.sparseLists ? 1 : 0;
+    *num_instruments = ctx->dev.num_instruments;
+    *num_media = std::max(1, ctx->dev.num_media);
+    return PMC_OK;
+}
+
+int pmc_tune_walk_cycle(pmc_ctx* ctx, const pmc_walk_cycle_in* in, pmc_walk_cycle_out* out)
+{
+    if (!ctx || !in || !out) return fail(PMC_ERR_INVALID, "pmc_tune_walk_cycle: invalid argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // (a tree grid: hints count cells in the device numbering, which has padding slots that hold no cell)
+    std::vector<int32_t> cellExt;
+    if (ctx->dev.cell_ext && ctx->dev.cell_slots > 0)
+    {
+        cellExt.resize(size_t(ctx->dev.cell_slots));
+        HIP_TRY(hipMemcpy(cellExt.data(), ctx->dev.cell_ext, sizeof(int32_t) * cellExt.size(), hipMemcpyDeviceToHost));
+    }
+    const std::string problem = walkCycleProblem(ctx, *in, *out, cellExt);
+    if (!problem.empty()) return fail(PMC_ERR_INVALID, "pmc_tune_walk_cycle: " + problem);
+    SegmentPlan P;
+    if (int rc = planWalkCycle(ctx, P)) return rc;
+    if (in->n > P.size[0])
+        return fail(PMC_ERR_INVALID, "pmc_tune_walk_cycle: " + std::to_string(in->n) + " slots, slot group 0 has " + std::to_string(P.size[0]));
+    if (in->live_list && !P.sparseLists) return fail(PMC_ERR_INVALID, "pmc_tune_walk_cycle: the segment plan of this context keeps no lists of live slots");
+    return runWalkCycle(ctx, P, *in, *out);
+}
 
 int pmc_launch_flavour(pmc_ctx* ctx, int32_t* flavour)
 {

@@ -26,7 +26,7 @@ SYMBOLS = ["pmc_abi_version", "pmc_build_info", "pmc_last_error", "pmc_frame_lay
            "pmc_debug_tables", "pmc_tuning_set", "pmc_tuning_clear", "pmc_tune_dipole_cosines", "pmc_tune_source_velocities",
            "pmc_launch_flavour", "pmc_tune_log_geometry", "pmc_tune_log_partition", "pmc_tune_rf_log_flush", "pmc_tune_stat_log_flush",
            "pmc_tune_cell_numbering", "pmc_tune_device_function", "pmc_tune_device_function_widths", "pmc_tune_locate", "pmc_tune_instrument",
-           "pmc_tune_detector", "pmc_tune_wavelength_bins", "pmc_tune_angular_probabilities"]
+           "pmc_tune_detector", "pmc_tune_wavelength_bins", "pmc_tune_angular_probabilities", "pmc_tune_walk_cycle", "pmc_tune_walk_cycle_limits"]
 
 # the scene-free device functions of pmc_tune_device_function (include/pmc_tuning.h PMC_FN_*)
 DEVICE_FUNCTIONS = {"hg_value": 0, "hg_cone_mean": 1, "phase_value": 2, "hg_cosine": 3, "dipole_value": 4, "random_direction": 5, "direction_about": 6,
@@ -59,6 +59,19 @@ class LogGeometry(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("cell_slots", "rf_num_lambda", "rf_keys", "rf_parts", "rf_logged", "stat_records", "stat_parts", "stat_logged",
                                          "chunk", "rf_bucket_bits", "stat_bucket_bits", "scan_threads", "sort_block", "max_parts", "reduce_span",
                                          "rf_short_run", "stat_short_run", "max_entries")]
+
+
+class WalkCycleIn(C.Structure):
+    """pmc_walk_cycle_in (include/pmc_tuning.h)"""
+    _fields_ = ([("n", C.c_int64), ("live_list", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("list", "r", "k", "mask", "ppW", "u1", "u2", "depth", "hint", "nscatt", "wavelength", "dust_ext", "dust_sca",
+                                             "dust_abs", "dust_idx", "W", "rfell")])
+
+
+class WalkCycleOut(C.Structure):
+    """pmc_walk_cycle_out (include/pmc_tuning.h)"""
+    _fields_ = ([(n, C.c_void_p) for n in ("ptau", "sint", "nint", "mint", "taupath", "tausample")]
+                + [(n, C.c_uint64) for n in ("visits", "rewalks", "paths", "internal_errors")])
 
 
 def lib():
@@ -146,6 +159,9 @@ def lib():
             L.pmc_tune_wavelength_bins.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
             L.pmc_tune_angular_probabilities.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
                                                          C.POINTER(C.c_double)]
+        if hasattr(L, "pmc_tune_walk_cycle"):  # (likewise)
+            L.pmc_tune_walk_cycle.argtypes = [C.c_void_p, C.POINTER(WalkCycleIn), C.POINTER(WalkCycleOut)]
+            L.pmc_tune_walk_cycle_limits.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         _lib = L
     return _lib
 
@@ -510,6 +526,53 @@ class Engine:
         kind, cos_delta = C.c_int32(0), C.c_double(0.)
         _check(lib().pmc_tune_angular_probabilities(self._h, int(source), _ptr(k), k.shape[0], _ptr(p), C.byref(kind), _ptr(axis), C.byref(cos_delta)))
         return p, kind.value, axis, cos_delta.value
+
+    def walk_cycle_limits(self):
+        """test aid (pmc_tune_walk_cycle_limits): (slots of group 0 -- the largest n of ``walk_cycle`` --, whether ``live_list`` is accepted,
+        instruments of the scene, its medium components)"""
+        n, lists, instruments, media = C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _check(lib().pmc_tune_walk_cycle_limits(self._h, C.byref(n), C.byref(lists), C.byref(instruments), C.byref(media)))
+        return int(n.value), bool(lists.value), int(instruments.value), int(media.value)
+
+    def walk_cycle(self, r, k, mask, ppW, u1=None, u2=None, depth=None, hint=None, nscatt=None, live_list=False, order=None, wavelength=None,
+                   dust_ext=None, dust_sca=None, dust_abs=None, dust_idx=None, W=None, rfell=None, n=None):
+        """test aid (pmc_tune_walk_cycle): one cycle's walks of slot group 0 on the slot states given here, through the cycle start kernel and the
+        walk kernels a generation of ``run_primary`` runs.  r, k: [n][3]; mask: [n] observer bits of the mode word (1 << (8 + instrument)); ppW:
+        [num_instruments][n]; u1, u2 (forced scattering) or depth (not forced); hint: -1 or a cell of the device numbering (default -1); nscatt
+        (default 1); live_list: the slots run as the list of a sparse generation, in the order `order` gives; the other arrays as the scene needs
+        them (include/pmc_tuning.h).  n: the slot count, where it is not len(r).  Returns a dict: ptau [num_instruments][n], sint, nint, mint
+        (device numbering), taupath, tausample, and the ints visits, rewalks, paths, internal_errors"""
+        def arr(a, dtype, shape=None):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            return a if shape is None else a.reshape(shape)
+        r, k = arr(r, np.float64, (-1, 3)), arr(k, np.float64, (-1, 3))
+        count = (0 if r is None else r.shape[0]) if n is None else int(n)
+        room = max(count, 1)
+        _, _, num_inst, num_media = self.walk_cycle_limits()
+        ppW = arr(ppW, np.float64, (num_inst, -1))
+        keep = {"r": r, "k": k, "mask": arr(mask, np.int32), "ppW": ppW, "u1": arr(u1, np.float64), "u2": arr(u2, np.float64),
+                "depth": arr(depth, np.float64), "hint": np.full(room, -1, dtype=np.int32) if hint is None else arr(hint, np.int32),
+                "nscatt": np.ones(room, dtype=np.int32) if nscatt is None else arr(nscatt, np.int32), "list": arr(order, np.int32),
+                "wavelength": arr(wavelength, np.float64), "dust_ext": arr(dust_ext, np.float64), "dust_sca": arr(dust_sca, np.float64),
+                "dust_abs": arr(dust_abs, np.float64), "dust_idx": arr(dust_idx, np.int32), "W": arr(W, np.float64), "rfell": arr(rfell, np.int32)}
+        for name, value in keep.items():  # (the library reads n elements of every array it is given: a shorter one is refused here)
+            per = {"r": 3, "k": 3, "ppW": num_inst, "dust_idx": num_media}.get(name, 1)
+            if value is not None and value.size < per * count:
+                raise ValueError(f"{name} has {value.size} elements, {count} slots need {per * count}")
+        a = WalkCycleIn(n=count, live_list=1 if live_list else 0)
+        for name, value in keep.items():
+            setattr(a, name, None if value is None else value.ctypes.data)
+        res = {"ptau": np.empty((num_inst, room)), "sint": np.empty(room), "nint": np.empty(room), "mint": np.empty(room, dtype=np.int32),
+               "taupath": np.empty(room), "tausample": np.empty(room)}
+        o = WalkCycleOut()
+        for name, value in res.items():
+            setattr(o, name, value.ctypes.data)
+        _check(lib().pmc_tune_walk_cycle(self._h, C.byref(a), C.byref(o)))
+        res = {name: value[..., :count] for name, value in res.items()}
+        res.update(visits=int(o.visits), rewalks=int(o.rewalks), paths=int(o.paths), internal_errors=int(o.internal_errors))
+        return res
 
     def trace_ray(self, r, k, cap=4096):
         r = np.ascontiguousarray(r, dtype=np.float64)

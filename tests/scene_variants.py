@@ -41,3 +41,15 @@ def with_pixels(tmp_path, base, instrument, pixels):
     path = tmp_path / f"{base}_{instrument}_{pixels}.ski"
     path.write_text("\n".join(lines))
     return str(path)
+
+
+def with_optical_depth(tmp_path, base, depth):
+    """tests/ski/<base>.ski with the optical depth of its (one) OpticalDepthMaterialNormalization set to `depth`: the same grid and density
+    distribution, every density scaled"""
+    import re
+    text = open(ski(base + ".ski")).read()
+    assert len(re.findall(r'<OpticalDepthMaterialNormalization [^>]*opticalDepth="[^"]*"', text)) == 1
+    text = re.sub(r'(<OpticalDepthMaterialNormalization [^>]*opticalDepth=")[^"]*"', lambda m: f'{m.group(1)}{depth}"', text)
+    path = tmp_path / f"{base}_tau{depth}.ski"
+    path.write_text(text)
+    return str(path)
