@@ -68,7 +68,7 @@ int pmc_tune_dipole_cosines(pmc_ctx* ctx, const double* u, int64_t n, double* co
    source at rest gives zeros. */
 int pmc_tune_source_velocities(pmc_ctx* ctx, int32_t source, const double* r, int64_t n, double* v_out);
 
-/* ---- Test aids: the counting sort and the reduce kernels behind the radiation-field log and the statistics log (skirt9_amd/csrc/pmc_walk_tree.inc:
+/* ---- Test aids: the counting sort and the reduce kernels behind the radiation-field log and the statistics log (skirt9_amd/csrc/pmc_log.inc:
    rfHistKernel, rfScanKernel, rfScatterKernel, rfReduceKernel, statReduceKernel), run on logs that the HOST supplies instead of the walk and launch
    kernels.  A log is n (key, value) pairs in whole chunks of `chunk` entries: n > 0, a multiple of `chunk`, at most `max_entries`.  Every aid checks
    its arguments and returns PMC_ERR_INVALID with a message instead of launching; it allocates the device buffers it needs and frees them, works on

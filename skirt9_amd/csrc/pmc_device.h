@@ -478,7 +478,7 @@ struct RfLogArgs
 // (its place in its open chunk is saved when the kernel ends, by wave index, and taken up again by the next launch: a claim per
 // entry, or per wave and call, is a same-address atomic -- measured: the launch kernel twice as slow); chunkFill[chunk] tells the
 // flush how many entries of a chunk are there.  The log is partitioned by key range (the counting sort of the radiation-field log,
-// pmc_walk_tree.inc) and summed per bin in LDS (statReduceKernel) at the end of the segment, or when it is half full: 28 bytes of
+// pmc_log.inc) and summed per bin in LDS (statReduceKernel) at the end of the segment, or when it is half full: 28 bytes of
 // streaming traffic per entry instead of a sector atomic, and no kernel more in the chain of a generation (every small kernel there
 // waits for a free CU next to the other groups' walk kernels: flushed every few generations the log was SLOWER than the atomics).
 struct StatLogArgs

@@ -270,6 +270,7 @@ namespace
 #include "pmc_walk.inc"
 #include "pmc_walk_voro_run.inc"
 #include "pmc_walk_tree.inc"
+#include "pmc_log.inc"
 #include "pmc_transition.inc"
 #include "pmc_ray.inc"
 }

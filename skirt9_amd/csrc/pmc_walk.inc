@@ -598,6 +598,36 @@
         return tau;
     }
 
+    // The pass-1 checkpoints of the propagation kernels (walkPropKernel, pmc_walk_tree.inc, with the derivation; voroPropKernel,
+    // pmc_walk_voro_run.inc): the decisions.  A kernel keeps two saved walker states of its own layout, A (certainly at or before the
+    // interaction point) and B (a later candidate), and one word of flags: CK_SEL the buffer that holds B (A is in the other one),
+    // CK_HASA / CK_HASB, CK_LIN the branch of sampleForcedDepth that the path's uniforms take (the sampled depth is u2 * tau_path).
+    constexpr uint32_t CK_SEL = 1u, CK_HASA = 2u, CK_HASB = 4u, CK_LIN = 8u;
+    // the flags of a new path: no checkpoint yet
+    __device__ __forceinline__ uint32_t ckptStart(const DevScene& S, double u1) { return (S.path_length_bias != 0. && u1 < S.path_length_bias) ? CK_LIN : 0u; }
+    // the tick of a pass-1 walk at depth tau > 0: true if the caller is to save its current state, as the new B, in buffer ck & CK_SEL (after the call).
+    // Without a B that is the first one; with one, B is certain once the lower bound of the sampled depth has passed its depth tauB, and becomes A.
+    __device__ __forceinline__ bool ckptTick(uint32_t& ck, double tau, double tauB, double u2)
+    {
+        if (ck & CK_HASB)
+        {
+            const double bound = u2 * tau;
+            const double need = (ck & CK_LIN) ? tauB : tauB * (1. + tau) * (1. + 1e-13);
+            if (!(bound >= need)) return false;
+            ck = (ck ^ CK_SEL) | CK_HASA;
+        }
+        ck |= CK_HASB;
+        return true;
+    }
+    // the buffer pass 2 resumes from once the depth `target` has been sampled: the later state that lies at or before the interaction point
+    // (B is a candidate; A is certain but for a sampled depth that a rejection round has redrawn: checked as well), or -1: from the start
+    __device__ __forceinline__ int ckptResume(uint32_t ck, double tauA, double tauB, double target)
+    {
+        if ((ck & CK_HASB) && tauB <= target) return (int)(ck & CK_SEL);
+        if ((ck & CK_HASA) && tauA <= target) return (int)((ck & CK_SEL) ^ 1u);
+        return -1;
+    }
+
     // SpecialFunctions::lnmean(x1, x2, lnx1, lnx2) (SKIRT/utils/SpecialFunctions.cpp:860-880)
     __device__ __forceinline__ double lnmean(double x1, double x2, double lnx1, double lnx2)
     {

@@ -1,13 +1,20 @@
 // pmc_walk_tree.inc -- the octree walk (included by pmc_kernels.hip after pmc_walk.inc, inside its anonymous namespace):
-// the fast step and the two walk kernels of a generation.
+// the fast step, the pieces the kernels share (frame, step head and tail, undecided steps, epilogues, checkpoint packing,
+// radiation-field log append) and the three walk kernels.
 //
 //   walkPeelKernel   all peel-off walks towards ONE observer (MediumSystem::getExtinctionOpticalDepth,
 //                    MediumSystem.cpp:1192-1260).  Every walk of the launch has the same direction k_obs, so the
 //                    direction, RN(1/k), the sign bits and everything derived from them are wave-uniform: they live in
 //                    SGPRs, the wall selection is scalar, and a lane keeps only position, optical depth and cell.
+//                    This form serves scenes with several media, and octrees whose LDS has no room for the task queues.
+//   walkPeelKernel2  the same walks for every other scene: one instantiation per sign octant of k_obs, and a lane takes
+//                    up its next walk by itself from a queue of task records that its wave keeps in LDS.
 //   walkPropKernel   the propagation walk of every slot (MediumSystem::setExtinctionOpticalDepths, :849-901, and the
 //                    interaction point, SpatialGridPath.cpp:164-206): pass 1 over the whole path, the sampled optical
 //                    depth between the passes (MonteCarloSimulation.cpp:696-722), pass 2 up to it; per-lane directions.
+//
+// Not here: the checkpoint decisions of pass 1 (pmc_walk.inc: ckptStart, ckptTick, ckptResume, shared with voroPropKernel) and the
+// kernels that sort and sum the logs behind the walks (pmc_log.inc).
 //
 // The step is software-pipelined around its ONE memory round trip: the hot record of a cell (CellRec: density + six
 // links, 32 bytes) is requested as soon as the cell is known -- when the link through the exit wall of the previous
@@ -313,6 +320,122 @@
         C.numCells = (uint32_t)S.cell_slots;
     }
 
+    // ---- what the three kernels share: the frame, the step, the undecided steps of a service round, the epilogues
+    // the frame of a kernel: the coordinate table staged in LDS (all lanes of the workgroup: a barrier), the constants of the step
+    template<bool WIDE> __device__ __forceinline__ GridLds treeFrame(const DevScene& S, double* lds, TreeConst& C)
+    {
+        requireLdsBaseZero(lds);
+        stageGrid<GRID_TREE>(S, lds, threadIdx.x, blockDim.x);
+        __syncthreads();
+        GridLds L = makeGridLds(S, lds);
+        if (!WIDE) L.gtab = nullptr;  // (octrees up to level 10 always have their table in LDS: the test folds away)
+        loadTreeConst(S, C);
+        return L;
+    }
+    // a lane without a walk
+    template<bool WIDE> __device__ __forceinline__ void idleWalk(TWalk<WIDE>& w, CellLoad& g)
+    {
+        w.cell = 0, w.axis = 0, w.szb = 8u, w.bx = w.by = w.bz = 0u;
+        w.ds = 0., w.tau = 0., w.s = 0., w.dens = 0., w.lastm = -1;
+        w.rx = w.ry = w.rz = 0.;
+        g.a = make_uint4(0, 0, 0, 0), g.b = make_uint4(0, 0, 0, 0);
+    }
+    // the direction towards an observer: wave-uniform (scalar loads from the scene)
+    __device__ __forceinline__ void observerDir(const DevInstrument& I, Dir& d)
+    {
+        d.kx = I.kx, d.ky = I.ky, d.kz = I.kz;
+        d.ikx = I.ikx, d.iky = I.iky, d.ikz = I.ikz;
+        d.sgn = I.sgn;
+        setDirMasks(d);
+    }
+
+    // The step, head: the position after the pending segment, r + k (ds + eps) (TreeSpatialGrid.cpp:186-191), which needs no memory; then, from the
+    // record of the current cell, the density (w.dens) and the link through the exit wall (returned by value: with reference parameters walkPeelKernel
+    // spills).  Between head and tail a kernel adds the pending segment to its sums and decides whether the walk stops.  (walkPeelKernel2: see there.)
+    struct StepHead { double nrx, nry, nrz; uint32_t link; };
+    template<bool WIDE, int SGN>
+    __device__ __forceinline__ StepHead treeStepHead(const Dir& d, double eps, TWalk<WIDE>& w, const CellLoad& g PMC_WPROF_ARG)
+    {
+        const double step = w.ds + eps;
+        StepHead h;
+        h.nrx = w.rx + d.kx * step, h.nry = w.ry + d.ky * step, h.nrz = w.rz + d.kz * step;
+        h.link = cellLink<SGN>(g, d, w.axis);
+        w.dens = cellDensity(g);
+        PMC_WSTAMP(0);
+        return h;
+    }
+    // The step, tail: the walk moves to (nrx, nry, nrz) and enters the leaf behind the exit wall; that leaf's record is requested BEFORE
+    // the arithmetic that enters it.  Returns the new state: ST_ACTIVE (w is in the new cell, g its record in flight), or ST_EDGE / ST_SLOW
+    // (the next service round decides: treeServeUndecided).
+    template<bool WIDE, int SGN>
+    __device__ __forceinline__ int treeAdvance(const TreeConst& C, const char* nodes, const Dir& d, TWalk<WIDE>& w, CellLoad& g, uint32_t link,
+                                               double nrx, double nry, double nrz PMC_WPROF_ARG)
+    {
+        w.rx = nrx, w.ry = nry, w.rz = nrz;
+        uint32_t cell2;
+        int st = treeResolve<WIDE, SGN>(C, nodes, d, w, link, nrx, nry, nrz, cell2 PMC_WPROF_PASS);
+        PMC_WSTAMP(1);
+        if (st == ST_ACTIVE)
+        {
+            cellIssue(C, cell2, g);
+            st = treeEnterBox<WIDE, SGN>(C, d, w PMC_WPROF_PASS);
+            if (st == ST_ACTIVE) w.cell = cell2;
+            PMC_WSTAMP(4);
+        }
+        return st;
+    }
+    // The undecided steps of a service round (rare): the literal algorithm.  Returns true if the lane takes up a cell whose record has
+    // not been requested yet.  (Profiling builds count here: edge, literal steps, and the walks that have ended.)
+    template<bool WIDE>
+    __device__ __forceinline__ bool treeServeUndecided(const DevScene& S, const GridLds& L, const TreeConst& C, const Dir& d, TWalk<WIDE>& w, int& st PMC_WPROF_ARG)
+    {
+        bool fresh = false;
+        PMC_CENSUS(2, st == ST_EDGE);
+        if (st == ST_EDGE) st = treeEdgeStateAt(C, w.rx, w.ry, w.rz);
+        PMC_CENSUS(0, st == ST_SLOW);
+        if (st == ST_SLOW)
+        {
+            st = treeSlowStep<WIDE>(S, L, d, w) ? ST_ACTIVE : ST_EXIT;
+            fresh = st == ST_ACTIVE;
+        }
+        PMC_CENSUS(6, st == ST_HIT);
+        PMC_CENSUS(7, st == ST_EXIT);
+        return fresh;
+    }
+    // a finished peel-off walk: tau >= taumax (MediumSystem.cpp:1215-1218) or the optical depth of the whole path
+    __device__ __forceinline__ void peelStoreResult(double* ptau, int slot, double tau, int& st)
+    {
+        if (st == ST_HIT || st == ST_EXIT)
+        {
+            ptau[slot] = st == ST_HIT ? INFINITY : tau;
+            st = ST_IDLE;
+        }
+    }
+    // the work counters of a wave of a peel-off kernel
+    __device__ __forceinline__ void flushPeelWork(const DevScene& S, int lane, unsigned long long visits, unsigned long long waveSteps, unsigned long long services)
+    {
+        if (lane == 0 && visits)
+        {
+            atomicAdd(S.counters + 2, visits);
+            atomicAdd(S.counters + PMC_CTR_WALKWORK + 0, waveSteps);
+            atomicAdd(S.counters + PMC_CTR_WALKWORK + 1, visits);
+            atomicAdd(S.counters + PMC_CTR_WALKWORK + 2, services);
+        }
+    }
+#ifdef PMC_PROFILE
+    // the cycle stamps of a wave go to the eight counters from `base`, its census to those from base + 16 (208 / 224: peel-off, 216 / 232: propagation)
+    __device__ __forceinline__ void flushWalkProf(const DevScene& S, int lane, const WalkProf& prof, int base, bool stamps)
+    {
+        if (stamps && lane == 0)
+            for (int i = 0; i < 8; ++i) atomicAdd(S.counters + base + i, (unsigned long long)prof.t[i]);
+        for (int i = 0; i < 8; ++i)
+        {
+            const unsigned long long c = waveSum(prof.census[i]);
+            if (lane == 0 && c) atomicAdd(S.counters + base + 16 + i, c);
+        }
+    }
+#endif
+
     // ================================================================================================
     //  peel-off walks towards observer `obs` (the instrument that starts an observer group) of the slots
     //  [slotBase, slotBase + numSlots): task record 1 + obs of every slot; result: SlotArrays::ptau
@@ -325,35 +448,21 @@
         constexpr int SGNX = -1;  // (the direction's signs from scalar registers)
         const DevScene& S = c_scene[sceneSlot];
         extern __shared__ double lds[];
-        const int tid = threadIdx.x;
-        const int lane = tid & 63;
-        requireLdsBaseZero(lds);
-        stageGrid<GRID_TREE>(S, lds, tid, blockDim.x);
-        __syncthreads();
-        GridLds L = makeGridLds(S, lds);
-        if (!WIDE) L.gtab = nullptr;  // (octrees up to level 10 always have their table in LDS: the test folds away)
+        const int lane = threadIdx.x & 63;
+        TreeConst C;
+        const GridLds L = treeFrame<WIDE>(S, lds, C);
         const SlotArrays& A = S.slots;
         const TaskArrays& K = S.tasks;
         const int64_t rec = (int64_t)(1 + obs) * A.num_slots;
         double* const ptau = A.ptau + (int64_t)obs * A.num_slots;
         const char* nodes = reinterpret_cast<const char*>(S.nodes);
         const double eps = S.eps;
-        TreeConst C;
-        loadTreeConst(S, C);
-        // the observer's direction: wave-uniform (scalar loads from the scene)
-        const DevInstrument& I = S.inst[obs];
         Dir d;
-        d.kx = I.kx, d.ky = I.ky, d.kz = I.kz;
-        d.ikx = I.ikx, d.iky = I.iky, d.ikz = I.ikz;
-        d.sgn = I.sgn;
-        setDirMasks(d);
+        observerDir(S.inst[obs], d);
 
         TWalk<WIDE> w;
-        w.cell = 0, w.axis = 0, w.szb = 8u, w.bx = w.by = w.bz = 0u;
-        w.ds = 0., w.tau = 0., w.s = 0., w.dens = 0., w.lastm = -1;
-        w.rx = w.ry = w.rz = 0.;
         CellLoad g;  // the record of w.cell (in flight, or landed) whenever the lane is ST_ACTIVE
-        g.a = make_uint4(0, 0, 0, 0), g.b = make_uint4(0, 0, 0, 0);
+        idleWalk(w, g);
         int slot = -1;
         int st = ST_IDLE;
         double sext = 0., target = 0.;
@@ -376,24 +485,9 @@
             if (service)
             {
                 services += 1;
-                bool fresh = false;  // the lane takes up a cell whose record has not been requested yet
-                // ---- undecided steps (rare): the literal algorithm
-                PMC_CENSUS(2, st == ST_EDGE);
-                if (st == ST_EDGE) st = treeEdgeStateAt(C, w.rx, w.ry, w.rz);
-                PMC_CENSUS(0, st == ST_SLOW);
-                if (st == ST_SLOW)
-                {
-                    st = treeSlowStep<WIDE>(S, L, d, w) ? ST_ACTIVE : ST_EXIT;
-                    fresh = st == ST_ACTIVE;
-                }
-                PMC_CENSUS(6, st == ST_HIT);
-                PMC_CENSUS(7, st == ST_EXIT);
-                // ---- finished walks: tau >= taumax (MediumSystem.cpp:1215-1218) or the optical depth of the whole path
-                if (st == ST_HIT || st == ST_EXIT)
-                {
-                    ptau[slot] = st == ST_HIT ? INFINITY : w.tau;
-                    st = ST_IDLE;
-                }
+                // ---- undecided steps, finished walks
+                bool fresh = treeServeUndecided<WIDE>(S, L, C, d, w, st PMC_WPROF_PASS);  // the lane takes up a cell whose record has not been requested yet
+                peelStoreResult(ptau, slot, w.tau, st);
                 // ---- the next slots
                 const int got = claimSlots(S, cursor, (unsigned long long)numSlots, lane, st == ST_IDLE, poolNext, poolEnd, exhausted, list ? 64ull : (unsigned long long)PMC_TASK_CHUNK);
                 PMC_WSTAMP(5);
@@ -441,13 +535,7 @@
                 PMC_WSTAMP(7);
                 if (st == ST_ACTIVE)
                 {
-                    // the position after the pending segment, r + k (ds + eps) (TreeSpatialGrid.cpp:186-191): needs no memory
-                    const double step = w.ds + eps;
-                    const double nrx = w.rx + d.kx * step, nry = w.ry + d.ky * step, nrz = w.rz + d.kz * step;
-                    // the record of the current cell: density and the link through the exit wall
-                    const uint32_t link = cellLink<SGNX>(g, d, w.axis);
-                    w.dens = cellDensity(g);
-                    PMC_WSTAMP(0);
+                    const StepHead h = treeStepHead<WIDE, SGNX>(d, eps, w, g PMC_WPROF_PASS);
                     // the pending segment (MediumSystem.cpp:1207-1219): stop once tau >= taumax
                     double tau1 = w.tau + sext * w.dens * w.ds;
                     if (MM)
@@ -461,37 +549,14 @@
                     else
                     {
                         w.tau = tau1;
-                        w.rx = nrx, w.ry = nry, w.rz = nrz;
-                        uint32_t cell2;
-                        st = treeResolve<WIDE, SGNX>(C, nodes, d, w, link, nrx, nry, nrz, cell2 PMC_WPROF_PASS);
-                        PMC_WSTAMP(1);
-                        if (st == ST_ACTIVE)
-                        {
-                            // the next cell's record is requested BEFORE the arithmetic that enters the cell
-                            cellIssue(C, cell2, g);
-                            st = treeEnterBox<WIDE, SGNX>(C, d, w PMC_WPROF_PASS);
-                            if (st == ST_ACTIVE) w.cell = cell2;
-                            PMC_WSTAMP(4);
-                        }
+                        st = treeAdvance<WIDE, SGNX>(C, nodes, d, w, g, h.link, h.nrx, h.nry, h.nrz PMC_WPROF_PASS);
                     }
                 }
             }
         }
-        if (lane == 0 && visits)
-        {
-            atomicAdd(S.counters + 2, visits);
-            atomicAdd(S.counters + PMC_CTR_WALKWORK + 0, waveSteps);
-            atomicAdd(S.counters + PMC_CTR_WALKWORK + 1, visits);
-            atomicAdd(S.counters + PMC_CTR_WALKWORK + 2, services);
-        }
+        flushPeelWork(S, lane, visits, waveSteps, services);
 #ifdef PMC_PROFILE
-        if (lane == 0)
-            for (int i = 0; i < 8; ++i) atomicAdd(S.counters + 208 + i, (unsigned long long)prof.t[i]);
-        for (int i = 0; i < 8; ++i)
-        {
-            const unsigned long long c = waveSum(prof.census[i]);
-            if (lane == 0 && c) atomicAdd(S.counters + 224 + i, c);
-        }
+        flushWalkProf(S, lane, prof, 208, true);
 #endif
     }
 
@@ -520,25 +585,16 @@
         extern __shared__ double lds[];
         const int tid = threadIdx.x;
         const int lane = tid & 63;
-        requireLdsBaseZero(lds);
-        stageGrid<GRID_TREE>(S, lds, tid, blockDim.x);
-        __syncthreads();
-        GridLds L = makeGridLds(S, lds);
-        if (!WIDE) L.gtab = nullptr;  // (octrees up to level 10 always have their table in LDS: the test folds away)
+        TreeConst C;
+        const GridLds L = treeFrame<WIDE>(S, lds, C);
         const SlotArrays& A = S.slots;
         const TaskArrays& K = S.tasks;
         const int64_t rec = (int64_t)(1 + obs) * A.num_slots;
         double* const ptau = A.ptau + (int64_t)obs * A.num_slots;
         const char* nodes = reinterpret_cast<const char*>(S.nodes);
         const double eps = S.eps;
-        TreeConst C;
-        loadTreeConst(S, C);
-        const DevInstrument& I = S.inst[obs];
         Dir d;
-        d.kx = I.kx, d.ky = I.ky, d.kz = I.kz;
-        d.ikx = I.ikx, d.iky = I.iky, d.ikz = I.ikz;
-        d.sgn = I.sgn;
-        setDirMasks(d);
+        observerDir(S.inst[obs], d);
         // the wave's queue of task records
         char* const qbase = reinterpret_cast<char*>(lds) + queueOffset + (tid >> 6) * PEEL_QBYTES;
         double* const qF = reinterpret_cast<double*>(qbase);                       // [6][PEEL_QCAP]
@@ -550,11 +606,8 @@
         uint32_t xcdSeg = xccId(), xcdTried = 0u;  // (sorted records) the segment of the tile order this wave takes its walks from
 
         TWalk<WIDE> w;
-        w.cell = 0, w.axis = 0, w.szb = 8u, w.bx = w.by = w.bz = 0u;
-        w.ds = 0., w.tau = 0., w.s = 0., w.dens = 0., w.lastm = -1;
-        w.rx = w.ry = w.rz = 0.;
         CellLoad g;
-        g.a = make_uint4(0, 0, 0, 0), g.b = make_uint4(0, 0, 0, 0);
+        idleWalk(w, g);
         int slot = -1;
         int st = ST_IDLE;
         double sext = 0., target = 0.;
@@ -576,20 +629,9 @@
             if (drained ? (pendingMask != 0ull) : (64 - __popcll(activeMask) >= PMC_PEEL2_REFILL))
             {
                 services += 1;
-                bool fresh = false;  // the lane takes up a cell whose record has not been requested yet
-                // undecided steps (rare): the literal algorithm
-                if (st == ST_EDGE) st = treeEdgeStateAt(C, w.rx, w.ry, w.rz);
-                if (st == ST_SLOW)
-                {
-                    st = treeSlowStep<WIDE>(S, L, d, w) ? ST_ACTIVE : ST_EXIT;
-                    fresh = st == ST_ACTIVE;
-                }
-                // finished walks: tau >= taumax (MediumSystem.cpp:1215-1218) or the optical depth of the whole path
-                if (st == ST_HIT || st == ST_EXIT)
-                {
-                    ptau[slot] = st == ST_HIT ? INFINITY : w.tau;
-                    st = ST_IDLE;
-                }
+                // undecided steps, finished walks
+                bool fresh = treeServeUndecided<WIDE>(S, L, C, d, w, st PMC_WPROF_PASS);  // the lane takes up a cell whose record has not been requested yet
+                peelStoreResult(ptau, slot, w.tau, st);
                 // the queue is refilled with the records of the next 64 slots that hold a walk
                 if (!exhausted && qCount <= PEEL_QCAP - 64)
                 {
@@ -684,12 +726,15 @@
                 waveSteps += 1;
                 if (st == ST_ACTIVE)
                 {
+                    // (the head of the step, written out: the record counts as landed AFTER the position arithmetic.  Through treeStepHead this kernel was
+                    // 7 % slower with cellLanded in front of the call and 2 % slower with it inside the helper -- profiles/sweeps/octree_step_once.md)
                     const double step = w.ds + eps;
-                    const double nrx = w.rx + d.kx * step, nry = w.ry + d.ky * step, nrz = w.rz + d.kz * step;
+                    StepHead h;  // (not plain locals: 0.4 ms, 2 %, slower, same file.  Fragile -- it is the allocator's answer to the source form: time any edit here)
+                    h.nrx = w.rx + d.kx * step, h.nry = w.ry + d.ky * step, h.nrz = w.rz + d.kz * step;
 #ifndef PMC_EXP_NARROW_LOADS
                     cellLanded(g);
 #endif
-                    const uint32_t link = cellLink<SGNX>(g, d, w.axis);
+                    h.link = cellLink<SGNX>(g, d, w.axis);
                     w.dens = cellDensity(g);
                     const double tau1 = w.tau + sext * w.dens * w.ds;
                     if (tau1 > target)
@@ -697,26 +742,15 @@
                     else
                     {
                         w.tau = tau1;
-                        w.rx = nrx, w.ry = nry, w.rz = nrz;
-                        uint32_t cell2;
-                        st = treeResolve<WIDE, SGNX>(C, nodes, d, w, link, nrx, nry, nrz, cell2 PMC_WPROF_PASS);
-                        if (st == ST_ACTIVE)
-                        {
-                            cellIssue(C, cell2, g);
-                            st = treeEnterBox<WIDE, SGNX>(C, d, w PMC_WPROF_PASS);
-                            if (st == ST_ACTIVE) w.cell = cell2;
-                        }
+                        st = treeAdvance<WIDE, SGNX>(C, nodes, d, w, g, h.link, h.nrx, h.nry, h.nrz PMC_WPROF_PASS);
                     }
                 }
             }
         }
-        if (lane == 0 && visits)
-        {
-            atomicAdd(S.counters + 2, visits);
-            atomicAdd(S.counters + PMC_CTR_WALKWORK + 0, waveSteps);
-            atomicAdd(S.counters + PMC_CTR_WALKWORK + 1, visits);
-            atomicAdd(S.counters + PMC_CTR_WALKWORK + 2, services);
-        }
+        flushPeelWork(S, lane, visits, waveSteps, services);
+#ifdef PMC_PROFILE
+        flushWalkProf(S, lane, prof, 208, false);  // (the census only: this kernel has but the two stamps of treeAdvance, no phase breakdown)
+#endif
     }
 
     // ================================================================================================
@@ -736,8 +770,90 @@
     // and 19.1 without any record; 144 bytes of LDS per lane.  (ckptOffset < 0: no room in LDS, e.g. next to the coordinate table of a
     // 12-level octree: pass 2 walks the path from its start.)  Round 3 measured checkpoints in HBM (slower: their stores sit in the
     // step loop's in-order memory pipe); these never leave LDS.
+    // The decisions (when B becomes A, which state pass 2 resumes from) are ckptTick and ckptResume in pmc_walk.inc, shared with voroPropKernel.
     constexpr int PROP_CKPT_BYTES = PMC_PROP_BLOCK * 2 * 9 * 8;
-    constexpr uint32_t CK_SEL = 1u, CK_HASA = 2u, CK_HASB = 4u, CK_LIN = 8u;
+    // a checkpoint of a lane, q[field * PMC_PROP_BLOCK]; fields: position (3), tau, s, ds, bx | by << 32, cell | bz << 32, lastm | (axis | szb << 2) << 32
+    template<bool WIDE> __device__ __forceinline__ void ckptSave(double* q, const TWalk<WIDE>& w)
+    {
+        q[0 * PMC_PROP_BLOCK] = w.rx, q[1 * PMC_PROP_BLOCK] = w.ry, q[2 * PMC_PROP_BLOCK] = w.rz;
+        q[3 * PMC_PROP_BLOCK] = w.tau, q[4 * PMC_PROP_BLOCK] = w.s, q[5 * PMC_PROP_BLOCK] = w.ds;
+        q[6 * PMC_PROP_BLOCK] = __longlong_as_double((long long)((unsigned long long)w.bx | ((unsigned long long)w.by << 32)));
+        q[7 * PMC_PROP_BLOCK] = __longlong_as_double((long long)((unsigned long long)w.cell | ((unsigned long long)w.bz << 32)));
+        q[8 * PMC_PROP_BLOCK] = __longlong_as_double((long long)((unsigned long long)(uint32_t)w.lastm | ((unsigned long long)(w.axis | (w.szb << 2)) << 32)));
+    }
+    template<bool WIDE> __device__ __forceinline__ void ckptLoad(const double* q, TWalk<WIDE>& w)
+    {
+        w.rx = q[0 * PMC_PROP_BLOCK], w.ry = q[1 * PMC_PROP_BLOCK], w.rz = q[2 * PMC_PROP_BLOCK];
+        w.tau = q[3 * PMC_PROP_BLOCK], w.s = q[4 * PMC_PROP_BLOCK], w.ds = q[5 * PMC_PROP_BLOCK];
+        const unsigned long long w6 = (unsigned long long)__double_as_longlong(q[6 * PMC_PROP_BLOCK]);
+        const unsigned long long w7 = (unsigned long long)__double_as_longlong(q[7 * PMC_PROP_BLOCK]);
+        const unsigned long long w8 = (unsigned long long)__double_as_longlong(q[8 * PMC_PROP_BLOCK]);
+        w.bx = (uint32_t)w6, w.by = (uint32_t)(w6 >> 32);
+        w.cell = (uint32_t)w7, w.bz = (uint32_t)(w7 >> 32);
+        w.lastm = (int)(uint32_t)w8;
+        w.axis = (uint32_t)(w8 >> 32) & 3u;
+        w.szb = (uint32_t)(w8 >> 34);
+    }
+
+    // The wave's chunk of the group's log of radiation-field contributions (pmc_device.h RfLogArgs): wave-uniform.  The contributions go to
+    // the log -- coalesced stores; partitioned by key range and summed in LDS after the generation (pmc_log.inc): as atomics into the table
+    // (238 per history, every lane on a sector of its own) they cost 0.95 s per 1e8 packets, more than the walks themselves.
+    struct RfLogWave
+    {
+        bool ok;                  // the log takes entries (false: none configured, or full -- atomics)
+        unsigned long long base;  // first entry of the wave's chunk
+        uint32_t fill;            // entries of it in use (PMC_RF_LOG_CHUNK: the wave holds no chunk yet)
+    };
+    // the contributions (key `at`: DEVICE numbering of the cells) of the lanes with `pending`, the wave converged: to its chunk, or, the log full, to the table
+    __device__ __forceinline__ void rfLogAppend(const DevScene& S, const RfLogArgs& rl, RfLogWave& lw, int lane, bool pending, int64_t at, double value)
+    {
+        const unsigned long long m = __ballot(pending);
+        if (m == 0ull) return;
+        bool logged = false;
+        if (lw.ok)
+        {
+            const uint32_t n = (uint32_t)__popcll(m);
+            const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (lw.fill + n > (uint32_t)PMC_RF_LOG_CHUNK)
+            {
+                // the rest of the chunk (fewer than n entries) is filled up, the next chunk claimed
+                if (pending && lw.fill + rank < (uint32_t)PMC_RF_LOG_CHUNK) rl.keys[lw.base + lw.fill + rank] = rl.padKey;
+                unsigned long long got = 0;
+                if (lane == 0) got = atomicAdd(S.counters + rl.cursor, (unsigned long long)PMC_RF_LOG_CHUNK);
+                got = __shfl(got, 0, 64);
+                lw.fill = PMC_RF_LOG_CHUNK;
+                if (got + PMC_RF_LOG_CHUNK > rl.cap)
+                    lw.ok = false;  // (the log is full: atomics from here on)
+                else
+                {
+                    lw.base = got;
+                    lw.fill = 0;
+                }
+            }
+            if (lw.ok)
+            {
+                if (pending)
+                {
+                    rl.keys[lw.base + lw.fill + rank] = (uint32_t)at;
+                    rl.vals[lw.base + lw.fill + rank] = value;
+                }
+                lw.fill += n;
+                logged = true;
+            }
+        }
+        if (pending && !logged)
+        {
+            // (the caller's cell index is looked up here; for the log, when the sums are added to the table)
+            const int64_t dev = at / S.rf_num_lambda;
+            unsafeAtomicAdd(S.rf + ((int64_t)S.cell_ext[dev] * S.rf_num_lambda + (at - dev * S.rf_num_lambda)), value);
+        }
+    }
+    // the unused rest of the wave's last chunk is filled up with pad keys
+    __device__ __forceinline__ void rfLogEnd(const RfLogArgs& rl, const RfLogWave& lw, int lane)
+    {
+        if (rl.cap == 0ull) return;
+        for (uint32_t i = lw.fill + (uint32_t)lane; i < (uint32_t)PMC_RF_LOG_CHUNK; i += 64u) rl.keys[lw.base + i] = rl.padKey;
+    }
     // EA: the explicit-absorption photon cycle (see walkKernel in pmc_walk.inc): scattering and absorption optical depths apart, no pass-1
     // records (an interaction inside them would need the absorption depths as well)
     // MM: several medium components (see walkKernel in pmc_walk.inc): no pass-1 records either
@@ -751,35 +867,26 @@
         extern __shared__ double lds[];
         const int tid = threadIdx.x;
         const int lane = tid & 63;
-        requireLdsBaseZero(lds);
-        stageGrid<GRID_TREE>(S, lds, tid, blockDim.x);
-        __syncthreads();
-        GridLds L = makeGridLds(S, lds);
-        if (!WIDE) L.gtab = nullptr;  // (octrees up to level 10 always have their table in LDS: the test folds away)
+        TreeConst C;
+        const GridLds L = treeFrame<WIDE>(S, lds, C);
         const SlotArrays& A = S.slots;
         const TaskArrays& K = S.tasks;
         const char* nodes = reinterpret_cast<const char*>(S.nodes);
         const double eps = S.eps;
         const bool force = S.force_scattering != 0;
-        TreeConst C;
-        loadTreeConst(S, C);
-        // the two pass-1 checkpoints of this lane: ckState[(buffer * 9 + field) * PMC_PROP_BLOCK]; fields: position (3), tau, s, ds,
-        // bx | by << 32, cell | bz << 32, lastm | (axis | szb << 2) << 32
+        // the two pass-1 checkpoints of this lane: buffer b at ckState + b * 9 * PMC_PROP_BLOCK (ckptSave, ckptLoad)
         const bool ckpt = ckptOffset >= 0 && force && !EA && !MM;
         double* const ckState = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + (ckptOffset >= 0 ? ckptOffset : 0)) + tid;
-        uint32_t ck = 0;            // CK_SEL: the buffer that holds B; CK_HASA / CK_HASB; CK_LIN: the sampled depth is u2 * tau_path
+        uint32_t ck = 0;            // the CK_ flags (pmc_walk.inc)
         double ckTauB = 0.;         // cumulative optical depth of state B
         double uni1 = 0., uni2 = 0.;  // the uniforms drawn for simulateForcedPropagation (see startCycle)
 
         TWalk<WIDE> w;
-        w.cell = 0, w.axis = 0, w.szb = 8u, w.bx = w.by = w.bz = 0u;
-        w.ds = 0., w.tau = 0., w.s = 0., w.dens = 0., w.lastm = -1;
-        w.rx = w.ry = w.rz = 0.;
+        CellLoad g;  // the record of w.cell (in flight, or landed) whenever the lane is ST_ACTIVE
+        idleWalk(w, g);
         Dir d;
         d.kx = d.ky = d.kz = 0., d.ikx = d.iky = d.ikz = 0., d.sgn = 0;
         setDirMasks(d);
-        CellLoad g;  // the record of w.cell (in flight, or landed) whenever the lane is ST_ACTIVE
-        g.a = make_uint4(0, 0, 0, 0), g.b = make_uint4(0, 0, 0, 0);
         int slot = -1;
         int st = ST_IDLE;
         int mode = MODE_NONE;
@@ -790,11 +897,7 @@
         uint32_t visits = 0, rewalks = 0, paths = 0;
         double rfL = 0., rfExtBeg = 1.;
         int rfEll = -1;
-        // (RF) the wave's chunk of the group's log of radiation-field contributions: wave-uniform
-        bool logOK = RF && rfLog.cap != 0ull;
-        unsigned long long logBase = 0;
-        uint32_t logFill = PMC_RF_LOG_CHUNK;  // (no chunk yet)
-        const unsigned long long laneBelow = (1ull << lane) - 1ull;
+        RfLogWave logWave = {RF && rfLog.cap != 0ull, 0ull, PMC_RF_LOG_CHUNK};  // (RF; no chunk yet)
         bool exhausted = false;
         unsigned long long poolNext = 0, poolEnd = 0;  // wave-uniform
         unsigned long long waveSteps = 0, laneSteps = 0, services = 0;
@@ -812,17 +915,7 @@
             if (service)
             {
                 services += 1;
-                bool fresh = false;  // the lane takes up a cell whose record has not been requested yet
-                PMC_CENSUS(2, st == ST_EDGE);
-                if (st == ST_EDGE) st = treeEdgeStateAt(C, w.rx, w.ry, w.rz);
-                PMC_CENSUS(0, st == ST_SLOW);
-                if (st == ST_SLOW)
-                {
-                    st = treeSlowStep<WIDE>(S, L, d, w) ? ST_ACTIVE : ST_EXIT;
-                    fresh = st == ST_ACTIVE;
-                }
-                PMC_CENSUS(6, st == ST_HIT);
-                PMC_CENSUS(7, st == ST_EXIT);
+                bool fresh = treeServeUndecided<WIDE>(S, L, C, d, w, st PMC_WPROF_PASS);  // the lane takes up a cell whose record has not been requested yet
                 // ---- finished walks: the result, or pass 2 over the same path (`again`)
                 bool again = false;
                 bool resumed = false;  // pass 2 resumes from the state saved during pass 1
@@ -846,26 +939,11 @@
                         visits += nseg;
                         if (ckpt)
                         {
-                            // pass 2 resumes from the later checkpoint that lies at or before the interaction point (B is a candidate;
-                            // A is certain but for a sampled depth that a rejection round has redrawn: checked as well)
-                            int from = -1;
-                            if ((ck & CK_HASB) && ckTauB <= target)
-                                from = (int)(ck & CK_SEL);
-                            else if ((ck & CK_HASA) && ckState[((ck & CK_SEL) ^ 1u) * 9 * PMC_PROP_BLOCK + 3 * PMC_PROP_BLOCK] <= target)
-                                from = (int)((ck & CK_SEL) ^ 1u);
+                            // pass 2 resumes from the later checkpoint that lies at or before the interaction point (A's depth waits in LDS)
+                            const int from = ckptResume(ck, ckState[(((ck & CK_SEL) ^ 1u) * 9 + 3) * PMC_PROP_BLOCK], ckTauB, target);
                             if (from >= 0)
                             {
-                                const double* const q = ckState + from * 9 * PMC_PROP_BLOCK;
-                                w.rx = q[0 * PMC_PROP_BLOCK], w.ry = q[1 * PMC_PROP_BLOCK], w.rz = q[2 * PMC_PROP_BLOCK];
-                                w.tau = q[3 * PMC_PROP_BLOCK], w.s = q[4 * PMC_PROP_BLOCK], w.ds = q[5 * PMC_PROP_BLOCK];
-                                const unsigned long long w6 = (unsigned long long)__double_as_longlong(q[6 * PMC_PROP_BLOCK]);
-                                const unsigned long long w7 = (unsigned long long)__double_as_longlong(q[7 * PMC_PROP_BLOCK]);
-                                const unsigned long long w8 = (unsigned long long)__double_as_longlong(q[8 * PMC_PROP_BLOCK]);
-                                w.bx = (uint32_t)w6, w.by = (uint32_t)(w6 >> 32);
-                                w.cell = (uint32_t)w7, w.bz = (uint32_t)(w7 >> 32);
-                                w.lastm = (int)(uint32_t)w8;
-                                w.axis = (uint32_t)(w8 >> 32) & 3u;
-                                w.szb = (uint32_t)(w8 >> 34);
+                                ckptLoad(ckState + from * 9 * PMC_PROP_BLOCK, w);
                                 nseg = 0;
                                 mode = MODE_PASS2;
                                 st = ST_ACTIVE;
@@ -943,8 +1021,7 @@
                         if (!again)
                         {
                             uni1 = u1, uni2 = u2;
-                            // (no checkpoint yet; the branch of simulateForcedPropagation the uniforms will take: sampleForcedDepth)
-                            ck = (S.path_length_bias != 0. && u1 < S.path_length_bias) ? CK_LIN : 0u;
+                            ck = ckptStart(S, u1);
                         }
                     }
                     if (again)
@@ -959,29 +1036,10 @@
             if (ckpt)
             {
                 const bool p1 = st == ST_ACTIVE && mode == MODE_PASS1 && w.tau > 0.;
-                bool save = p1 && !(ck & CK_HASB);
-                if (p1 && (ck & CK_HASB))
+                if (p1 && ckptTick(ck, w.tau, ckTauB, uni2))
                 {
-                    // B is certain once the lower bound of the sampled depth has passed it: it becomes A, the current state the new B
-                    const double bound = uni2 * w.tau;
-                    const double need = (ck & CK_LIN) ? ckTauB : ckTauB * (1. + w.tau) * (1. + 1e-13);
-                    if (bound >= need)
-                    {
-                        ck = (ck ^ CK_SEL) | CK_HASA;
-                        save = true;
-                    }
-                }
-                if (save)
-                {
-                    double* const q = ckState + (ck & CK_SEL) * 9 * PMC_PROP_BLOCK;
-                    q[0 * PMC_PROP_BLOCK] = w.rx, q[1 * PMC_PROP_BLOCK] = w.ry, q[2 * PMC_PROP_BLOCK] = w.rz;
-                    q[3 * PMC_PROP_BLOCK] = w.tau, q[4 * PMC_PROP_BLOCK] = w.s, q[5 * PMC_PROP_BLOCK] = w.ds;
-                    q[6 * PMC_PROP_BLOCK] = __longlong_as_double((long long)((unsigned long long)w.bx | ((unsigned long long)w.by << 32)));
-                    q[7 * PMC_PROP_BLOCK] = __longlong_as_double((long long)((unsigned long long)w.cell | ((unsigned long long)w.bz << 32)));
-                    q[8 * PMC_PROP_BLOCK] = __longlong_as_double(
-                        (long long)((unsigned long long)(uint32_t)w.lastm | ((unsigned long long)(w.axis | (w.szb << 2)) << 32)));
+                    ckptSave(ckState + (ck & CK_SEL) * 9 * PMC_PROP_BLOCK, w);
                     ckTauB = w.tau;
-                    ck |= CK_HASB;
                 }
             }
             // ---------------- walk steps
@@ -996,13 +1054,7 @@
                 double rfValue = 0.;
                 if (st == ST_ACTIVE)
                 {
-                    // the position after the pending segment, r + k (ds + eps) (TreeSpatialGrid.cpp:186-191): needs no memory
-                    const double step = w.ds + eps;
-                    const double nrx = w.rx + d.kx * step, nry = w.ry + d.ky * step, nrz = w.rz + d.kz * step;
-                    // the record of the current cell: density and the link through the exit wall
-                    const uint32_t link = cellLink<SGNX>(g, d, w.axis);
-                    w.dens = cellDensity(g);
-                    PMC_WSTAMP(0);
+                    const StepHead h = treeStepHead<WIDE, SGNX>(d, eps, w, g PMC_WPROF_PASS);
                     // the pending segment: MediumSystem.cpp:863-871 (pass 1), SpatialGridPath.cpp:177-196 (pass 2: stop in
                     // the first segment with tau > target), :988-1008 (non-forced)
                     const double ds = w.ds;
@@ -1039,73 +1091,14 @@
                             }
                             rfExtBeg = extEnd;
                         }
-                        w.rx = nrx, w.ry = nry, w.rz = nrz;
-                        uint32_t cell2;
-                        st = treeResolve<WIDE, SGNX>(C, nodes, d, w, link, nrx, nry, nrz, cell2 PMC_WPROF_PASS);
-                        PMC_WSTAMP(1);
-                        if (st == ST_ACTIVE)
-                        {
-                            // the next cell's record is requested BEFORE the arithmetic that enters the cell
-                            cellIssue(C, cell2, g);
-                            st = treeEnterBox<WIDE, SGNX>(C, d, w PMC_WPROF_PASS);
-                            if (st == ST_ACTIVE) w.cell = cell2;
-                            PMC_WSTAMP(4);
-                        }
+                        st = treeAdvance<WIDE, SGNX>(C, nodes, d, w, g, h.link, h.nrx, h.nry, h.nrz PMC_WPROF_PASS);
                     }
                 }
-                if (RF)
-                {
-                    // ---- the radiation-field contributions of this step (the lanes have converged: the bookkeeping of the
-                    // wave's chunk is wave-uniform).  They go to the group's log -- coalesced stores; partitioned by key range
-                    // and summed in LDS after the generation: as atomics into the table (238 per history, every lane on a sector
-                    // of its own) they cost 0.95 s per 1e8 packets, more than the walks themselves.
-                    const unsigned long long m = __ballot(rfPending);
-                    if (m != 0ull)
-                    {
-                        bool logged = false;
-                        if (logOK)
-                        {
-                            const uint32_t n = (uint32_t)__popcll(m);
-                            const uint32_t rank = (uint32_t)__popcll(m & laneBelow);
-                            if (logFill + n > (uint32_t)PMC_RF_LOG_CHUNK)
-                            {
-                                // the rest of the chunk (fewer than n entries) is filled up, the next chunk claimed
-                                if (rfPending && logFill + rank < (uint32_t)PMC_RF_LOG_CHUNK) rfLog.keys[logBase + logFill + rank] = rfLog.padKey;
-                                unsigned long long got = 0;
-                                if (lane == 0) got = atomicAdd(S.counters + rfLog.cursor, (unsigned long long)PMC_RF_LOG_CHUNK);
-                                got = __shfl(got, 0, 64);
-                                logFill = PMC_RF_LOG_CHUNK;
-                                if (got + PMC_RF_LOG_CHUNK > rfLog.cap)
-                                    logOK = false;  // (the log is full: atomics from here on)
-                                else
-                                {
-                                    logBase = got;
-                                    logFill = 0;
-                                }
-                            }
-                            if (logOK)
-                            {
-                                if (rfPending)
-                                {
-                                    rfLog.keys[logBase + logFill + rank] = (uint32_t)rfAt;
-                                    rfLog.vals[logBase + logFill + rank] = rfValue;
-                                }
-                                logFill += n;
-                                logged = true;
-                            }
-                        }
-                        if (rfPending && !logged)
-                        {
-                            const int64_t dev = rfAt / S.rf_num_lambda;
-                            unsafeAtomicAdd(S.rf + ((int64_t)S.cell_ext[dev] * S.rf_num_lambda + (rfAt - dev * S.rf_num_lambda)), rfValue);
-                        }
-                    }
-                }
+                // ---- the radiation-field contributions of this step (the lanes have converged)
+                if (RF) rfLogAppend(S, rfLog, logWave, lane, rfPending, rfAt, rfValue);
             }
         }
-        // (RF) the unused rest of the wave's last chunk
-        if (RF && rfLog.cap != 0ull)
-            for (uint32_t i = logFill + (uint32_t)lane; i < (uint32_t)PMC_RF_LOG_CHUNK; i += 64u) rfLog.keys[logBase + i] = rfLog.padKey;
+        if (RF) rfLogEnd(rfLog, logWave, lane);
         flushWalkCounters(S, lane, paths, visits, rewalks);
         if (lane == 0 && waveSteps)
         {
@@ -1114,348 +1107,7 @@
             atomicAdd(S.counters + PMC_CTR_WALKWORK + 5, services);
         }
 #ifdef PMC_PROFILE
-        if (lane == 0)
-            for (int i = 0; i < 8; ++i) atomicAdd(S.counters + 216 + i, (unsigned long long)prof.t[i]);
-        for (int i = 0; i < 8; ++i)
-        {
-            const unsigned long long c = waveSum(prof.census[i]);
-            if (lane == 0 && c) atomicAdd(S.counters + 232 + i, c);
-        }
+        flushWalkProf(S, lane, prof, 216, true);
 #endif
     }
 
-    // ================================================================================================
-    //  radiation field: the log of one slot group and generation -> table.  The log is a sequence of chunks of PMC_RF_LOG_CHUNK
-    //  entries, each written by one wave (filled up with pad keys).  Four kernels, launched behind the generation's walks:
-    //      rfHistKernel      entries per partition (key >> PMC_RF_BUCKET_BITS), counted per workgroup in LDS
-    //      rfScanKernel      start of every partition in the partitioned log (one workgroup)
-    //      rfScatterKernel   every chunk sorted by partition in LDS (rank by an LDS counter per partition, runs claimed with
-    //                        one atomic per partition present), then written out in runs: coalesced stores
-    //      rfReduceKernel    equal shares of the partitioned log per workgroup -- the partitions of the dense centre hold most
-    //                        entries --, summed per key in LDS (64 KB per partition), added to the table
-    //  A counting sort on the partition index only: order inside a partition does not matter to a sum.  (Rounds 1-3 used
-    //  hipcub::DeviceRadixSort for the partition and read spans with several partitions once per partition.)
-    // ================================================================================================
-    constexpr uint32_t RF_MAX_PARTS = 8192;           // partitions an LDS histogram holds: tables up to 2^26 entries are logged (10^6 cells x 64 bins)
-    constexpr uint32_t RF_TILE = PMC_RF_LOG_CHUNK;    // entries per tile of the counting sort = one chunk of the log
-    constexpr int RF_SORT_BLOCK = 512;
-    constexpr unsigned long long PMC_RF_REDUCE_SPAN = 1ull << 17;
-    constexpr int RF_REDUCE_BLOCK = 512;
-
-    // (BITS: keys per partition = 2^BITS -- PMC_RF_BUCKET_BITS for the radiation-field log, PMC_STAT_BUCKET_BITS for the statistics log)
-    template<int BITS>
-    // (fills: entries of every tile that are there -- the statistics log, whose waves leave chunks open or short -- or null: all of them)
-    __global__ __launch_bounds__(256) void rfHistKernel(const uint32_t* __restrict__ keys, const unsigned long long n, const uint32_t numParts,
-                                                        unsigned long long* __restrict__ hist, const uint32_t* __restrict__ fills)
-    {
-        __shared__ uint32_t h[RF_MAX_PARTS];
-        const uint32_t tid = threadIdx.x;
-        for (uint32_t i = tid; i < numParts; i += blockDim.x) h[i] = 0u;
-        __syncthreads();
-        const unsigned long long tiles = n / RF_TILE;
-        for (unsigned long long t = blockIdx.x; t < tiles; t += gridDim.x)
-        {
-            const uint4* k4 = reinterpret_cast<const uint4*>(keys + t * RF_TILE);
-            const unsigned long long left = fills ? fills[t] : RF_TILE;  // entries of this tile that are there
-            for (uint32_t j = tid; j < RF_TILE / 4u; j += blockDim.x)
-            {
-                if (4ull * j >= left) break;
-                const uint4 k = k4[j];
-                const uint32_t b0 = k.x >> BITS, b1 = k.y >> BITS, b2 = k.z >> BITS, b3 = k.w >> BITS;
-                if (b0 < numParts) atomicAdd(&h[b0], 1u);  // (pad keys lie beyond every partition: dropped here and in the scatter)
-                if (b1 < numParts && 4ull * j + 1 < left) atomicAdd(&h[b1], 1u);
-                if (b2 < numParts && 4ull * j + 2 < left) atomicAdd(&h[b2], 1u);
-                if (b3 < numParts && 4ull * j + 3 < left) atomicAdd(&h[b3], 1u);
-            }
-        }
-        __syncthreads();
-        for (uint32_t i = tid; i < numParts; i += blockDim.x)
-            if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
-    }
-
-    // exclusive prefix sum of `mine` over the lanes of a workgroup of up to 1024 lanes (wave scans + the waves' totals in LDS)
-    __device__ __forceinline__ unsigned long long blockExclusiveScan(unsigned long long mine, unsigned long long* waveTotals, unsigned long long& total)
-    {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (blockDim.x + 63) >> 6;
-        unsigned long long incl = mine;
-        for (int d = 1; d < 64; d <<= 1)
-        {
-            const unsigned long long up = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) waveTotals[wave] = incl;
-        __syncthreads();
-        unsigned long long before = 0ull, all = 0ull;
-        for (int w = 0; w < waves; ++w)
-        {
-            const unsigned long long t = waveTotals[w];
-            if (w < wave) before += t;
-            all += t;
-        }
-        total = all;
-        __syncthreads();
-        return before + incl - mine;
-    }
-
-    // hist (counts) -> cursor (the same array: next free position of every partition) and start[0 .. numParts] (kept for the reduce)
-    // (one workgroup of PMC_SCAN_THREADS lanes with few registers -- a prefix in LDS instead of wave shuffles of 64-bit values --: room on a
-    // CU next to a resident propagation workgroup, see endedScanKernel)
-    __global__ __launch_bounds__(PMC_SCAN_THREADS) void rfScanKernel(unsigned long long* __restrict__ hist, unsigned long long* __restrict__ start, const uint32_t numParts)
-    {
-        __shared__ unsigned long long part[PMC_SCAN_THREADS];
-        const uint32_t tid = threadIdx.x;
-        const uint32_t per = (numParts + PMC_SCAN_THREADS - 1u) / PMC_SCAN_THREADS;
-        const uint32_t lo = tid * per, hi = lo + per < numParts ? lo + per : numParts;
-        unsigned long long sum = 0ull;
-        for (uint32_t b = lo; b < hi; ++b) sum += hist[b];
-        part[tid] = sum;
-        __syncthreads();
-        for (uint32_t off = 1; off < PMC_SCAN_THREADS; off <<= 1)
-        {
-            const unsigned long long add = tid >= off ? part[tid - off] : 0ull;
-            __syncthreads();
-            part[tid] += add;
-            __syncthreads();
-        }
-        unsigned long long at = part[tid] - sum;
-        for (uint32_t b = lo; b < hi; ++b)
-        {
-            const unsigned long long c = hist[b];
-            hist[b] = at;
-            start[b] = at;
-            at += c;
-        }
-        if (tid == PMC_SCAN_THREADS - 1) start[numParts] = part[PMC_SCAN_THREADS - 1];
-    }
-
-    template<int BITS>
-    __global__ __launch_bounds__(RF_SORT_BLOCK) void rfScatterKernel(const uint32_t* __restrict__ keys, const double* __restrict__ vals, const unsigned long long n,
-                                                                     const uint32_t numParts, unsigned long long* __restrict__ cursor,
-                                                                     uint32_t* __restrict__ outKeys, double* __restrict__ outVals, const uint32_t* __restrict__ fills)
-    {
-        extern __shared__ double rfLds[];
-        __shared__ unsigned long long waveTotals[16];
-        double* stageV = rfLds;                                                 // RF_TILE doubles
-        uint32_t* stageK = reinterpret_cast<uint32_t*>(rfLds + RF_TILE);         // RF_TILE keys
-        uint32_t* cnt = stageK + RF_TILE;                                       // per partition: entries of the tile, then start of its run in the tile
-        uint32_t* delta = cnt + numParts;                                       // per partition: position of its run in the output - start in the tile (mod 2^32)
-        constexpr uint32_t E = RF_TILE / RF_SORT_BLOCK;                         // entries per lane
-        constexpr uint32_t MAXPER = RF_MAX_PARTS / RF_SORT_BLOCK;               // partitions per lane in the tile's scan
-        const uint32_t tid = threadIdx.x;
-        const uint32_t per = (numParts + RF_SORT_BLOCK - 1u) / RF_SORT_BLOCK;
-        const uint32_t lo = tid * per, hi = lo + per < numParts ? lo + per : numParts;
-        const unsigned long long tiles = n / RF_TILE;
-        for (unsigned long long t = blockIdx.x; t < tiles; t += gridDim.x)
-        {
-            for (uint32_t i = tid; i < numParts; i += RF_SORT_BLOCK) cnt[i] = 0u;
-            __syncthreads();
-            // a lane's entries: E consecutive keys (two 16-byte loads) and values
-            uint32_t k[E], rank[E];
-            double v[E];
-            const unsigned long long base = t * RF_TILE + (unsigned long long)tid * E;
-            for (uint32_t j = 0; j < E; j += 4u)
-            {
-                const uint4 q = *reinterpret_cast<const uint4*>(keys + base + j);
-                k[j] = q.x, k[j + 1] = q.y, k[j + 2] = q.z, k[j + 3] = q.w;
-            }
-            for (uint32_t j = 0; j < E; j += 2u)
-            {
-                const double2 q = *reinterpret_cast<const double2*>(vals + base + j);
-                v[j] = q.x, v[j + 1] = q.y;
-            }
-            // (a tile of the statistics log that a wave has left open or short: the entries beyond its fill are not there)
-            if (fills)
-            {
-                const uint32_t there = fills[t];
-                for (uint32_t j = 0; j < E; ++j)
-                    if (tid * E + j >= there) k[j] = 0xFFFFFFFFu;
-            }
-            for (uint32_t j = 0; j < E; ++j)
-            {
-                const uint32_t b = k[j] >> BITS;
-                rank[j] = b < numParts ? atomicAdd(&cnt[b], 1u) : 0u;
-            }
-            __syncthreads();
-            // runs of the tile: exclusive scan of the counts; every partition present claims its run in the output
-            uint32_t c[MAXPER];
-            uint32_t sum = 0u;
-            for (uint32_t i = 0; i < MAXPER; ++i)
-            {
-                const uint32_t b = lo + i;
-                c[i] = b < hi ? cnt[b] : 0u;
-                sum += c[i];
-            }
-            unsigned long long total;
-            uint32_t at = (uint32_t)blockExclusiveScan((unsigned long long)sum, waveTotals, total);
-            for (uint32_t i = 0; i < MAXPER; ++i)
-            {
-                const uint32_t b = lo + i;
-                if (b < hi)
-                {
-                    cnt[b] = at;
-                    if (c[i]) delta[b] = (uint32_t)atomicAdd(&cursor[b], (unsigned long long)c[i]) - at;
-                    at += c[i];
-                }
-            }
-            __syncthreads();
-            for (uint32_t j = 0; j < E; ++j)
-            {
-                const uint32_t b = k[j] >> BITS;
-                if (b < numParts)
-                {
-                    const uint32_t pos = cnt[b] + rank[j];
-                    stageK[pos] = k[j];
-                    stageV[pos] = v[j];
-                }
-            }
-            __syncthreads();
-            const uint32_t live = (uint32_t)total;
-            for (uint32_t pos = tid; pos < live; pos += RF_SORT_BLOCK)
-            {
-                const uint32_t key = stageK[pos];
-                const uint32_t dest = pos + delta[key >> BITS];
-                outKeys[dest] = key;
-                outVals[dest] = stageV[pos];
-            }
-            __syncthreads();
-        }
-    }
-
-    __global__ __launch_bounds__(RF_REDUCE_BLOCK) void rfReduceKernel(const int sceneSlot, const uint32_t* __restrict__ keys, const double* __restrict__ vals,
-                                                                      const unsigned long long* __restrict__ start, const uint32_t numParts)
-    {
-        const DevScene& S = c_scene[sceneSlot];
-        extern __shared__ double acc[];
-        constexpr uint32_t SIZE = 1u << PMC_RF_BUCKET_BITS;
-        const uint32_t tid = threadIdx.x;
-        const unsigned long long total = start[numParts];
-        const unsigned long long first = (unsigned long long)blockIdx.x * PMC_RF_REDUCE_SPAN;
-        if (first >= total) return;
-        const unsigned long long last = first + PMC_RF_REDUCE_SPAN < total ? first + PMC_RF_REDUCE_SPAN : total;
-        const int64_t size = (int64_t)S.cell_slots * S.rf_num_lambda;  // (keys count cells in the device numbering)
-        const int nl = S.rf_num_lambda;
-        // table index of a key: the caller's cell index from the device one (padding slots of the device numbering hold no cell)
-        auto tableIndex = [&](int64_t key) -> int64_t {
-            if (key >= size) return -1;
-            const int64_t dev = nl == 1 ? key : key / nl;
-            const int m = S.cell_ext[dev];
-            return m < 0 ? -1 : (int64_t)m * nl + (key - dev * nl);
-        };
-        // the partition that holds entry `first`: the last one that starts at or before it
-        uint32_t b = 0u, hiPart = numParts;
-        while (hiPart - b > 1u)
-        {
-            const uint32_t mid = (b + hiPart) >> 1;
-            if (start[mid] <= first)
-                b = mid;
-            else
-                hiPart = mid;
-        }
-        unsigned long long pos = first;
-        while (pos < last)
-        {
-            while (start[b + 1u] <= pos) ++b;  // (empty partitions)
-            const unsigned long long end = start[b + 1u] < last ? start[b + 1u] : last;
-            const int64_t partBase = (int64_t)b << PMC_RF_BUCKET_BITS;
-            if (end - pos < (unsigned long long)PMC_RF_SHORT_RUN)
-            {
-                // a short run (the sparse outskirts; tables with many wavelength bins): not worth clearing and flushing 64 KB
-                for (unsigned long long i = pos + tid; i < end; i += RF_REDUCE_BLOCK)
-                {
-                    const int64_t at = tableIndex(partBase + (keys[i] & (SIZE - 1u)));
-                    if (at >= 0) unsafeAtomicAdd(S.rf + at, vals[i]);
-                }
-            }
-            else
-            {
-                for (uint32_t i = tid; i < SIZE; i += RF_REDUCE_BLOCK) acc[i] = 0.;
-                __syncthreads();
-                for (unsigned long long i = pos + tid; i < end; i += RF_REDUCE_BLOCK) atomicAdd(&acc[keys[i] & (SIZE - 1u)], vals[i]);
-                __syncthreads();
-                for (uint32_t i = tid; i < SIZE; i += RF_REDUCE_BLOCK)
-                {
-                    const double v = acc[i];
-                    if (v != 0.)
-                    {
-                        const int64_t at = tableIndex(partBase + i);
-                        if (at >= 0) unsafeAtomicAdd(S.rf + at, v);
-                    }
-                }
-                __syncthreads();
-            }
-            pos = end;
-        }
-    }
-
-    // ================================================================================================
-    //  statistics log -> accumulator records (pmc_device.h StatLogArgs): the log, partitioned by key range (2^PMC_STAT_BUCKET_BITS records
-    //  per partition) by the counting sort above; every workgroup takes an equal share of it -- the partitions of the image centre hold
-    //  most entries --, sums w^0 .. w^4 per record in LDS and adds the non-zero sums to DevScene::stat_acc (five consecutive doubles of
-    //  a 64-byte record: lanes on consecutive addresses).  FluxRecorder.cpp:1000-1012.
-    // ================================================================================================
-    __global__ __launch_bounds__(RF_REDUCE_BLOCK) void statReduceKernel(const int sceneSlot, const uint32_t* __restrict__ keys, const double* __restrict__ vals,
-                                                                        const unsigned long long* __restrict__ start, const uint32_t numParts)
-    {
-        const DevScene& S = c_scene[sceneSlot];
-        extern __shared__ double acc[];  // [5][SIZE]
-        constexpr uint32_t SIZE = 1u << PMC_STAT_BUCKET_BITS;
-        const uint32_t tid = threadIdx.x;
-        const unsigned long long total = start[numParts];
-        const unsigned long long first = (unsigned long long)blockIdx.x * PMC_RF_REDUCE_SPAN;
-        if (first >= total) return;
-        const unsigned long long last = first + PMC_RF_REDUCE_SPAN < total ? first + PMC_RF_REDUCE_SPAN : total;
-        const int64_t records = S.stat_acc_records;
-        // the partition that holds entry `first`: the last one that starts at or before it
-        uint32_t b = 0u, hiPart = numParts;
-        while (hiPart - b > 1u)
-        {
-            const uint32_t mid = (b + hiPart) >> 1;
-            if (start[mid] <= first)
-                b = mid;
-            else
-                hiPart = mid;
-        }
-        unsigned long long pos = first;
-        while (pos < last)
-        {
-            while (start[b + 1u] <= pos) ++b;  // (empty partitions)
-            const unsigned long long end = start[b + 1u] < last ? start[b + 1u] : last;
-            const int64_t partBase = (int64_t)b << PMC_STAT_BUCKET_BITS;
-            if (end - pos < (unsigned long long)PMC_STAT_SHORT_RUN)
-            {
-                // a short run (the outskirts of the image): not worth clearing and flushing 80 KB
-                for (unsigned long long i = pos + tid; i < end; i += RF_REDUCE_BLOCK)
-                {
-                    const int64_t rec = partBase + (keys[i] & (SIZE - 1u));
-                    if (rec < records)
-                    {
-                        // (powers as FluxRecorder.cpp:1003-1008 forms them, wn *= w: ((w w) w) w -- the same operations as the atomic path)
-                        const double w = vals[i], w2 = w * w, w3 = w2 * w, w4 = w3 * w;
-                        double* const at = S.stat_acc + (rec << 3);
-                        unsafeAtomicAdd(at + 0, 1.), unsafeAtomicAdd(at + 1, w), unsafeAtomicAdd(at + 2, w2), unsafeAtomicAdd(at + 3, w3), unsafeAtomicAdd(at + 4, w4);
-                    }
-                }
-            }
-            else
-            {
-                for (uint32_t i = tid; i < 5u * SIZE; i += RF_REDUCE_BLOCK) acc[i] = 0.;
-                __syncthreads();
-                for (unsigned long long i = pos + tid; i < end; i += RF_REDUCE_BLOCK)
-                {
-                    const uint32_t k = keys[i] & (SIZE - 1u);
-                    const double w = vals[i], w2 = w * w, w3 = w2 * w, w4 = w3 * w;
-                    atomicAdd(&acc[k], 1.), atomicAdd(&acc[SIZE + k], w), atomicAdd(&acc[2u * SIZE + k], w2), atomicAdd(&acc[3u * SIZE + k], w3),
-                        atomicAdd(&acc[4u * SIZE + k], w4);
-                }
-                __syncthreads();
-                // (eight lanes per record, five of them add: consecutive addresses of one 64-byte record)
-                for (uint32_t i = tid; i < 8u * SIZE; i += RF_REDUCE_BLOCK)
-                {
-                    const uint32_t k = i >> 3, p = i & 7u;
-                    if (p < 5u && acc[k] != 0. && partBase + k < records) unsafeAtomicAdd(S.stat_acc + ((partBase + k) << 3) + p, acc[p * SIZE + k]);
-                }
-                __syncthreads();
-            }
-            pos = end;
-        }
-    }

@@ -360,8 +360,7 @@
         __shared__ double ckState[2 * 7 * WALKS];
         __shared__ double ckUniform[WALKS];
         const int walkIndex = (int)threadIdx.x / LANES;
-        uint32_t ck = 0u;  // CK_SEL: the slot of the candidate; CK_HASA / CK_HASB; CK_LIN: the uniform branch of the path-length bias
-        constexpr uint32_t CK_SEL = 1u, CK_HASA = 2u, CK_HASB = 4u, CK_LIN = 8u;
+        uint32_t ck = 0u;  // the CK_ flags (pmc_walk.inc, with the decisions: ckptStart, ckptTick, ckptResume)
         const bool checkpoints = force && S.voro_prop_checkpoints != 0 && !EA && !MM;
         double ssca = 0., sabs = 0., tabs = 0.;  // (EA) cross sections of the walk, cumulative absorption optical depth
         double mx[PMC_MAX_MEDIA] = {0., 0., 0., 0.}, msc[PMC_MAX_MEDIA] = {0., 0., 0., 0.}, mab[PMC_MAX_MEDIA] = {0., 0., 0., 0.};  // (MM) per component
@@ -541,17 +540,8 @@
                         if (leader) paths += 1;
                         // the later state that is valid for this depth: nothing before it can be the interaction segment if its depth has not
                         // passed the sampled one
-                        int from = -1;
-                        if (ck & CK_HASB)
-                        {
-                            const int b = (int)(ck & CK_SEL);
-                            if (ckState[(b * 7 + 3) * WALKS + walkIndex] <= target) from = b;
-                        }
-                        if (from < 0 && (ck & CK_HASA))
-                        {
-                            const int a = (int)((ck & CK_SEL) ^ 1u);
-                            if (ckState[(a * 7 + 3) * WALKS + walkIndex] <= target) from = a;
-                        }
+                        const int b = (int)(ck & CK_SEL);
+                        const int from = ckptResume(ck, ckState[((b ^ 1) * 7 + 3) * WALKS + walkIndex], ckState[(b * 7 + 3) * WALKS + walkIndex], target);
                         if (from >= 0)
                         {
                             const double* const p = ckState + from * 7 * WALKS + walkIndex;
@@ -576,7 +566,7 @@
                         {
                             // (the uniforms of this path's sampling wait in the result fields: startCycle)
                             const double u1 = A.sint[slot], u2 = A.nint[slot];
-                            if (S.path_length_bias != 0. && u1 < S.path_length_bias) ck = CK_LIN;
+                            ck = ckptStart(S, u1);
                             if (leader) ckUniform[walkIndex] = u2;
                         }
                     }
@@ -630,31 +620,15 @@
             // ---------------- checkpoints of the pass-1 walks (a wave-uniform tick, every PMC_VPROP_STEPS scan steps)
             if (checkpoints)
             {
+                // (B's depth and the path's uniform wait in LDS)
                 const bool p1 = st == ST_ACTIVE && mode == MODE_PASS1 && tau > 0.;
-                bool save = p1 && !(ck & CK_HASB);
-                if (p1 && (ck & CK_HASB))
+                if (p1 && ckptTick(ck, tau, ckState[((int)(ck & CK_SEL) * 7 + 3) * WALKS + walkIndex], ckUniform[walkIndex]) && leader)
                 {
-                    // B is certain once the lower bound of the sampled depth has passed it: it becomes A, the current state the new B
-                    const double tauB = ckState[((int)(ck & CK_SEL) * 7 + 3) * WALKS + walkIndex];
-                    const double bound = ckUniform[walkIndex] * tau;
-                    const double need = (ck & CK_LIN) ? tauB : tauB * (1. + tau) * (1. + 1e-13);
-                    if (bound >= need)
-                    {
-                        ck = (ck ^ CK_SEL) | CK_HASA;
-                        save = true;
-                    }
-                }
-                if (save)
-                {
-                    if (leader)
-                    {
-                        double* const p = ckState + (int)(ck & CK_SEL) * 7 * WALKS + walkIndex;
-                        p[0 * WALKS] = rx, p[1 * WALKS] = ry, p[2 * WALKS] = rz;
-                        p[3 * WALKS] = tau, p[4 * WALKS] = s;
-                        p[5 * WALKS] = __longlong_as_double((long long)((unsigned long long)(uint32_t)cell | ((unsigned long long)c.run << 32)));
-                        p[6 * WALKS] = __longlong_as_double((long long)(unsigned long long)(uint32_t)lastm);
-                    }
-                    ck |= CK_HASB;
+                    double* const p = ckState + (int)(ck & CK_SEL) * 7 * WALKS + walkIndex;
+                    p[0 * WALKS] = rx, p[1 * WALKS] = ry, p[2 * WALKS] = rz;
+                    p[3 * WALKS] = tau, p[4 * WALKS] = s;
+                    p[5 * WALKS] = __longlong_as_double((long long)((unsigned long long)(uint32_t)cell | ((unsigned long long)c.run << 32)));
+                    p[6 * WALKS] = __longlong_as_double((long long)(unsigned long long)(uint32_t)lastm);
                 }
             }
             // ---------------- scan steps: ROWS groups of entries of the walk's cell each, ROWS entries per lane; the last one of a cell ends its

@@ -1,5 +1,5 @@
 """Plain numpy references of the counting sort and the reduce kernels behind the radiation-field log and the statistics log
-(skirt9_amd/csrc/pmc_walk_tree.inc: rfHistKernel, rfScanKernel, rfScatterKernel, rfReduceKernel, statReduceKernel), and the builders of the
+(skirt9_amd/csrc/pmc_log.inc: rfHistKernel, rfScanKernel, rfScatterKernel, rfReduceKernel, statReduceKernel), and the builders of the
 synthetic logs that tests/test_gpu_log_pipeline.py sends through them (include/pmc_tuning.h: pmc_tune_log_partition, pmc_tune_rf_log_flush,
 pmc_tune_stat_log_flush).  tests/test_log_checks.py checks both on the CPU.
 

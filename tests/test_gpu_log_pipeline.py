@@ -1,4 +1,4 @@
-"""The counting sort and the reduce kernels behind the radiation-field log and the statistics log (skirt9_amd/csrc/pmc_walk_tree.inc:
+"""The counting sort and the reduce kernels behind the radiation-field log and the statistics log (skirt9_amd/csrc/pmc_log.inc:
 rfHistKernel, rfScanKernel, rfScatterKernel, rfReduceKernel, statReduceKernel) on synthetic logs, on the MI355X.
 
 Every radiation-field contribution of an octree run and every statistics contribution passes through these kernels.  The test aids of
