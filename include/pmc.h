@@ -440,7 +440,7 @@ typedef struct pmc_dust_heating
 int pmc_dust_temperatures(pmc_ctx* ctx, const pmc_dust_heating* tables, double* out);
 /* milliseconds in the kernel of the most recent pmc_dust_temperatures on this context (HIP events) */
 int pmc_last_temperature_ms(pmc_ctx* ctx, float* kernel_ms);
-/* number of photon histories kept in flight on the device (default 24 Mi, fewer where the device memory is short; environment PMC_NUM_SLOTS).  The slots are
+/* number of photon histories kept in flight on the device, 1 ... 2^30 (default 24 Mi, fewer where the device memory is short; environment PMC_NUM_SLOTS).  The slots are
    divided into slot groups (default 3; environment PMC_NUM_GROUPS) whose generations run on separate streams */
 int pmc_set_num_slots(pmc_ctx* ctx, int64_t num_slots);
 /* HIP-event timing of the most recent pmc_run_primary: whole segment, sum over its walk-kernel launches, sum over

@@ -120,7 +120,7 @@ int pmc_tune_stat_log_flush(pmc_ctx* ctx, const uint32_t* keys, const double* va
    PMC_ERR_INVALID on a grid without a device numbering. */
 int pmc_tune_cell_numbering(pmc_ctx* ctx, int32_t* ext_out);
 
-/* ---- Test aids: the scalar device functions of the transition, launch and walk kernels (skirt9_amd/csrc/pmc_transition.inc, pmc_walk.inc,
+/* ---- Test aids: the scalar device functions of the transition, launch and walk kernels (skirt9_amd/csrc/pmc_phase.inc, pmc_detect.inc, pmc_launch.inc, pmc_walk.inc,
    pmc_kernels.hip), run over n argument tuples that the HOST supplies, one lane per tuple: the kernels reach some of their branches with one history
    in 10^5 or with none.  The lanes call the functions the kernels call.  Every aid checks its arguments and returns PMC_ERR_INVALID with a message
    instead of launching (a null context or buffer, n < 0 or n > 2^20, an unknown function or kind, a table of fewer than 2 nodes, an instrument or

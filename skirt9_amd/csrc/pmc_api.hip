@@ -290,7 +290,7 @@ int pmc_set_launch(pmc_ctx* ctx, int32_t block, int32_t grid)
 int pmc_set_num_slots(pmc_ctx* ctx, int64_t num_slots)
 {
     if (!ctx) return fail(PMC_ERR_INVALID, "null context");
-    if (num_slots < 64 || num_slots > (int64_t(1) << 30)) return fail(PMC_ERR_INVALID, "num_slots out of range");
+    if (num_slots < 1 || num_slots > (int64_t(1) << 30)) return fail(PMC_ERR_INVALID, "num_slots out of range");
     ctx->numSlots = num_slots;
     ctx->slotsConfigured = true;
     return PMC_OK;

@@ -249,7 +249,7 @@ struct DevSource
 };
 
 // ---- launch flavours: what a scene fixes of SourceSystem::launch, so that its launch kernel holds nothing of what the scene cannot reach
-// (launchHistory, pmc_transition.inc; the kernels are listed once: launchKernels, pmc_kernels.hip).  A flavour is
+// (launchHistory, pmc_launch.inc; the kernels are listed once: launchKernels, pmc_kernels.hip).  A flavour is
 //   PMC_LAUNCH_KIN        some source moves (DevScene::kin)
 // | PMC_LAUNCH_OLIGO      every source is oligochromatic: no SED sampling, no black body, no wavelength bias
 // | PMC_LAUNCH_ISOTROPIC  every source emits isotropically

@@ -10,7 +10,7 @@
 // >70 % of the work is in the walks: a pointer chase through the cell records in HBM / L2 with one dependent gather and
 // about 120-150 f64 instructions per step.  The loop runs over a pool of `num_slots` concurrently live histories whose
 // state lives in HBM (struct of arrays, pmc_device.h SlotArrays), divided into slot groups with a stream each; ONE
-// generation of a group = one scattering cycle of every live slot of the group, and is five kernels (generation 6,
+// generation of a group = one scattering cycle of every live slot of the group, and is these kernels (generation 6,
 // DESIGN.md section 4):
 //
 //   walkPropKernel    (pmc_walk_tree.inc, octree) the propagation walk of every slot: pass 1 over the whole path, the
@@ -24,15 +24,17 @@
 //                     slot one after the other in one lane; voroPeelKernel and voroPropKernel in pmc_walk_voro_run.inc
 //                     take the walks of a Voronoi grid that has tables of runs, two lanes per walk.)
 //   transitionKernel  (pmc_transition.inc) one lane per live slot, every wave working through its own compacted list:
-//                     detection of the cycle's peel-off packets (FluxRecorder::detect: privatised SED bins and a
-//                     claim-once hot-bin table in LDS in front of f64 atomics, per-history statistics lists), the
-//                     interaction the propagation walk found (weights, termination), HG scattering from the slot's
-//                     Philox stream keyed by (seed, history index) (include/pmc_philox.h), and the start state of every
-//                     walk of the next cycle (task records, pmc_device.h TaskArrays).
-//   endedScanKernel   exclusive scan of the per-tile counts of histories that ended: the history index a slot takes up
-//                     next is a pure function of the slot order.
-//   launchKernel      one lane per ended history: flush of its statistics list, SourceSystem::launch of the next
-//                     history, first cycle.
+//                     detection of the cycle's peel-off packets (FluxRecorder::detect, pmc_detect.inc: privatised SED bins
+//                     and a claim-once hot-bin table in LDS in front of f64 atomics, per-history statistics lists), the
+//                     interaction the propagation walk found (weights, termination), HG scattering (pmc_phase.inc) from the
+//                     slot's Philox stream keyed by (seed, history index) (include/pmc_philox.h), and which observers get a
+//                     peel-off packet in the next cycle (announceCycle, pmc_cycle.inc).
+//   endedScanKernel   (pmc_transition.inc) exclusive scan of the per-tile counts of histories that ended: the history index
+//                     a slot takes up next is a pure function of the slot order.
+//   launchKernel      (pmc_launch.inc) one lane per ended history: flush of its statistics list, SourceSystem::launch of
+//                     the next history, first cycle.
+//   cycleStartKernel  (pmc_cycle.inc) the start state of every walk of the cycle that a live slot is about to begin (task
+//                     records, pmc_device.h TaskArrays), with the counting sort that orders them (peelSort*Kernel).
 //
 // The host enqueues generations until no slot is alive (pmc_api.hip); one 8-byte readback per generation and group tells
 // it when a group is done, and the kernels of the other groups keep the device busy meanwhile.
@@ -271,7 +273,11 @@ namespace
 #include "pmc_walk_voro_run.inc"
 #include "pmc_walk_tree.inc"
 #include "pmc_log.inc"
+#include "pmc_phase.inc"
+#include "pmc_detect.inc"
+#include "pmc_cycle.inc"
 #include "pmc_transition.inc"
+#include "pmc_launch.inc"
 #include "pmc_ray.inc"
 }
 

@@ -923,7 +923,7 @@ namespace
     int checkKernelErrors(pmc_ctx* ctx)
     {
         const unsigned long long* ctr = ctx->dev.counters;
-        // internal errors (a sorted peel-off record without a place: see peelTile, pmc_transition.inc)
+        // internal errors (a sorted peel-off record without a place: see peelTile, pmc_cycle.inc)
         {
             unsigned long long tail[3] = {0, 0, 0};  // counters 5 .. 7
             HIP_TRY(hipMemcpy(tail, ctr + 5, sizeof(tail), hipMemcpyDeviceToHost));

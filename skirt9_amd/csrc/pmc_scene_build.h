@@ -449,7 +449,7 @@ namespace
     }
 
     // ---- LDS plan (in doubles from the start of dynamic LDS; DevScene::lds_*).  Walk kernels and cycle start kernel: the grid tables, at offset 0.
-    // Transition and launch kernels: no grid tables; privatised SED blocks, hot-bin table (pmc_transition.inc HOT_BINS keys + values), integer scratch
+    // Transition and launch kernels: no grid tables; privatised SED blocks, hot-bin table (pmc_detect.inc HOT_BINS keys + values), integer scratch
     // (regrouping arrays and list-append counters).  Launch kernel only, behind the regions the two share: Sersic tables, then the index borders of
     // the dust mix (DustMix::_lambdav: the binary search of every new history's wavelength) if they fit
     struct LdsPlan

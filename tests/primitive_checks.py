@@ -1,4 +1,4 @@
-"""References of the scalar device functions that the photon loop reaches rarely (skirt9_amd/csrc/pmc_transition.inc, pmc_walk.inc,
+"""References of the scalar device functions that the photon loop reaches rarely (skirt9_amd/csrc/pmc_phase.inc, pmc_detect.inc, pmc_launch.inc, pmc_walk.inc,
 pmc_kernels.hip), the argument lists that reach every branch of them, and the rule by which tests/test_gpu_primitives.py accepts what the
 device functions return (include/pmc_tuning.h: pmc_tune_device_function, pmc_tune_locate, pmc_tune_detector, pmc_tune_wavelength_bins,
 pmc_tune_angular_probabilities).  tests/test_primitive_checks.py checks all of it on the CPU.

@@ -1,5 +1,5 @@
 """Electron media on the GPU (run with `pytest -m gpu`): Thomson scattering with the dipole phase function in the transition kernel
-(skirt9_amd/csrc/pmc_transition.inc PhaseDipole), alone and next to dust components.
+(skirt9_amd/csrc/pmc_phase.inc PhaseDipole), alone and next to dust components.
 
 The CPU oracle (oracle/life_cycle.cpp) has no dipole: it reads an electron component as an isotropic scatterer with the same opacities.
 So the oracle pins everything the phase function cannot touch, and -- where all first scatterings share one incoming direction -- the

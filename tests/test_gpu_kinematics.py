@@ -1,5 +1,5 @@
 """Moving sources on the GPU (run with `pytest -m gpu`): the Doppler shift of what a source with a bulk velocity emits
-(skirt9_amd/csrc/pmc_transition.inc launchHistory, startCycleWalks, onCycleDone: the kinematic flavours of the launch, cycle start and
+(skirt9_amd/csrc/pmc_launch.inc launchHistory, pmc_cycle.inc startCycleWalks, pmc_transition.inc onCycleDone: the kinematic flavours of the launch, cycle start and
 transition kernels).
 
 The CPU oracle (oracle/life_cycle.cpp) has no Doppler shift.  It is used through an identity: a source whose velocity v is the same for all

@@ -36,15 +36,16 @@ def _sim(path, n):
     return _sims[key]
 
 
-def _reference(path, first, n, seed, rf=False):
-    """oracle frames (and field) of histories [first, first + n) of the scene at `path`: once per module, whatever the slot count"""
-    key = (path, first, n, seed, rf)
+def _reference(path, first, n, seed, rf=False, ext=False):
+    """oracle frames (and field) of histories [first, first + n) of the scene at `path`: once per module, whatever the slot count
+    (ext: the oracle follows the scene's dipole phase functions and moving sources, oracle_lib.run_primary)"""
+    key = (path, first, n, seed, rf, ext)
     if key not in _oracle:
         sim = _sim(path, n)
         if rf:
-            _oracle[key] = O.run_primary_rf(sim, first, n, O.RNG_PHILOX, seed=seed)
+            _oracle[key] = O.run_primary_rf(sim, first, n, O.RNG_PHILOX, seed=seed, ext=ext)
         else:
-            frames, counters = O.run_primary(sim, first, n, O.RNG_PHILOX, seed=seed)
+            frames, counters = O.run_primary(sim, first, n, O.RNG_PHILOX, seed=seed, ext=ext)
             _oracle[key] = (frames, None, counters)
     return _oracle[key]
 
@@ -77,7 +78,8 @@ def _check_pool(eng, name, slots, n):
     assert eng.last_timing()["generations"] >= n / slots
 
 
-def _run_and_compare(path, name, n, slots, first=0, seed=SEED):
+def _run_and_compare(path, name, n, slots, first=0, seed=SEED, ext=False, two_bins_per_history=False):
+    """returns the engine's frames and counters"""
     sim = _sim(path, n)
     eng = _engine(sim, slots)
     eng.run_primary(first, n, seed)
@@ -85,9 +87,10 @@ def _run_and_compare(path, name, n, slots, first=0, seed=SEED):
     c = eng.counters()
     _check_pool(eng, name, slots, n)
     eng.close()
-    ref, _, counters = _reference(path, first, n, seed)
+    ref, _, counters = _reference(path, first, n, seed, ext=ext)
     _check_counters(c, counters, n)
-    _compare_frames(sim, gpu, ref, n)
+    _compare_frames(sim, gpu, ref, n, two_bins_per_history=two_bins_per_history)
+    return gpu, c
 
 
 SCENES = [("cfg1.ski", 20000), ("cfg1mesh2.ski", 20000), ("cfg1nf.ski", 50000), ("cfg1nfea.ski", 50000), ("cfg1laser.ski", 20000),
