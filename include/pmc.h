@@ -27,6 +27,8 @@
  *                        secondary dust emission source
  *   pmc_sampler_*     <- ParticleSnapshot::density(Position) evaluated for the sample positions of the setup phase
  *                        (ParticleSnapshot.cpp:233-243; DensityTreePolicy.cpp:141, MediumSystem.cpp:91-96)
+ *   pmc_sample_cells  <- SpatialGrid::cellIndex(Position) for many positions and the cell values there: ProbeFormBridge::valuesAtPosition,
+ *                        the operation behind every cut form of a probe (ProbeFormBridge.cpp, PlanarCutsForm.cpp)
  *   pmc_counters      <- no reference counterpart: counted cell visits / detector updates for the roofline
  *
  * Conventions: plain C, no exceptions cross the boundary; every function returns PMC_OK (0) or a negative
@@ -409,6 +411,18 @@ int pmc_last_integrate_work(pmc_ctx* ctx, float* kernel_ms, uint64_t* lane_steps
    call too.  The device keeps the weight and PMC_INTEGRATE_PASS_VALUES - 1 values per pass. */
 int pmc_integrate_weighted_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, const double* directions, int32_t num_values,
                                 const double* cell_weights, const double* cell_values, double* sums);
+/* ProbeFormBridge::valuesAtPosition for grid quantities: cells[p] = SpatialGrid::cellIndex(positions[p]) in the numbering pmc_trace_ray reports
+   (-1 outside), values[v * num_points + p] = cell_values[v * num_cells + cells[p]], 0 outside.  All host pointers; positions [num_points][3];
+   num_points may be 0; num_values may be 0 (cells only; cell_values and values NULL); cells may be NULL.  Non-finite coordinates: PMC_ERR_INVALID.
+   cellIndex is not the start of a ray: the domain box is closed, a position on a wall shared by two cells belongs to the upper one, a position
+   on the outer upper wall to the last cell (TreeNode.cpp:66-76, OctTreeNode.cpp:37-42, BinTreeNode.cpp:53-62; CartesianSpatialGrid.cpp:60-69 with
+   NR::locateFail; VoronoiMeshSnapshot.cpp:1006-1040).  The values are copies of the caller's doubles: a unit factor belongs in cell_values.
+   The points pass through the device in chunks of PMC_SAMPLE_CHUNK_POINTS, which bounds the device memory of a call; the cells of a chunk are
+   located once and the values read there in passes of PMC_INTEGRATE_PASS_VALUES. */
+#define PMC_SAMPLE_CHUNK_POINTS (1 << 20)
+int pmc_sample_cells(pmc_ctx* ctx, int64_t num_points, const double* positions, int32_t num_values, const double* cell_values,
+                     double* values, int32_t* cells);
+int pmc_last_sample_ms(pmc_ctx* ctx, float* kernel_ms);   /* HIP events around the kernels of the most recent call */
 
 /* ---------------------------------------------------------------- dust temperatures ---- */
 

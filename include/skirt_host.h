@@ -116,6 +116,31 @@ int skh_write_probes_with(const skh_simulation* sim, const skh_probe_engine* eng
    a caller that keeps the table on the device copies it to the host only then */
 int32_t skh_probes_need_radiation_field(const skh_simulation* sim, int32_t when);
 
+/* ConvergenceInfoProbe (ConvergenceInfoProbe.cpp): <prefix>_<probe>_convergence.dat -- per material type the input and the gridded mass and
+   optical depth along the coordinate axes at the probe's wavelength, then the optical depths of the cells' diagonals -- is written by every
+   skh_write_probes* function; its gridded optical depths are six rays per material type through `integrate`, without which it fails.
+   ConvergenceCutsProbe (ConvergenceCutsProbe.cpp, DefaultCutsForm.cpp, PlanarCutsForm::writePlanarCut): per material type present the true
+   density <prefix>_<probe>_dust_t_xy.fits / _elec_t_xy.fits -- the media's own density at 1024 x 1024 positions over the grid's bounding box in
+   the plane z = 0, computed by the host -- and the gridded density _dust_g_xy.fits / _elec_g_xy.fits -- the value of the cell that holds each
+   position; the plane y = 0 (_xz) when skh_dimension is 2 or 3 and the plane x = 0 (_yz) when it is 3.  The gridded cuts come from a point
+   sampler handed over at run time -- libpmc.so's pmc_sample_cells with user = the pmc_ctx (the `user` of `engine`) -- so that this library does
+   not link the engine.  skh_write_probes_sampled is skh_write_probes_with plus the sampler; `engine` may be NULL or hold NULL members for what
+   the ski file's probes do not need (the sampler's user is engine->user).  Without a sampler -- also through skh_write_probes,
+   skh_write_probes_when and skh_write_probes_with -- a ski file with a ConvergenceCutsProbe that is due fails with "needs a sampler": the files
+   are never left out silently and never computed on the CPU instead. */
+typedef int (*skh_sample_fn)(void* user, int64_t num_points, const double* positions, int32_t num_values, const double* cell_values, double* values,
+                             int32_t* cells);
+int skh_write_probes_sampled(const skh_simulation* sim, const skh_probe_engine* engine, skh_sample_fn sample, const char* outdir, int32_t when);
+/* MediumSystem::dimension (MediumSystem.cpp:403-408): 1 spherical, 2 axisymmetric, 3 neither -- the largest of the medium components */
+int32_t skh_dimension(const skh_simulation* sim);
+
+/* SpatialGrid::cellIndex(Position) of the simulation's grid for many positions [num_points][3] (valid after skh_setup): cells[p] = the cell
+   that holds positions[p] in the numbering of pmc_trace_ray, -1 outside the grid.  A literal restatement of the reference's functions
+   (TreeNode::leafChild with OctTreeNode::child / BinTreeNode::child; NR::locateFail per axis of a Cartesian grid; the nearest site of a
+   Voronoi mesh), on one thread: the domain box is closed and a position on a wall between two cells belongs to the upper one.  It is the CPU
+   yardstick of pmc_sample_cells, as skh_dust_temperatures is of pmc_dust_temperatures. */
+int skh_cell_indices(const skh_simulation* sim, int64_t num_points, const double* positions, int32_t* cells);
+
 /* A set-up scene as ONE file: everything pmc_create reads plus the numbers a driver of the photon loop needs.  In a job of
    one process per GPU, one process sets the simulation up (all host cores) and saves it, the others load it instead of
    repeating the setup -- the reference repeats Simulation::setupSimulation in every MPI process.  A loaded scene serves

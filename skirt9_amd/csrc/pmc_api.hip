@@ -688,4 +688,122 @@ int pmc_last_integrate_work(pmc_ctx* ctx, float* kernel_ms, uint64_t* lane_steps
     return PMC_OK;
 }
 
+// the point sampler (pmc_locate.inc): the points go through the device in chunks of PMC_SAMPLE_CHUNK_POINTS, located once per chunk, the values
+// gathered in passes of PMC_INTEGRATE_PASS_VALUES at the cells of the chunk.  Device memory of a call: 3 + PMC_INTEGRATE_PASS_VALUES doubles and two
+// int32 per point of a chunk (64 MiB), and one pass of cell values
+int pmc_sample_cells(pmc_ctx* ctx, int64_t num_points, const double* positions, int32_t num_values, const double* cell_values, double* values,
+                     int32_t* cells)
+{
+    if (!ctx) return fail(PMC_ERR_INVALID, "null context");
+    if (num_points < 0) return fail(PMC_ERR_INVALID, "pmc_sample_cells: negative number of points");
+    if (num_values < 0) return fail(PMC_ERR_INVALID, "pmc_sample_cells: negative number of values");
+    if (num_points > 0 && !positions) return fail(PMC_ERR_INVALID, "pmc_sample_cells: null positions");
+    if (num_values > 0 && !cell_values) return fail(PMC_ERR_INVALID, "pmc_sample_cells: null cell values");
+    if (num_points > 0 && num_values > 0 && !values) return fail(PMC_ERR_INVALID, "pmc_sample_cells: null result array");
+    ctx->sampleMs = 0.f;
+    for (size_t i = 0, n = 3 * size_t(num_points); i < n; ++i)
+        if (!std::isfinite(positions[i]))
+            return fail(PMC_ERR_INVALID, "pmc_sample_cells: coordinate " + std::to_string(i % 3) + " of point " + std::to_string(i / 3) + " is not finite");
+    if (num_points == 0 || (num_values == 0 && !cells)) return PMC_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->sceneDirty)
+    {
+        HIP_TRY(pmcUploadScene(ctx->slot, &ctx->dev, ctx->stream));
+        ctx->sceneDirty = false;
+    }
+    const DevScene& D = ctx->dev;
+    constexpr int W = PMC_INTEGRATE_PASS_VALUES;
+    const size_t numCells = size_t(D.num_cells);
+    // the cell values renumbered and interleaved as pmc_integrate_rays uploads them: one record [W] per cell of the walk kernels' numbering
+    const bool renumbered = D.grid_kind == PMC_GRID_OCTREE || D.grid_kind == PMC_GRID_BINTREE;
+    const size_t slots = renumbered ? size_t(D.cell_slots) : numCells;
+    std::vector<int32_t> ext;
+    if (renumbered && num_values > 0)
+    {
+        ext.resize(slots);
+        HIP_TRY(hipMemcpy(ext.data(), D.cell_ext, slots * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int32_t m : ext)
+            if (m >= D.num_cells) return fail(PMC_ERR_DEVICE, "pmc_sample_cells: cell numbering table out of range");
+    }
+    const int64_t chunkMax = PMC_SAMPLE_CHUNK_POINTS;
+    const size_t chunkRoom = size_t(std::min(num_points, chunkMax));
+    CallBuffers scratch;
+    double *dPositions = nullptr, *dQ = nullptr, *dValues = nullptr;
+    int32_t *dWalkCells = nullptr, *dCells = nullptr;
+    HIP_TRY(scratch.get(3 * chunkRoom, &dPositions));
+    HIP_TRY(scratch.get(chunkRoom, &dWalkCells));
+    HIP_TRY(scratch.get(chunkRoom, &dCells));
+    if (num_values > 0)
+    {
+        HIP_TRY(scratch.get(slots * W, &dQ));
+        HIP_TRY(scratch.get(W * chunkRoom, &dValues));
+    }
+    hipEvent_t evA = nullptr, evB = nullptr;
+    HIP_TRY(hipEventCreate(&evA));
+    if (hipError_t e = hipEventCreate(&evB); e != hipSuccess)
+    {
+        hipEventDestroy(evA);
+        return hipFail(e, "hipEventCreate");
+    }
+    const auto timed = [&](hipError_t launched) {
+        hipError_t e = launched;
+        if (e == hipSuccess) e = hipEventRecord(evB, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        float ms = 0.f;
+        if (e == hipSuccess && hipEventElapsedTime(&ms, evA, evB) == hipSuccess) ctx->sampleMs += ms;
+        return e;
+    };
+    const int numPasses = (num_values + W - 1) / W;
+    const size_t numChunks = size_t((num_points + chunkMax - 1) / chunkMax);
+    // the records of every pass, built once on the host; with one pass they are uploaded once, with several once per chunk and pass (the
+    // located cells of a chunk stay on the device for its passes, which is what bounds the device memory)
+    std::vector<double> q(size_t(numPasses) * slots * W), part(num_values > 0 ? W * chunkRoom : 0);
+    for (int pass = 0; pass < numPasses; ++pass)
+    {
+        const int v0 = pass * W, nv = std::min(W, num_values - v0);
+        double* record = q.data() + size_t(pass) * slots * W;
+        for (size_t c = 0; c < slots; ++c)
+        {
+            const int64_t m = renumbered ? int64_t(ext[c]) : int64_t(c);
+            for (int j = 0; j < W; ++j) record[c * W + j] = (j < nv && m >= 0) ? cell_values[size_t(v0 + j) * numCells + size_t(m)] : 0.;
+        }
+    }
+    hipError_t e = hipSuccess;
+    for (size_t chunk = 0; chunk < numChunks && e == hipSuccess; ++chunk)
+    {
+        const size_t first = chunk * size_t(chunkMax);
+        const size_t n = std::min(size_t(chunkMax), size_t(num_points) - first);
+        // the locate kernel stages the grid tables per workgroup: no more workgroups than the CUs hold at once, no more than the points fill
+        const int grid = int(std::max<size_t>(1, std::min<size_t>((n + 255) / 256, size_t(ctx->numCU) * 4)));
+        e = hipMemcpy(dPositions, positions + 3 * first, 3 * n * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipEventRecord(evA, ctx->stream);
+        if (e == hipSuccess)
+            e = timed(pmcLaunchLocateCells(ctx->slot, D.grid_kind, ctx->wide, dPositions, dWalkCells, dCells, n, grid, ctx->walkLds, ctx->stream));
+        if (e == hipSuccess && cells) e = hipMemcpy(cells + first, dCells, n * sizeof(int32_t), hipMemcpyDeviceToHost);
+        for (int pass = 0; pass < numPasses && e == hipSuccess; ++pass)
+        {
+            const int v0 = pass * W, nv = std::min(W, num_values - v0);
+            if (chunk == 0 || numPasses > 1)
+                e = hipMemcpy(dQ, q.data() + size_t(pass) * slots * W, slots * W * sizeof(double), hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipEventRecord(evA, ctx->stream);
+            if (e == hipSuccess) e = timed(pmcLaunchGatherCells(dWalkCells, dQ, dValues, n, nv, int((n + 255) / 256), ctx->stream));
+            if (e == hipSuccess) e = hipMemcpy(part.data(), dValues, size_t(nv) * n * sizeof(double), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) break;
+            for (int j = 0; j < nv; ++j) std::memcpy(values + size_t(v0 + j) * size_t(num_points) + first, part.data() + size_t(j) * n, n * sizeof(double));
+        }
+    }
+    hipEventDestroy(evA);
+    hipEventDestroy(evB);
+    if (e != hipSuccess) return hipFail(e, "pmc_sample_cells");
+    return PMC_OK;
+}
+
+int pmc_last_sample_ms(pmc_ctx* ctx, float* kernel_ms)
+{
+    if (!ctx) return fail(PMC_ERR_INVALID, "null context");
+    if (kernel_ms) *kernel_ms = ctx->sampleMs;
+    return PMC_OK;
+}
+
 }  // extern "C"

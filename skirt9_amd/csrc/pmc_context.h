@@ -83,6 +83,10 @@ extern "C" hipError_t pmcLaunchTrace(int slot, int gridKind, int wide, int unifo
 extern "C" int pmcProbeWorkWords(void);
 extern "C" hipError_t pmcLaunchIntegrate(int slot, int gridKind, int wide, int averaged, const double* origins, const double* directions, const double* q,
                                          double* sums, unsigned long long numRays, unsigned long long* work, int grid, size_t ldsBytes, hipStream_t stream);
+extern "C" hipError_t pmcLaunchLocateCells(int slot, int gridKind, int wide, const double* positions, int32_t* walkCells, int32_t* cells,
+                                           unsigned long long numPoints, int grid, size_t ldsBytes, hipStream_t stream);
+extern "C" hipError_t pmcLaunchGatherCells(const int32_t* walkCells, const double* q, double* values, unsigned long long numPoints, int numValues, int grid,
+                                           hipStream_t stream);
 
 namespace
 {
@@ -130,6 +134,7 @@ struct pmc_ctx final : TableSink
     float integrateMs{0};
     unsigned long long integrateLaneSteps{0}, integrateWaveSteps{0};
     float temperatureMs{0};  // kernel of the most recent pmc_dust_temperatures (pmc_last_temperature_ms)
+    float sampleMs{0};       // kernels of the most recent pmc_sample_cells (pmc_last_sample_ms)
     DevScene dev{};
     std::vector<void*> allocations;
     std::vector<void*> slotAllocations;
@@ -249,7 +254,7 @@ struct pmc_ctx final : TableSink
     }
 };
 
-// device buffers of one call (pmc_trace_ray, pmc_integrate_rays, pmc_dust_temperatures): freed when the call returns, whichever way
+// device buffers of one call (pmc_trace_ray, pmc_integrate_rays, pmc_sample_cells, pmc_dust_temperatures): freed when the call returns, whichever way
 struct CallBuffers
 {
     std::vector<void*> owned;

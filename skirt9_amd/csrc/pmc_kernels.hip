@@ -41,7 +41,8 @@
 //
 // Outside the photon loop, pmc_ray.inc runs single rays through the same traversal code: one ray cursor (rayStart, rayAdvance) under
 // traceRayKernel (pmc_trace_ray: the (m, ds) of one ray, for the bit-exact check) and integrateRaysKernel (pmc_integrate_rays: one ray per lane,
-// the probe maps' line integrals).
+// the probe maps' line integrals).  pmc_locate.inc answers SpatialGrid::cellIndex for many positions (pmc_sample_cells: locateCellsKernel, then
+// gatherCellsKernel for the cell values there).
 //
 // The reference stores the whole path (<= 1000 x 40 B per thread) and binary-searches the interaction point
 // (SpatialGridPath.cpp:164-206).  Here the path is walked twice with bit-identical arithmetic instead: pass 1 yields
@@ -279,6 +280,7 @@ namespace
 #include "pmc_transition.inc"
 #include "pmc_launch.inc"
 #include "pmc_ray.inc"
+#include "pmc_locate.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -365,6 +367,12 @@ static const auto integrateWeightedKernels = flavourTable<5>([](auto f) {
     constexpr int F = decltype(f)::value;
     return KernelFlavour<IntegrateKernel>{integrateRaysKernel<RAY_GRIDS[F], F == 1, true>, 0};
 });
+// the point sampler (pmc_locate.inc, pmc_sample_cells)
+typedef void (*LocateKernel)(int, LocateArgs);
+static const auto locateKernels = flavourTable<5>([](auto f) {
+    constexpr int F = decltype(f)::value;
+    return KernelFlavour<LocateKernel>{locateCellsKernel<RAY_GRIDS[F], F == 1>, 0};
+});
 // launch kernel: the launch flavour (pmc_device.h PMC_LAUNCH_*, pmcLaunchFlavourOf); flavour 0 (| PMC_LAUNCH_KIN) is the generic kernel
 typedef void (*LaunchKernel)(int, int, int, int, uint64_t, uint64_t, uint64_t, int, StatLogArgs);
 static const auto launchKernels = flavourTable<PMC_LAUNCH_FLAVOURS>([](auto f) {
@@ -415,7 +423,7 @@ extern "C" hipError_t pmcConfigureKernels(size_t walkLds, size_t transitionLds)
     }
     for (hipError_t e : {raiseLdsLimits(peelKernels, walkMax), raiseLdsLimits(peel2Kernels, walkMax), raiseLdsLimits(propKernels, walkMax),
                          raiseLdsLimits(walkKernels, walkMax), raiseLdsLimits(binWalkKernels, walkMax), raiseLdsLimits(traceKernels, walkMax),
-                         raiseLdsLimits(integrateKernels, walkMax), raiseLdsLimits(integrateWeightedKernels, walkMax)})
+                         raiseLdsLimits(integrateKernels, walkMax), raiseLdsLimits(integrateWeightedKernels, walkMax), raiseLdsLimits(locateKernels, walkMax)})
         if (e != hipSuccess) return e;
     const struct
     {
@@ -874,5 +882,21 @@ extern "C" hipError_t pmcLaunchIntegrate(int slot, int gridKind, int wide, int a
     const ProbeArgs A = {origins, directions, q, sums, numRays, work};
     const IntegrateKernel kernel = (averaged ? integrateWeightedKernels : integrateKernels)[rayKernelIndex(gridKind, wide)].kernel;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), ldsBytes, stream, slot, A);
+    return hipGetLastError();
+}
+
+// the point sampler (pmc_locate.inc): the cells of numPoints positions, in the walk kernels' numbering and in the caller's ...
+extern "C" hipError_t pmcLaunchLocateCells(int slot, int gridKind, int wide, const double* positions, int32_t* walkCells, int32_t* cells,
+                                           unsigned long long numPoints, int grid, size_t ldsBytes, hipStream_t stream)
+{
+    const LocateArgs A = {positions, walkCells, cells, numPoints};
+    hipLaunchKernelGGL(locateKernels[rayKernelIndex(gridKind, wide)].kernel, dim3(grid), dim3(256), ldsBytes, stream, slot, A);
+    return hipGetLastError();
+}
+// ... and one pass of numValues <= PMC_INTEGRATE_PASS_VALUES values read at them: values [numValues][numPoints], q as for pmcLaunchIntegrate
+extern "C" hipError_t pmcLaunchGatherCells(const int32_t* walkCells, const double* q, double* values, unsigned long long numPoints, int numValues, int grid,
+                                           hipStream_t stream)
+{
+    hipLaunchKernelGGL(gatherCellsKernel, dim3(grid), dim3(256), 0, stream, walkCells, q, values, numPoints, numValues);
     return hipGetLastError();
 }

@@ -18,7 +18,8 @@ _LIBDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 SYMBOLS = ["pmc_abi_version", "pmc_build_info", "pmc_last_error", "pmc_frame_layout_of", "pmc_create", "pmc_create_ext", "pmc_destroy", "pmc_bind_frames",
            "pmc_clear_frames", "pmc_run_primary", "pmc_set_progress", "pmc_sync", "pmc_download", "pmc_frames_device", "pmc_frames_size",
            "pmc_last_kernel_ms", "pmc_counters", "pmc_reset_counters", "pmc_trace_ray", "pmc_integrate_rays",
-           "pmc_last_integrate_work", "pmc_integrate_weighted_rays", "pmc_dust_temperatures", "pmc_last_temperature_ms", "pmc_set_launch",
+           "pmc_last_integrate_work", "pmc_integrate_weighted_rays", "pmc_sample_cells", "pmc_last_sample_ms", "pmc_dust_temperatures",
+           "pmc_last_temperature_ms", "pmc_set_launch",
            "pmc_set_num_slots", "pmc_last_timing", "pmc_last_walk_timing", "pmc_walk_work", "pmc_radiation_field_size", "pmc_radiation_field_device",
            "pmc_download_radiation_field", "pmc_clear_radiation_field", "pmc_bind_radiation_field", "pmc_sampler_create",
            "pmc_sampler_density", "pmc_sampler_destroy", "pmc_history_range", "pmc_comm_init_all", "pmc_comm_unique_id",
@@ -114,6 +115,9 @@ def lib():
             L.pmc_integrate_weighted_rays.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
             L.pmc_dust_temperatures.argtypes = [C.c_void_p, C.POINTER(DustHeating), C.c_void_p]
             L.pmc_last_temperature_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        if hasattr(L, "pmc_sample_cells"):  # (likewise)
+            L.pmc_sample_cells.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.pmc_last_sample_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.pmc_set_launch.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.pmc_set_num_slots.argtypes = [C.c_void_p, C.c_int64]
         L.pmc_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -169,6 +173,8 @@ def lib():
 # settings the library itself reads from the environment (include/pmc.h); every other PMC_* name is a tuning switch
 # values whose sums pmc_integrate_rays keeps in registers per pass over the rays (include/pmc.h PMC_INTEGRATE_PASS_VALUES)
 INTEGRATE_PASS_VALUES = 4
+# points that pmc_sample_cells keeps on the device at a time (include/pmc.h PMC_SAMPLE_CHUNK_POINTS)
+SAMPLE_CHUNK_POINTS = 1 << 20
 
 ENVIRONMENT_SETTINGS = ("PMC_NUM_SLOTS", "PMC_NUM_GROUPS", "PMC_STAT_POOL_BLOCKS")
 
@@ -633,6 +639,44 @@ class Engine:
         if not hasattr(lib(), "pmc_integrate_weighted_rays"):  # (an engine built from an older commit and loaded through PMC_LIBRARY)
             return None, self._h
         return C.cast(lib().pmc_integrate_weighted_rays, C.c_void_p).value, self._h
+
+    def sample_cells(self, positions, cell_values=None, cells=True):
+        """(values, cells) at the positions [n][3] (pmc_sample_cells: the point sampler behind the cut forms of the probes).  cells[p] =
+        SpatialGrid::cellIndex(positions[p]) in the numbering ``trace_ray`` reports, -1 outside the grid: the domain box is closed and a position on
+        a wall between two cells belongs to the upper one.  values[v, p] = cell_values[v, cells[p]], 0 outside, copied bit for bit;
+        cell_values: [V][num_cells], or [num_cells] (then values is [n]), or None (cells only: values is None).  cells=False: the call gets no array
+        for the cells (NULL) and None is returned for them"""
+        r = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        n = r.shape[0]
+        single = False
+        q = out = None
+        if cell_values is not None:
+            q = np.ascontiguousarray(cell_values, dtype=np.float64)
+            single = q.ndim == 1
+            q = q.reshape(1, -1) if single else q
+            if q.ndim != 2:
+                raise ValueError("cell_values must be [V][num_cells]")
+            if q.shape[0] and q.shape[1] != self.num_cells:
+                raise ValueError(f"cell_values has {q.shape[1]} cells per value, the grid has {self.num_cells}")
+            out = np.zeros((q.shape[0], n), dtype=np.float64)
+        m = np.full(n, -2, dtype=np.int32) if cells else None
+        num_values = q.shape[0] if q is not None else 0
+        _check(lib().pmc_sample_cells(self._h, n, r.ctypes.data_as(C.c_void_p), num_values,
+                                      q.ctypes.data_as(C.c_void_p) if num_values else None, out.ctypes.data_as(C.c_void_p) if num_values else None,
+                                      m.ctypes.data_as(C.c_void_p) if cells else None))
+        if out is not None and single:
+            out = out[0].copy()
+        return out, m
+
+    def sample_callback(self):
+        """``sample_cells`` as a C callback for the host layer's cut forms: (address of pmc_sample_cells, user pointer = the context)"""
+        return C.cast(lib().pmc_sample_cells, C.c_void_p).value, self._h
+
+    def last_sample_ms(self):
+        """milliseconds in the kernels of the most recent sample_cells (HIP events)"""
+        ms = C.c_float(0)
+        _check(lib().pmc_last_sample_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def dust_temperatures(self, tables):
         """[H + 1][num_cells]: the equilibrium temperature of every dust component in every cell and their mass-weighted mean

@@ -101,6 +101,11 @@ INTEGRATE_WEIGHTED_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.
 TEMPERATURE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double))
 
 
+# skh_sample_fn (include/skirt_host.h)
+SAMPLE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                        C.POINTER(C.c_int32))
+
+
 class DustHeating(C.Structure):
     """pmc_dust_heating (include/pmc.h)"""
     _fields_ = [("num_components", C.c_int32), ("num_lambda", C.c_int32), ("num_temperatures", C.c_int32), ("num_cells", C.c_int32),
@@ -210,6 +215,10 @@ def lib():
         L.skh_probes_need_radiation_field.restype = C.c_int32
         L.skh_probes_need_radiation_field.argtypes = [C.c_void_p, C.c_int32]
         L.skh_write_probes_with.argtypes = [C.c_void_p, C.POINTER(ProbeEngine), C.c_char_p, C.c_int32]
+        L.skh_cell_indices.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.skh_write_probes_sampled.argtypes = [C.c_void_p, C.POINTER(ProbeEngine), C.c_void_p, C.c_char_p, C.c_int32]
+        L.skh_dimension.restype = C.c_int32
+        L.skh_dimension.argtypes = [C.c_void_p]
         L.skh_dust_heating.argtypes = [C.c_void_p, C.POINTER(DustHeating)]
         L.skh_dust_components.restype = C.c_int32
         L.skh_dust_components.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
@@ -360,6 +369,25 @@ class Simulation:
                          "averaged": L.skh_probe_map_averaged(self._h, index) == 1, "origins": origins, "directions": directions, "cell_values": values})
         return maps
 
+    def cell_indices(self, positions):
+        """SpatialGrid::cellIndex of the positions [n][3] (skh_cell_indices): the cell that holds each, in the numbering ``Engine.trace_ray``
+        reports, -1 outside the grid; a position on a wall between two cells belongs to the upper one.  The CPU restatement, on one thread, of
+        ``Engine.sample_cells``"""
+        import numpy as np
+        assert self._setup, "call setup() first"
+        r = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        out = np.full(r.shape[0], -2, dtype=np.int32)
+        if lib().skh_cell_indices(self._h, r.shape[0], r.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError(lib().skh_last_error().decode())
+        return out
+
+    def dimension(self):
+        """MediumSystem::dimension: 1 spherical, 2 axisymmetric, 3 neither -- the largest over the medium components (skh_dimension)"""
+        n = lib().skh_dimension(self._h)
+        if n < 0:
+            raise RuntimeError(lib().skh_last_error().decode())
+        return int(n)
+
     def dust_components(self):
         """the medium components that are dust, in order: the rows of ``temperature_tables`` and ``dust_temperatures`` (empty unless the
         simulation is panchromatic, stores the radiation field and has dust)"""
@@ -394,7 +422,7 @@ class Simulation:
             raise RuntimeError(lib().skh_last_error().decode())
         return out
 
-    def write_probes(self, outdir, integrator=None, when=None, weighted=None, temperatures=None, rf=None):
+    def write_probes(self, outdir, integrator=None, when=None, weighted=None, temperatures=None, rf=None, sampler=None):
         """write the probe files into outdir.  integrator: an ``Engine`` (its pmc_integrate_rays, pmc_integrate_weighted_rays and
         pmc_dust_temperatures are handed to the host library as C functions: rays and tables never pass through Python; only when a
         TemperatureProbe or DustAbsorptionPerCellProbe is among the probes written is the radiation field table downloaded from it, unless rf
@@ -403,7 +431,10 @@ class Simulation:
         maps need `weighted`, a callable (origins, directions, cell_weights [num_cells], cell_values [V][num_cells]) -> sums [n][1 + V]
         (the raw sums of pmc_integrate_weighted_rays), and the temperatures come from `temperatures`, a callable (tables) ->
         [H + 1][num_cells], or else are computed by the host from `rf`, the table rf[m * nbins + ell].  when: "Setup" or "Run" for the
-        probes with that probeAfter only, None for all"""
+        probes with that probeAfter only, None for all.  sampler: what a ConvergenceCutsProbe takes its gridded cuts from -- an ``Engine``
+        (its pmc_sample_cells is handed over as a C function; the same engine as the integrator, if that is one), or a callable
+        (positions [n][3], cell_values [V][num_cells]) -> values [V][n], the cell values at ``cell_indices(positions)`` and 0 outside the grid;
+        without one such a probe fails ("needs a sampler")"""
         import numpy as np
         assert self._setup, "call setup() first"
         os.makedirs(outdir, exist_ok=True)
@@ -469,7 +500,29 @@ class Simulation:
             assert table.size == self.radiation_field_size
             keep.append(table)
             engine.rf = table.ctypes.data
-        if lib().skh_write_probes_with(self._h, C.byref(engine), os.fsencode(outdir), code) != 0:
+        sample = None
+        if hasattr(sampler, "sample_callback"):
+            sample, user = sampler.sample_callback()
+            address = user if isinstance(user, int) or user is None else C.cast(user, C.c_void_p).value
+            if engine.user is not None and engine.user != address:
+                raise ValueError("integrator and sampler must be the same engine")
+            engine.user = user
+        elif sampler is not None:
+            def call_sample(_, n, positions, num_values, values, out, cells):
+                try:
+                    r = np.ctypeslib.as_array(positions, shape=(n, 3))
+                    q = np.ctypeslib.as_array(values, shape=(num_values, num_cells))
+                    np.ctypeslib.as_array(out, shape=(num_values, n))[:] = np.asarray(sampler(r, q), dtype=np.float64).reshape(num_values, n)
+                    if cells:
+                        np.ctypeslib.as_array(cells, shape=(n,))[:] = self.cell_indices(r)
+                    return 0
+                except Exception as error:
+                    failure.append(error)
+                    return 1
+
+            keep.append(SAMPLE_FN(call_sample))
+            sample = C.cast(keep[-1], C.c_void_p)
+        if lib().skh_write_probes_sampled(self._h, C.byref(engine), sample, os.fsencode(outdir), code) != 0:
             if failure:
                 raise failure[0]
             raise RuntimeError(lib().skh_last_error().decode())

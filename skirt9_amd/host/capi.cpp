@@ -344,6 +344,43 @@ int skh_write_probes_with(const skh_simulation* h, const skh_probe_engine* engin
     }
 }
 
+int skh_write_probes_sampled(const skh_simulation* h, const skh_probe_engine* engine, skh_sample_fn sample, const char* outdir, int32_t when)
+{
+    try
+    {
+        if (!h || !h->sim || !outdir) throw std::runtime_error("invalid argument");
+        skh::Simulation::ProbeEngine e;
+        if (engine)
+        {
+            e.integrate = engine->integrate;
+            e.weighted = engine->integrate_weighted;
+            e.temperatures = engine->temperatures;
+            e.user = engine->user;
+            e.rf = engine->rf;
+        }
+        e.sample = sample;
+        h->sim->writeProbes(e, outdir, when);
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int32_t skh_dimension(const skh_simulation* h)
+{
+    try
+    {
+        if (!h || !h->sim) throw std::runtime_error("invalid argument");
+        return h->sim->dimension();
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
 int skh_dust_heating(const skh_simulation* h, pmc_dust_heating* out)
 {
     try
@@ -395,6 +432,22 @@ int skh_dust_temperatures_from(const pmc_dust_heating* tables, const double* rf,
         if (!tables->width || !tables->sigma || !tables->planckabs || !tables->temperature || !tables->cell_factor || !tables->mass_density)
             throw std::runtime_error("null table");
         skh::Simulation::dustTemperatures(*tables, rf, out);
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        return fail(e);
+    }
+}
+
+int skh_cell_indices(const skh_simulation* h, int64_t num_points, const double* positions, int32_t* cells)
+{
+    try
+    {
+        if (!h || !h->sim || num_points < 0 || (num_points > 0 && (!positions || !cells))) throw std::runtime_error("invalid argument");
+        const skh::SpatialGrid& grid = h->sim->grid();
+        for (int64_t p = 0; p < num_points; ++p)
+            cells[p] = grid.cellIndex(skh::Vec3{positions[3 * p], positions[3 * p + 1], positions[3 * p + 2]});
         return 0;
     }
     catch (const std::exception& e)

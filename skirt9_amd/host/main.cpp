@@ -13,7 +13,8 @@
 // maps computed on the first device (pmc_integrate_rays): those with probeAfter="Setup" before the photon loop, the others after it
 // (ProbeSystem::probeSetup / probeRun).  The temperature probes are written after the loop -- with several devices after the radiation field
 // has been summed over them -- from the table on the first device: the dust temperatures by pmc_dust_temperatures, the averages along the
-// rays of their maps by pmc_integrate_weighted_rays.  There is no CPU fallback: without a HIP device pmc_create fails and so does the run.
+// rays of their maps by pmc_integrate_weighted_rays.  The gridded cuts of a ConvergenceCutsProbe come from pmc_sample_cells on the same device,
+// with the Setup or the Run probes according to its probeAfter.  There is no CPU fallback: without a HIP device pmc_create fails and so does the run.
 
 #include "../../include/pmc.h"
 #include "../../include/skirt_host.h"
@@ -155,11 +156,16 @@ int main(int argc, char** argv)
     probeEngine.temperatures = [](void* user, const pmc_dust_heating* tables, double* out) {
         return pmc_dust_temperatures(static_cast<pmc_ctx*>(user), tables, out);
     };
+    // the point sampler of the convergence cuts: the same context
+    const skh_sample_fn sample = [](void* user, int64_t numPoints, const double* positions, int32_t numValues, const double* cellValues,
+                                    double* values, int32_t* cells) {
+        return pmc_sample_cells(static_cast<pmc_ctx*>(user), numPoints, positions, numValues, cellValues, values, cells);
+    };
     auto writeProbes = [&](int when) {
         probeEngine.user = ctxs[0];
         // (after the run: the host copy of the radiation field table, for DustAbsorptionPerCellProbe)
         probeEngine.rf = when == 1 && !rf.empty() ? rf.data() : nullptr;
-        if (skh_write_probes_with(sim, &probeEngine, outdir.c_str(), when) == 0) return true;
+        if (skh_write_probes_sampled(sim, &probeEngine, sample, outdir.c_str(), when) == 0) return true;
         // (the host layer reports that the integrator failed; the engine says why)
         errors[0] = std::string(skh_last_error()) + (*pmc_last_error() ? std::string(": ") + pmc_last_error() : std::string());
         return false;
@@ -169,7 +175,12 @@ int main(int argc, char** argv)
         bool ok = pmc_create_ext(skh_scene(sim), skh_scene_ext(sim), devices[g], &ctxs[g]) == PMC_OK;
         if (!ok) failed();
         // (probes after setup: before any photon packet is launched)
-        if (ok && g == 0) ok = writeProbes(0);
+        if (ok && g == 0)
+        {
+            const auto p0 = clock::now();
+            ok = writeProbes(0);
+            if (ok) printf("Finished setup output in %.3f s.\n", seconds(p0, clock::now()));
+        }
         if (ok)
         {
             // (the first device reports for all: MonteCarloSimulation::logProgress / Log::infoIfElapsed, every 3 s)
@@ -180,7 +191,10 @@ int main(int argc, char** argv)
                 }, nullptr, 3.);
             uint64_t first = 0, count = 0;
             pmc_history_range(n, g, G, &first, &count);
+            const auto l0 = clock::now();
             const int rc = pmc_run_primary(ctxs[g], first, count, (uint64_t)skh_seed(sim));
+            // (the loop alone, without the context and the setup output that "Finished primary emission" below counts in)
+            if (g == 0) printf("Photon loop on the first device: %.3f s.\n", seconds(l0, clock::now()));
             // (the pool of statistics list blocks ran out: the flux arrays of the segment are complete, its sums of w^k are not --
             // the run goes on, and the statistics files are left out below)
             if (rc == PMC_ERR_OVERFLOW) statisticsLost[g] = pmc_last_error();

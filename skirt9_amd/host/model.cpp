@@ -771,6 +771,34 @@ namespace skh
         int k = m % nz;
         return Box(xv[i], yv[j], zv[k], xv[i + 1], yv[j + 1], zv[k + 1]);
     }
+    namespace
+    {
+        // NR::locateFail (NR.hpp:130-143, 186-191): the bin of x among the borders xv, the last border in the last bin; -1 out of range
+        int locateFail(const Array& xv, double x)
+        {
+            int n = static_cast<int>(xv.size());
+            if (x > xv[n - 1]) return -1;
+            int jl = -1;
+            int ju = n - 1;
+            while (ju - jl > 1)
+            {
+                int jm = (ju + jl) >> 1;
+                if (x < xv[jm])
+                    ju = jm;
+                else
+                    jl = jm;
+            }
+            return jl;
+        }
+    }
+    int CartesianSpatialGrid::cellIndex(Vec3 r) const
+    {
+        int i = locateFail(xv, r.x);
+        int j = locateFail(yv, r.y);
+        int k = locateFail(zv, r.z);
+        if (i < 0 || j < 0 || k < 0) return -1;
+        return k + nz * j + nz * ny * i;
+    }
     void CartesianSpatialGrid::fill(pmc_grid& g) const
     {
         g.kind = PMC_GRID_CARTESIAN;
@@ -1197,6 +1225,27 @@ namespace skh
             }
         }
         flatNbrStart[6 * size_t(numNodes)] = static_cast<int32_t>(flatNbrList.size());
+    }
+
+    int OctreeSpatialGrid::cellIndex(Vec3 r) const
+    {
+        if (nodes.empty() || !nodes[0].box.contains(r.x, r.y, r.z)) return -1;
+        int id = 0;
+        while (nodes[id].firstChild >= 0)
+        {
+            // the corner that child 0 shares with its siblings: CHILD_0->rmax() (OctTreeNode.cpp:39), CHILD_0->xmax() ... (BinTreeNode.cpp:57-59)
+            const Box& first = nodes[nodes[id].firstChild].box;
+            int l;
+            if (binary)
+            {
+                int dir = nodes[id].level % 3;
+                l = dir == 0 ? (r.x < first.xmax ? 0 : 1) : dir == 1 ? (r.y < first.ymax ? 0 : 1) : (r.z < first.zmax ? 0 : 1);
+            }
+            else
+                l = (r.x < first.xmax ? 0 : 1) + (r.y < first.ymax ? 0 : 2) + (r.z < first.zmax ? 0 : 4);
+            id = nodes[id].firstChild + l;
+        }
+        return cellIndexOfNode[id];
     }
 
     void OctreeSpatialGrid::fill(pmc_grid& g) const

@@ -54,6 +54,8 @@ namespace skh
     public:
         virtual ~Geometry() {}
         virtual std::string type() const = 0;
+        // Geometry::dimension(): 1 spherical (SpheGeometry), 2 axisymmetric (AxGeometry), 3 neither (GenGeometry)
+        virtual int dimension() const = 0;
         virtual double density(Vec3 r) const = 0;
         virtual double columnX() const = 0;
         virtual double columnY() const = 0;
@@ -83,6 +85,7 @@ namespace skh
     public:
         explicit UniformBoxGeometry(const Box& box);
         std::string type() const override { return "UniformBoxGeometry"; }
+        int dimension() const override { return 3; }
         double density(Vec3 r) const override;
         double columnX() const override;
         double columnY() const override;
@@ -101,6 +104,7 @@ namespace skh
     public:
         ExpDiskGeometry(double radialScale, double verticalScale, double innerRadius, double outerRadius, double maxHeight);
         std::string type() const override { return "ExpDiskGeometry"; }
+        int dimension() const override { return 2; }
         double density(Vec3 r) const override;
         double columnX() const override { return 2.0 * radialColumn(); }
         double columnY() const override { return 2.0 * radialColumn(); }
@@ -118,6 +122,7 @@ namespace skh
     public:
         SersicGeometry(double effectiveRadius, double index);
         std::string type() const override { return "SersicGeometry"; }
+        int dimension() const override { return 1; }
         double density(Vec3 r) const override;
         double columnX() const override { return 2.0 * radialColumn(); }
         double columnY() const override { return 2.0 * radialColumn(); }
@@ -137,6 +142,7 @@ namespace skh
     public:
         explicit PlummerGeometry(double scale);
         std::string type() const override { return "PlummerGeometry"; }
+        int dimension() const override { return 1; }
         double density(Vec3 r) const override;
         double columnX() const override { return 2.0 * radialColumn(); }
         double columnY() const override { return 2.0 * radialColumn(); }
@@ -155,6 +161,7 @@ namespace skh
     public:
         explicit GaussianGeometry(double dispersion);
         std::string type() const override { return "GaussianGeometry"; }
+        int dimension() const override { return 1; }
         double density(Vec3 r) const override;
         double columnX() const override { return 2.0 * radialColumn(); }
         double columnY() const override { return 2.0 * radialColumn(); }
@@ -173,6 +180,7 @@ namespace skh
     public:
         SpheroidalGeometry(std::unique_ptr<Geometry> spherical, double flattening) : sphere_(std::move(spherical)), flat_(flattening) {}
         std::string type() const override { return "SpheroidalGeometryDecorator"; }
+        int dimension() const override { return 2; }
         double density(Vec3 r) const override;
         double columnX() const override { return 2.0 * radialColumn(); }
         double columnY() const override { return 2.0 * radialColumn(); }
@@ -193,6 +201,8 @@ namespace skh
     public:
         OffsetGeometry(std::unique_ptr<Geometry> geometry, Vec3 shift) : base_(std::move(geometry)), shift_(shift) {}
         std::string type() const override { return "OffsetGeometryDecorator"; }
+        // OffsetGeometryDecorator.cpp:10-13
+        int dimension() const override { return (shift_.x || shift_.y || base_->dimension() == 3) ? 3 : 2; }
         double density(Vec3 r) const override { return base_->density(Vec3{r.x - shift_.x, r.y - shift_.y, r.z - shift_.z}); }
         double columnX() const override { return base_->columnX(); }
         double columnY() const override { return base_->columnY(); }
@@ -227,6 +237,7 @@ namespace skh
     public:
         ShellGeometry(double rmin, double rmax, double p);
         std::string type() const override { return "ShellGeometry"; }
+        int dimension() const override { return 1; }
         double density(Vec3 r) const override;
         double columnX() const override { return 2.0 * radialColumn(); }
         double columnY() const override { return 2.0 * radialColumn(); }
@@ -245,6 +256,7 @@ namespace skh
     public:
         TorusGeometry(double p, double q, double halfOpening, double rmin, double rmax, bool anisotropicInner, double cutoffRadius);
         std::string type() const override { return "TorusGeometry"; }
+        int dimension() const override { return 2; }
         double density(Vec3 r) const override;
         double columnX() const override { return 2.0 * radialColumn(); }
         double columnY() const override { return 2.0 * radialColumn(); }
@@ -264,6 +276,7 @@ namespace skh
     public:
         RingGeometry(double ringRadius, double width, double verticalScale);
         std::string type() const override { return "RingGeometry"; }
+        int dimension() const override { return 2; }
         double density(Vec3 r) const override;
         double columnX() const override { return 2.0 * radialColumn(); }
         double columnY() const override { return 2.0 * radialColumn(); }
@@ -350,6 +363,11 @@ namespace skh
         virtual double massDensity(Vec3 r) const = 0;
         virtual double totalMass() const = 0;
         virtual double totalNumber() const = 0;
+        // Medium::dimension(): the symmetry of the component (GeometricMedium.cpp:21-26 -- the media of this path are at rest and have no
+        // magnetic field, so the geometry decides --, ImportedMedium.cpp:75-78)
+        virtual int dimension() const = 0;
+        // Medium::opticalDepthX / Y / Z (axis 0 / 1 / 2): the optical depth of the component along the full coordinate axis at a wavelength
+        virtual double opticalDepth(int axis, double lambda) const = 0;
         // Medium::generatePosition (sites of a Voronoi grid with the DustDensity policy)
         virtual Vec3 generatePosition(Random& random) const = 0;
         // many positions at once (the setup phase samples 100 per tree node and per cell): on the host cores by
@@ -387,6 +405,9 @@ namespace skh
         std::vector<Medium*> electrons;  // the electron components
         std::string type() const override { return "media"; }
         void setup() override {}
+        // (the medium system asks the components themselves: Simulation::dimension, the convergence probes)
+        int dimension() const override { throw std::runtime_error("dimension of a composite medium"); }
+        double opticalDepth(int, double) const override { throw std::runtime_error("optical depth of a composite medium"); }
         double numberDensity(Vec3) const override { throw std::runtime_error("number density of a composite medium"); }
         double massDensity(Vec3 r) const override
         {
@@ -442,6 +463,13 @@ namespace skh
         double number{0}, mass{0};  // results of setup()
 
         std::string type() const override { return "GeometricMedium"; }
+        int dimension() const override { return geometry->dimension(); }
+        // GeometricMedium.cpp:156-173
+        double opticalDepth(int axis, double lambda) const override
+        {
+            const double column = axis == 0 ? geometry->columnX() : axis == 1 ? geometry->columnY() : geometry->columnZ();
+            return number * column * mix->sectionExt(lambda);
+        }
         void setup() override;
         double numberDensity(Vec3 r) const override { return number * geometry->density(r); }
         double massDensity(Vec3 r) const override { return mass * geometry->density(r); }
@@ -464,6 +492,31 @@ namespace skh
         ParticleSnapshot snapshot;
 
         std::string type() const override { return "ParticleMedium"; }
+        int dimension() const override { return 3; }
+        // ImportedMedium.cpp:234-257 with Snapshot::SigmaX / Y / Z (Snapshot.cpp:535-590): the mean of 10000 densities along the axis of the
+        // snapshot's extent, at the offset 1e-12 diagonals from it, times the length; evaluated as a batch (the device sampler serves it
+        // when bound) and added up in the reference's order
+        double opticalDepth(int axis, double lambda) const override
+        {
+            const int numSamples = 10000;
+            const Box& box = snapshot.search().extent();  // ParticleSnapshot::extent (ParticleSnapshot.cpp:198-204)
+            const double eps = 1e-12 * box.diagonal();
+            const double lo = axis == 0 ? box.xmin : axis == 1 ? box.ymin : box.zmin;
+            const double hi = axis == 0 ? box.xmax : axis == 1 ? box.ymax : box.zmax;
+            std::vector<Vec3> positions(numSamples);
+            for (int k = 0; k < numSamples; k++)
+            {
+                const double v = lo + k * (hi - lo) / numSamples;
+                positions[k] = axis == 0 ? Vec3{v, eps, eps} : axis == 1 ? Vec3{eps, v, eps} : Vec3{eps, eps, v};
+            }
+            std::vector<double> density;
+            snapshot.densities(positions, density);
+            double sum = 0;
+            for (int k = 0; k < numSamples; k++) sum += density[k];
+            double result = (sum / numSamples) * (hi - lo) * mix->sectionExt(lambda);
+            if (!snapshot.holdsNumber()) result /= mix->mass();
+            return result;
+        }
         void setup() override { snapshot.load(options, SmoothingKernel::create(kernelType)); }
         double numberDensity(Vec3 r) const override
         {
@@ -517,8 +570,13 @@ namespace skh
         virtual int numCells() const = 0;
         virtual Box cellBox(int m) const = 0;  // box cells: the cell; Voronoi: the bounding box of the cell
         virtual void fill(pmc_grid& g) const = 0;
+        // SpatialGrid::cellIndex(Position): the cell that holds r, -1 outside the grid.  The domain box is closed, and a position on a wall
+        // between two cells belongs to the upper one (each grid restates the reference's function literally)
+        virtual int cellIndex(Vec3 r) const = 0;
         // SpatialGrid::volume / centralPositionInCell / randomPositionInCell
         virtual double volume(int m) const { return cellBox(m).volume(); }
+        // SpatialGrid::diagonal(m): of the cell's box (TreeSpatialGrid.cpp:103-106, CartesianSpatialGrid.cpp:53-56)
+        virtual double diagonal(int m) const { return cellBox(m).diagonal(); }
         virtual Vec3 centralPositionInCell(int m) const { return cellBox(m).center(); }
         virtual Vec3 randomPositionInCell(int m, Random& random) const { return random.position(cellBox(m)); }
     };
@@ -542,6 +600,8 @@ namespace skh
         int numCells() const override { return nx * ny * nz; }
         Box cellBox(int m) const override;
         void fill(pmc_grid& g) const override;
+        // CartesianSpatialGrid.cpp:60-69: NR::locateFail per axis
+        int cellIndex(Vec3 r) const override;
     };
 
     // PolicyTreeSpatialGrid (treeType OctTree or BinTree) with DensityTreePolicy
@@ -579,6 +639,8 @@ namespace skh
         int numCells() const override { return static_cast<int>(nodeOfCell.size()); }
         Box cellBox(int m) const override { return nodes[nodeOfCell[m]].box; }
         void fill(pmc_grid& g) const override;
+        // TreeSpatialGrid.cpp:110-114: root()->leafChild(r) (TreeNode.cpp:66-76) with OctTreeNode::child or BinTreeNode::child
+        int cellIndex(Vec3 r) const override;
 
     private:
         void subdivide(int id);
@@ -601,7 +663,9 @@ namespace skh
         int numCells() const override { return mesh.numCells(); }
         Box cellBox(int m) const override { return mesh.cellBox(m); }
         void fill(pmc_grid& g) const override;
+        int cellIndex(Vec3 r) const override { return mesh.cellIndex(r); }
         double volume(int m) const override { return mesh.volume(m); }
+        double diagonal(int m) const override { return cbrt(3. * mesh.volume(m)); }  // VoronoiMeshSpatialGrid.cpp:162-165
         Vec3 centralPositionInCell(int m) const override { return mesh.site(m); }
         // VoronoiMeshSnapshot::generatePosition(m) (:976-989): rejection sampling in the bounding box
         Vec3 randomPositionInCell(int m, Random& random) const override;

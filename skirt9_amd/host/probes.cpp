@@ -279,6 +279,225 @@ namespace skh
         return false;
     }
 
+    // ConvergenceInfoProbe::probe (ConvergenceInfoProbe.cpp:17-175): <prefix>_<probe>_convergence.dat.  Per material type present the input
+    // mass against the gridded mass, the input optical depth along the coordinate axes (Medium::opticalDepthX/Y/Z) against the gridded one --
+    // two rays per axis from (eps, eps, eps), eps = 1e-15 diagonals of the grid, through the caller's integrator with the opacity of that type
+    // as the cell value: MediumSystem::getExtinctionOpticalDepth(path, lambda, type), MediumSystem.cpp:1264-1275 --, then the statistics of the
+    // cells' diagonal optical depths.  Line formats: writeValues, StringUtils::toString 'g' with 6 digits, the percentage 'f' with 2
+    std::string Simulation::writeConvergenceInfo(const ProbeModel& probe, const ProbeEngine& engine, const std::string& base) const
+    {
+        if (!engine.integrate)
+            throw std::runtime_error("probe " + probe.name + " (ConvergenceInfoProbe) needs an integrator for its gridded optical depths");
+        const int numMedia = static_cast<int>(_media.size());
+        const int numCells = _grid->numCells();
+        const double lambda = probe.wavelength;
+        auto number = [](double value, char format, int precision) {
+            char buf[40];
+            snprintf(buf, sizeof(buf), format == 'f' ? "%1.*f" : "%1.*g", precision, value);
+            return std::string(buf);
+        };
+        const std::string path = base + probe.name + "_convergence.dat";
+        std::ofstream out(path);
+        if (!out) throw std::runtime_error("Could not open output file " + path);
+        auto line = [&](const std::string& text) { out << text << std::endl; };
+        auto writeValues = [&](double t, double g, double factor, const std::string& unit) {
+            std::string tail;
+            if (!unit.empty()) tail += " " + unit;
+            line("  Input:   " + number(t * factor, 'g', 6) + tail);
+            if (t > 0) tail += " (" + number(100. * (g - t) / t, 'f', 2) + " %)";
+            line("  Gridded: " + number(g * factor, 'g', 6) + tail);
+        };
+        const std::string atWavelength = number(_units.owavelength(lambda), 'g', 6) + " " + _units.uwavelength();
+        line("Spatial grid convergence information");
+        line("------------------------------------");
+        std::vector<int> all;
+        for (int h = 0; h != numMedia; ++h) all.push_back(h);
+        for (int kind = 0; kind != 2; ++kind)
+        {
+            std::vector<int> components;
+            for (int h = 0; h != numMedia; ++h)
+                if (_media[h]->mix->isElectrons() == (kind == 1)) components.push_back(h);
+            if (components.empty()) continue;  // MediumSystem::hasDust / hasElectrons
+            line("");
+            line(std::string("------ ") + (kind ? "Electrons" : "Dust") + " ------");
+            double mass_t = 0., mass_g = 0.;
+            for (int h : components)
+            {
+                mass_t += _media[h]->totalMass();
+                for (int m = 0; m != numCells; ++m) mass_g += _density[h][m] * _media[h]->mix->mass() * _grid->volume(m);
+            }
+            line("");
+            line("Total mass");
+            writeValues(mass_t, mass_g, _units.out("mass", 1.), _units.unit("mass"));
+            double tau_t[3] = {0., 0., 0.};
+            for (int h : components)
+                for (int axis = 0; axis != 3; ++axis) tau_t[axis] += _media[h]->opticalDepth(axis, lambda);
+            // the six rays of griddedOpticalDepth: per axis along it and against it
+            ProbeQuantity q;
+            q.kind = ProbeQuantity::Opacity;
+            q.components = components;
+            q.wave = Array{lambda};
+            std::vector<double> opacity(numCells);
+            for (int m = 0; m != numCells; ++m) opacity[m] = probeCellValue(q, 0, m);
+            const double eps = 1e-15 * _grid->extent.diagonal();
+            double origins[18], directions[18], sums[6] = {0., 0., 0., 0., 0., 0.};
+            for (int ray = 0; ray != 6; ++ray)
+                for (int a = 0; a != 3; ++a)
+                {
+                    origins[3 * ray + a] = eps;
+                    directions[3 * ray + a] = a == ray / 2 ? (ray % 2 ? -1. : 1.) : (ray % 2 ? -0. : 0.);
+                }
+            if (engine.integrate(engine.user, 6, origins, directions, 1, opacity.data(), sums) != 0)
+                throw std::runtime_error("probe " + probe.name + ": the ray integrator failed");
+            const char* axisName[3] = {"X", "Y", "Z"};
+            for (int axis = 0; axis != 3; ++axis)
+            {
+                double tau_g = sums[2 * axis];
+                tau_g += sums[2 * axis + 1];
+                line("");
+                line("Optical depth at " + atWavelength + " along full " + axisName[axis] + "-axis");
+                writeValues(tau_t[axis], tau_g, 1., "");
+            }
+        }
+        // writeOpticalDepthStatistics (ConvergenceInfoProbe.cpp:107-145)
+        {
+            ProbeQuantity q;
+            q.kind = ProbeQuantity::Opacity;
+            q.components = all;
+            q.wave = Array{lambda};
+            Array tauV(numCells);
+            for (int m = 0; m != numCells; ++m) tauV[m] = _grid->diagonal(m) * probeCellValue(q, 0, m);
+            double sum = 0., taumin = tauV[0], taumax = tauV[0];
+            for (double tau : tauV)
+            {
+                sum += tau;
+                taumin = std::min(taumin, tau);
+                taumax = std::max(taumax, tau);
+            }
+            const double tauavg = sum / numCells;
+            const int numBins = 500;
+            std::vector<int> countV(numBins + 1);
+            for (double tau : tauV)
+            {
+                int index = std::max(0, std::min(numBins, static_cast<int>((tau - taumin) / (taumax - taumin) * numBins)));
+                countV[index]++;
+            }
+            int count = 0;
+            int index = 0;
+            for (; index < numBins; index++)
+            {
+                count += countV[index];
+                if (count > 0.9 * numCells) break;
+            }
+            const double tau90 = taumin + index * (taumax - taumin) / numBins;
+            line("");
+            line("------ Cell statistics ------");
+            line("");
+            line("Optical depth of cell diagonal at " + atWavelength);
+            line("  Largest: " + number(taumax, 'g', 6));
+            line("  Average: " + number(tauavg, 'g', 6));
+            line("  90% <  : " + number(tau90, 'g', 6));
+        }
+        line("");
+        line("------------------------------------");
+        return path;
+    }
+
+    // ConvergenceCutsProbe::probe (ConvergenceCutsProbe.cpp:23-60) with its hard-coded DefaultCutsForm (DefaultCutsForm.cpp:20-34) and
+    // PlanarCutsForm::writePlanarCut (PlanarCutsForm.cpp:32-103): per material type the true density (an InputScalar quantity: the media's
+    // own density at the position, times the unit factor) and the gridded density (a GridScalarAccumulated quantity:
+    // ProbeFormBridge::valuesAtPosition, the value of the cell at cellIndex(position) times the unit factor, 0 outside) on 1024 x 1024
+    // positions per coordinate plane.  The true density is evaluated here (Medium::massDensities / numberDensities: all host cores, or the
+    // device sampler of an imported medium); the gridded one by the caller's point sampler, with the unit factor multiplied into the cell
+    // values beforehand (valuesInCell: one rounding)
+    void Simulation::writeConvergenceCuts(const ProbeModel& probe, const ProbeEngine& engine, const std::string& base, std::vector<std::string>& files) const
+    {
+        if (!engine.sample)
+            throw std::runtime_error("probe " + probe.name + " (ConvergenceCutsProbe) needs a sampler: hand over the engine's pmc_sample_cells");
+        constexpr int Np = 1024;
+        const int numCells = _grid->numCells();
+        const int dim = dimension();
+        const Box box = _grid->extent;
+        // PlanarCutsForm.cpp:36-44
+        const double xpsize = (box.xmax - box.xmin) / Np;
+        const double ypsize = (box.ymax - box.ymin) / Np;
+        const double zpsize = (box.zmax - box.zmin) / Np;
+        const double xbase = box.xmin + 0.5 * xpsize;
+        const double ybase = box.ymin + 0.5 * ypsize;
+        const double zbase = box.zmin + 0.5 * zpsize;
+        const Vec3 center = box.center();
+        const double xp = 0., yp = 0., zp = 0.;
+
+        std::vector<int> dust, electrons;
+        for (int h = 0; h != static_cast<int>(_media.size()); ++h) (_media[h]->mix->isElectrons() ? electrons : dust).push_back(h);
+        struct Plane
+        {
+            bool xd, yd, zd;
+            const char* name;
+        };
+        std::vector<Plane> planes{{true, true, false, "xy"}};
+        if (dim >= 2) planes.push_back({true, false, true, "xz"});
+        if (dim == 3) planes.push_back({false, true, true, "yz"});
+
+        std::vector<Vec3> positions(size_t(Np) * Np);
+        std::vector<double> flat(3 * positions.size()), one, cellValues(numCells);
+        Array vvv(positions.size());
+        for (int kind = 0; kind != 2; ++kind)
+        {
+            const bool mass = kind == 0;
+            const std::vector<int>& components = mass ? dust : electrons;
+            if (components.empty()) continue;  // MediumSystem::hasDust / hasElectrons
+            const std::string quantity = mass ? "massvolumedensity" : "numbervolumedensity";
+            const double unitFactor = _units.out(quantity, 1.);
+            ProbeQuantity q;
+            q.kind = mass ? ProbeQuantity::MassDensity : ProbeQuantity::NumberDensity;
+            q.components = components;
+            for (int m = 0; m != numCells; ++m) cellValues[m] = probeCellValue(q, 0, m) * unitFactor;
+            for (int gridded = 0; gridded != 2; ++gridded)
+                for (const Plane& plane : planes)
+                {
+                    const int Ni = Np, Nj = Np;
+                    for (int j = 0; j != Nj; ++j)
+                    {
+                        const double z = plane.zd ? (zbase + j * zpsize) : zp;
+                        for (int i = 0; i != Ni; ++i)
+                        {
+                            const double x = plane.xd ? (xbase + i * xpsize) : xp;
+                            const double y = plane.yd ? (ybase + (plane.zd ? i : j) * ypsize) : yp;
+                            positions[size_t(j) * Ni + i] = Vec3{x, y, z};
+                        }
+                    }
+                    if (!gridded)
+                    {
+                        // MediumSystem::dustMassDensity(Position) / electronNumberDensity(Position) (MediumSystem.cpp:456-470): the sum over
+                        // the components in order, then the unit factor
+                        std::fill(vvv.begin(), vvv.end(), 0.);
+                        for (int h : components)
+                        {
+                            if (mass)
+                                _media[h]->massDensities(positions, one);
+                            else
+                                _media[h]->numberDensities(positions, one);
+                            for (size_t p = 0; p != vvv.size(); ++p) vvv[p] += one[p];
+                        }
+                        for (double& v : vvv) v *= unitFactor;
+                    }
+                    else
+                    {
+                        for (size_t p = 0; p != positions.size(); ++p)
+                            flat[3 * p] = positions[p].x, flat[3 * p + 1] = positions[p].y, flat[3 * p + 2] = positions[p].z;
+                        if (engine.sample(engine.user, static_cast<int64_t>(positions.size()), flat.data(), 1, cellValues.data(), vvv.data(), nullptr) != 0)
+                            throw std::runtime_error("probe " + probe.name + ": the point sampler failed");
+                    }
+                    const std::string path = base + probe.name + "_" + (mass ? "dust" : "elec") + (gridded ? "_g_" : "_t_") + plane.name + ".fits";
+                    writeFitsCube(path, vvv.data(), _units.unit(quantity), Ni, Nj, _units.out("length", plane.xd ? xpsize : ypsize),
+                                  _units.out("length", plane.zd ? zpsize : ypsize), _units.out("length", plane.xd ? center.x : center.y),
+                                  _units.out("length", plane.zd ? center.z : center.y), _units.unit("length"), Array(), std::string("1"), nullptr);
+                    files.push_back(path);
+                }
+        }
+    }
+
     std::vector<std::string> Simulation::writeProbes(IntegrateFn integrate, void* user, const std::string& outdir, int when) const
     {
         ProbeEngine engine;
@@ -314,6 +533,16 @@ namespace skh
         for (const ProbeModel& probe : _probes)
         {
             if (when >= 0 && (when == 0) != probe.afterSetup) continue;
+            if (probe.type == "ConvergenceInfoProbe")
+            {
+                if (_hasMedium) files.push_back(writeConvergenceInfo(probe, engine, base));  // ConvergenceInfoProbe.cpp:152
+                continue;
+            }
+            if (probe.type == "ConvergenceCutsProbe")
+            {
+                if (_hasMedium) writeConvergenceCuts(probe, engine, base, files);  // ConvergenceCutsProbe.cpp:25
+                continue;
+            }
             if (probe.type == "DustAbsorptionPerCellProbe")
             {
                 // DustAbsorptionPerCellProbe.cpp:25-63 through TextOutFile; MediumSystem::hasDust

@@ -132,6 +132,9 @@ namespace skh
         // an OpacityProbe's own grid is a MaterialWavelengthRangeInterface item (OpacityProbe.cpp:18-33, Configuration.cpp:594-596, 657-659)
         for (auto& probe : _probes)
             if (probe.ownGrid) addGrid(probe.ownGrid.get());
+        // ... and so is a ConvergenceInfoProbe, with the single wavelength it looks at (SpecialtyWavelengthProbe.cpp: Range(wavelength, wavelength))
+        for (auto& probe : _probes)
+            if (probe.type == "ConvergenceInfoProbe") addWavelength(probe.wavelength);
         // MaterialWavelengthRangeInterface items: the normalisation wavelength and the tree policy wavelength
         for (auto& part : _media)
             if (part->normalizationWavelength() > 0) addWavelength(part->normalizationWavelength());

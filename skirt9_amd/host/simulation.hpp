@@ -100,6 +100,10 @@ namespace skh
         typedef int (*WeightedFn)(void* user, int64_t numRays, const double* origins, const double* directions, int32_t numValues,
                                   const double* cellWeights, const double* cellValues, double* sums);
         typedef int (*TemperatureFn)(void* user, const pmc_dust_heating* tables, double* out);
+        // the point sampler of the cut forms (the engine's pmc_sample_cells): cells[p] = SpatialGrid::cellIndex(positions[p]), values[v * numPoints + p] =
+        // cellValues[v * numCells + cells[p]] or 0 outside the grid; cells may be null
+        typedef int (*SampleFn)(void* user, int64_t numPoints, const double* positions, int32_t numValues, const double* cellValues, double* values,
+                                int32_t* cells);
         struct ProbeEngine
         {
             IntegrateFn integrate{nullptr};
@@ -107,6 +111,7 @@ namespace skh
             TemperatureFn temperatures{nullptr};
             void* user{nullptr};
             const double* rf{nullptr};
+            SampleFn sample{nullptr};  // ConvergenceCutsProbe (user as for the others)
         };
         std::vector<std::string> writeProbes(const ProbeEngine& engine, const std::string& outdir, int when = -1) const;
         // whether a probe written with `when` reads the radiation field (a TemperatureProbe or DustAbsorptionPerCellProbe that writes a file)
@@ -118,6 +123,13 @@ namespace skh
         // model objects, exposed for tests
         const SpatialGrid& grid() const { return *_grid; }
         const Medium& medium() const { return *_medium; }
+        // MediumSystem::dimension (MediumSystem.cpp:403-408): the largest dimension of the medium components, at least 1
+        int dimension() const
+        {
+            int result = 1;
+            for (const auto& part : _media) result = std::max(result, part->dimension());
+            return result;
+        }
         const Array& numberDensity(size_t h = 0) const { return _density[h]; }
         const SourceModel& source(int h = 0) const { return _sources[h]; }
         int numSources() const { return static_cast<int>(_sources.size()); }
@@ -164,6 +176,10 @@ namespace skh
         void readProbeSystem(const XmlElement& sim, const Reader& rd);
         static ProbeModel readDustAbsorptionProbe(const XmlElement& probe, const Reader& rd);
         static ProbeModel readFormProbe(const XmlElement& probe, const Reader& rd);
+        static ProbeModel readConvergenceCutsProbe(const XmlElement& probe, const Reader& rd);
+        static ProbeModel readConvergenceInfoProbe(const XmlElement& probe, const Reader& rd);
+        std::string writeConvergenceInfo(const ProbeModel& probe, const ProbeEngine& engine, const std::string& base) const;
+        void writeConvergenceCuts(const ProbeModel& probe, const ProbeEngine& engine, const std::string& base, std::vector<std::string>& files) const;
         static std::string readRadiationFieldProbe(const XmlElement& probe, const Reader& rd);
 
         // simulation.cpp: the stages of setup(), in order
@@ -227,6 +243,7 @@ namespace skh
             bool projected{false};                // ParallelProjectionForm (else PerCellForm)
             double inclination{0}, azimuth{0}, roll{0}, fieldOfViewX{0}, fieldOfViewY{0}, centerX{0}, centerY{0};
             int numPixelsX{250}, numPixelsY{250}, numSampling{1};
+            double wavelength{0.55e-6};               // ConvergenceInfoProbe (SpecialtyWavelengthProbe.hpp)
             std::unique_ptr<WavelengthGrid> ownGrid;  // OpacityProbe::wavelengthGrid (panchromatic only)
             const WavelengthGrid* grid{nullptr};      // Configuration::wavelengthGrid(ownGrid), set by setup()
         };

@@ -724,6 +724,30 @@ namespace skh
         return probe;
     }
 
+    // ConvergenceCutsProbe (ConvergenceCutsProbe.hpp, SpecialtyWhenProbe.hpp:25-31): a name and probeAfter; its form is the hard-coded
+    // DefaultCutsForm
+    Simulation::ProbeModel Simulation::readConvergenceCutsProbe(const XmlElement& pe, const Reader&)
+    {
+        ProbeModel probe;
+        probe.type = pe.name;
+        probe.name = pe.attr("probeName", "");
+        const std::string after = pe.attr("probeAfter", "Setup");
+        if (after == "Primary" || after == "Secondary") unsupported(pe.name + " probeAfter " + after);
+        if (after != "Setup" && after != "Run") throw std::runtime_error("ski: invalid probeAfter '" + after + "' for " + pe.name);
+        probe.afterSetup = after == "Setup";
+        return probe;
+    }
+
+    // ConvergenceInfoProbe (ConvergenceInfoProbe.hpp, SpecialtyWavelengthProbe.hpp:27-31): the same with the wavelength of its optical depths
+    Simulation::ProbeModel Simulation::readConvergenceInfoProbe(const XmlElement& pe, const Reader& rd)
+    {
+        ProbeModel probe = readConvergenceCutsProbe(pe, rd);
+        probe.wavelength = rd.quantity(pe, "wavelength", "wavelength", "0.55 micron");
+        if (!(probe.wavelength >= 1e-12 && probe.wavelength <= 1.))
+            throw std::runtime_error("ski: wavelength of probe " + probe.name + " out of range [1 pm, 1 m]");
+        return probe;
+    }
+
     // RadiationFieldProbe with a PerCellForm: its name
     std::string Simulation::readRadiationFieldProbe(const XmlElement& pe, const Reader& rd)
     {
@@ -883,7 +907,9 @@ namespace skh
 
     // the radiation field per cell (RadiationFieldProbe + PerCellForm); densities, opacities and dust temperatures per cell and in parallel
     // projection (DensityProbe, OpacityProbe, TemperatureProbe + PerCellForm, ParallelProjectionForm) and the absorbed luminosity per cell
-    // (DustAbsorptionPerCellProbe): probes.cpp; nothing else is on this path
+    // (DustAbsorptionPerCellProbe) and the true and gridded density in the coordinate planes (ConvergenceCutsProbe), the
+    // convergence information file (ConvergenceInfoProbe): probes.cpp; nothing else is
+    // on this path
     void Simulation::readProbeSystem(const XmlElement& sim, const Reader& rd)
     {
         const XmlElement* ps = sim.item("probeSystem");
@@ -901,6 +927,10 @@ namespace skh
                 _probes.push_back(readDustAbsorptionProbe(*pe, rd));
             else if (pe->name == "DensityProbe" || pe->name == "OpacityProbe" || pe->name == "TemperatureProbe")
                 _probes.push_back(readFormProbe(*pe, rd));
+            else if (pe->name == "ConvergenceCutsProbe")
+                _probes.push_back(readConvergenceCutsProbe(*pe, rd));
+            else if (pe->name == "ConvergenceInfoProbe")
+                _probes.push_back(readConvergenceInfoProbe(*pe, rd));
             else if (pe->name == "RadiationFieldProbe")
                 _rfProbeNames.push_back(readRadiationFieldProbe(*pe, rd));
             else
