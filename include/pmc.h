@@ -396,8 +396,11 @@ int pmc_trace_ray(pmc_ctx* ctx, const double r[3], const double k[3], int32_t* m
    without fused multiply-add -- the (m, ds) of pmc_trace_ray for the same ray, added up in double bit for bit.  origins and directions are
    [num_rays][3] (an origin may lie outside the grid; directions normalised by the caller), cell_values is [num_values][num_cells] in the cell
    numbering pmc_trace_ray reports; all host pointers; num_rays may be 0.  The device keeps PMC_INTEGRATE_PASS_VALUES sums per ray in registers:
-   more values take several passes over the rays.  A ray that is still inside the grid after 100000 cells fails the call with PMC_ERR_DEVICE. */
+   more values take several passes over the rays.  A ray that is still inside the grid after 100000 cells fails the call with PMC_ERR_DEVICE.
+   The rays pass through the device in batches of PMC_INTEGRATE_BATCH_RAYS, which bounds the device memory of a call (10 doubles per ray of a
+   batch); every batch makes its own passes. */
 #define PMC_INTEGRATE_PASS_VALUES 4
+#define PMC_INTEGRATE_BATCH_RAYS (1 << 22)
 int pmc_integrate_rays(pmc_ctx* ctx, int64_t num_rays, const double* origins, const double* directions, int32_t num_values,
                        const double* cell_values, double* sums);
 /* work of the most recent pmc_integrate_rays on this context: milliseconds in its kernels (HIP events), cell segments added (lane steps), and

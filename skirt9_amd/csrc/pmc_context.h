@@ -1,9 +1,11 @@
 // pmc_context.h -- what the translation units of the host side of libpmc.so share: the context behind a pmc_ctx handle (as a TableSink it is
-// where the tables of a scene go: device memory), the device buffers of one call, the launchers of pmc_kernels.hip.  pmc_api.hip holds the ABI
-// entry points (pmc_create: the stages of pmc_scene_build.h between the context's resources and the device-side configuration), pmc_tables.h
+// where the tables of a scene go: device memory), the launchers of pmc_kernels.hip, and the frame of a call that runs a kernel outside the
+// photon loop (its device buffers, the scene refresh, the event pair, the cell records of a pass).  pmc_api.hip holds the ABI entry points of the
+// context's life cycle (pmc_create: the stages of pmc_scene_build.h between the context's resources and the device-side configuration), pmc_tables.h
 // the grid tables (octree flattening, binary tree, Voronoi run / cone / observer tables) and the error text of the calling thread, both plain
 // host code; pmc_run.hip the generation loop (pmc_run_primary), pmc_comm.hip the RCCL calls, pmc_tuning.hip the switch table and the test aids of
-// include/pmc_tuning.h, pmc_temperature.hip the dust temperatures (kernel and entry point).
+// include/pmc_tuning.h, pmc_temperature.hip the dust temperatures (kernel and entry point), pmc_probe.hip the ray tracer, the ray integrator
+// and the point sampler.
 #ifndef PMC_CONTEXT_H
 #define PMC_CONTEXT_H
 
@@ -274,6 +276,87 @@ struct CallBuffers
         // (test aid, as in pmc_ctx::allocate: what the call does not write shows)
         if (pmcTune("PMC_POISON_ALLOCATIONS")) return hipMemset(d, 0xA5, std::max(count, size_t(1)) * sizeof(T));
         return hipSuccess;
+    }
+};
+
+// ---- the frame of a call that runs a kernel outside the photon loop (pmc_probe.hip, pmc_temperature.hip, the test aids of pmc_tuning.hip)
+
+// the scene in constant memory, brought up to date after whatever ctx->stream still runs (pmc_run_primary calls it per segment too)
+inline hipError_t sceneUpToDate(pmc_ctx* ctx)
+{
+    if (!ctx->sceneDirty) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = pmcUploadScene(ctx->slot, &ctx->dev, ctx->stream);
+    if (e == hipSuccess) ctx->sceneDirty = false;
+    return e;
+}
+
+// the two HIP events around the kernels of a call: destroyed when the call returns, whichever way
+struct EventPair
+{
+    hipEvent_t a{nullptr}, b{nullptr};
+    ~EventPair()
+    {
+        if (a) hipEventDestroy(a);
+        if (b) hipEventDestroy(b);
+    }
+    int create()
+    {
+        HIP_TRY(hipEventCreate(&a));
+        HIP_TRY(hipEventCreate(&b));
+        return PMC_OK;
+    }
+    hipError_t start(hipStream_t stream) { return hipEventRecord(a, stream); }
+    hipError_t stop(hipStream_t stream) { return hipEventRecord(b, stream); }
+    // between start and stop, once the stream has been synchronised (0 where the runtime does not say)
+    float elapsedMs() const
+    {
+        float ms = 0.f;
+        return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
+    }
+};
+
+// persistent waves: enough workgroups of four waves for every CU's share (the probe kernels stage the grid tables per workgroup), no more than
+// the items fill
+inline int persistentGrid(const pmc_ctx* ctx, size_t items)
+{
+    return int(std::max<size_t>(1, std::min<size_t>((items + 255) / 256, size_t(ctx->numCU) * 4)));
+}
+
+// the caller's cell values as the probe kernels gather them: per pass one record [slot][PMC_INTEGRATE_PASS_VALUES] in the numbering the kernels
+// walk in -- device cells of a tree (cell_ext[device cell] = the caller's m, -1: none), else the caller's
+struct CellRecords
+{
+    static constexpr int W = PMC_INTEGRATE_PASS_VALUES;
+    bool renumbered{false};
+    size_t numCells{0}, slots{0};
+    std::vector<int32_t> ext;
+
+    // `values`: the call has cell values to renumber (a tree's cell_ext is downloaded and checked)
+    int prepare(const DevScene& D, const std::string& name, bool values)
+    {
+        numCells = size_t(D.num_cells);
+        renumbered = D.grid_kind == PMC_GRID_OCTREE || D.grid_kind == PMC_GRID_BINTREE;
+        slots = renumbered ? size_t(D.cell_slots) : numCells;
+        if (!renumbered || !values) return PMC_OK;
+        ext.resize(slots);
+        HIP_TRY(hipMemcpy(ext.data(), D.cell_ext, slots * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int32_t m : ext)
+            if (m >= D.num_cells) return fail(PMC_ERR_DEVICE, name + ": cell numbering table out of range");
+        return PMC_OK;
+    }
+    // the record [slots][W] of pass `pass`: the cell's weight, where there are weights, and the next W (with weights W - 1) of the num_values
+    // rows of cell_values [.][numCells]; zero where a slot has no cell and past the last value
+    void build(double* record, int pass, int num_values, const double* cell_weights, const double* cell_values) const
+    {
+        const int lead = cell_weights ? 1 : 0, perPass = W - lead;
+        const int v0 = pass * perPass, nv = std::min(perPass, num_values - v0);
+        for (size_t c = 0; c < slots; ++c)
+        {
+            const int64_t m = renumbered ? int64_t(ext[c]) : int64_t(c);
+            if (cell_weights) record[c * W] = m >= 0 ? cell_weights[size_t(m)] : 0.;
+            for (int j = 0; j < perPass; ++j) record[c * W + lead + j] = (j < nv && m >= 0) ? cell_values[size_t(v0 + j) * numCells + size_t(m)] : 0.;
+        }
     }
 };
 

@@ -257,12 +257,7 @@ namespace
             if (rc) return rc;
         }
         *numSlots = (int)std::min<int64_t>(want, ctx->allocatedSlots);
-        if (ctx->sceneDirty)
-        {
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            HIP_TRY(pmcUploadScene(ctx->slot, &ctx->dev, ctx->stream));
-            ctx->sceneDirty = false;
-        }
+        HIP_TRY(sceneUpToDate(ctx));
         return PMC_OK;
     }
 

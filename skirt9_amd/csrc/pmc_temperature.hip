@@ -177,28 +177,20 @@ int pmc_dust_temperatures(pmc_ctx* ctx, const pmc_dust_heating* T, double* out)
     HIP_TRY(buffers.get(size_t(H + 1) * numCells, &dOut));
     A.rf = ctx->dev.rf, A.width = dWidth, A.sigma = dSigma, A.planckabs = dPlanck, A.temperature = dTemp, A.cellFactor = dFactor, A.rho = dRho, A.out = dOut;
     A.numCells = T->num_cells, A.numLambda = L, A.numT = NT, A.H = H;
-    hipEvent_t evA = nullptr, evB = nullptr;
-    HIP_TRY(hipEventCreate(&evA));
-    if (hipError_t e = hipEventCreate(&evB); e != hipSuccess)
-    {
-        hipEventDestroy(evA);
-        return hipFail(e, "hipEventCreate");
-    }
+    EventPair timer;
+    if (int rc = timer.create()) return rc;
     const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((numCells + TEMP_BLOCK - 1) / TEMP_BLOCK, size_t(ctx->numCU) * 8));
-    hipError_t e = hipEventRecord(evA, ctx->stream);
+    hipError_t e = timer.start(ctx->stream);
     if (e == hipSuccess)
     {
         hipLaunchKernelGGL(cellTemperatureKernel, dim3(grid), dim3(TEMP_BLOCK), lds, ctx->stream, A);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipEventRecord(evB, ctx->stream);
+    if (e == hipSuccess) e = timer.stop(ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(out, dOut, size_t(H + 1) * numCells * sizeof(double), hipMemcpyDeviceToHost);
-    float ms = 0.f;
-    if (e == hipSuccess && hipEventElapsedTime(&ms, evA, evB) == hipSuccess) ctx->temperatureMs = ms;
-    hipEventDestroy(evA);
-    hipEventDestroy(evB);
     if (e != hipSuccess) return hipFail(e, "pmc_dust_temperatures");
+    ctx->temperatureMs = timer.elapsedMs();
     return PMC_OK;
 }
 

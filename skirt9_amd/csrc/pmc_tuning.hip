@@ -72,14 +72,7 @@ extern "C" int pmc_tune_source_velocities(pmc_ctx* ctx, int32_t source, const do
     HIP_TRY(hipSetDevice(ctx->device));
     double* d = nullptr;
     HIP_TRY(hipMalloc(&d, sizeof(double) * size_t(6 * n)));
-    hipError_t e = hipSuccess;
-    if (ctx->sceneDirty)
-    {
-        // (the scene in constant memory, as pmc_trace_ray brings it up to date)
-        e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = pmcUploadScene(ctx->slot, &ctx->dev, ctx->stream);
-        if (e == hipSuccess) ctx->sceneDirty = false;
-    }
+    hipError_t e = sceneUpToDate(ctx);
     if (e == hipSuccess) e = hipMemcpyAsync(d, r, sizeof(double) * size_t(3 * n), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = pmcLaunchSourceVelocities(ctx->slot, source, d, n, d + 3 * n, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(v_out, d + 3 * n, sizeof(double) * size_t(3 * n), hipMemcpyDeviceToHost, ctx->stream);
@@ -122,16 +115,6 @@ namespace
         if (e == hipSuccess) e = B.get(pmcRfTempBytes(numParts) / sizeof(unsigned long long), &L.temp);
         if (e == hipSuccess) e = hipMemsetAsync(L.sortedKeys, 0, size_t(n) * sizeof(uint32_t), stream);
         if (e == hipSuccess) e = hipMemsetAsync(L.sortedVals, 0, size_t(n) * sizeof(double), stream);
-        return e;
-    }
-
-    // the scene in constant memory, as pmc_trace_ray brings it up to date
-    hipError_t sceneUpToDate(pmc_ctx* ctx)
-    {
-        if (!ctx->sceneDirty) return hipSuccess;
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = pmcUploadScene(ctx->slot, &ctx->dev, ctx->stream);
-        if (e == hipSuccess) ctx->sceneDirty = false;
         return e;
     }
 }

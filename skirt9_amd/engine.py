@@ -173,6 +173,8 @@ def lib():
 # settings the library itself reads from the environment (include/pmc.h); every other PMC_* name is a tuning switch
 # values whose sums pmc_integrate_rays keeps in registers per pass over the rays (include/pmc.h PMC_INTEGRATE_PASS_VALUES)
 INTEGRATE_PASS_VALUES = 4
+# rays that pmc_integrate_rays keeps on the device at a time (include/pmc.h PMC_INTEGRATE_BATCH_RAYS)
+INTEGRATE_BATCH_RAYS = 1 << 22
 # points that pmc_sample_cells keeps on the device at a time (include/pmc.h PMC_SAMPLE_CHUNK_POINTS)
 SAMPLE_CHUNK_POINTS = 1 << 20
 

@@ -452,49 +452,42 @@ class Simulation:
                 engine.temperatures = getattr(integrator, "temperature_callback", lambda: (None, None))()[0]
                 if rf is None and integrator.radiation_field_size == self.radiation_field_size:
                     rf = integrator.download_radiation_field()
-        elif integrator is not None:
-            def call(_, n, origins, directions, num_values, values, sums):
+
+        def array(pointer, *shape):
+            return np.ctypeslib.as_array(pointer, shape=shape)
+
+        def trampoline(prototype, body):
+            # a C function of `prototype` around body(the arguments after `user`): 0, or 1 with the exception kept for below
+            def call(_, *arguments):
                 try:
-                    r = np.ctypeslib.as_array(origins, shape=(n, 3))
-                    k = np.ctypeslib.as_array(directions, shape=(n, 3))
-                    q = np.ctypeslib.as_array(values, shape=(num_values, num_cells))
-                    np.ctypeslib.as_array(sums, shape=(n, num_values))[:] = np.asarray(integrator(r, k, q), dtype=np.float64).reshape(n, num_values)
+                    body(*arguments)
                     return 0
                 except Exception as error:  # (an exception must not cross the C frames: reported below)
                     failure.append(error)
                     return 1
 
-            keep.append(INTEGRATE_FN(call))
-            engine.integrate = C.cast(keep[-1], C.c_void_p)
+            keep.append(prototype(call))
+            return C.cast(keep[-1], C.c_void_p)
+
+        if integrator is not None and not hasattr(integrator, "integrate_callback"):
+            def call(n, origins, directions, num_values, values, sums):
+                result = integrator(array(origins, n, 3), array(directions, n, 3), array(values, num_values, num_cells))
+                array(sums, n, num_values)[:] = np.asarray(result, dtype=np.float64).reshape(n, num_values)
+
+            engine.integrate = trampoline(INTEGRATE_FN, call)
         if weighted is not None:
-            def call_weighted(_, n, origins, directions, num_values, weights, values, sums):
-                try:
-                    r = np.ctypeslib.as_array(origins, shape=(n, 3))
-                    k = np.ctypeslib.as_array(directions, shape=(n, 3))
-                    w = np.ctypeslib.as_array(weights, shape=(num_cells,))
-                    q = np.ctypeslib.as_array(values, shape=(num_values, num_cells))
-                    result = np.asarray(weighted(r, k, w, q), dtype=np.float64).reshape(n, 1 + num_values)
-                    np.ctypeslib.as_array(sums, shape=(n, 1 + num_values))[:] = result
-                    return 0
-                except Exception as error:
-                    failure.append(error)
-                    return 1
+            def call_weighted(n, origins, directions, num_values, weights, values, sums):
+                result = weighted(array(origins, n, 3), array(directions, n, 3), array(weights, num_cells), array(values, num_values, num_cells))
+                array(sums, n, 1 + num_values)[:] = np.asarray(result, dtype=np.float64).reshape(n, 1 + num_values)
 
-            keep.append(INTEGRATE_WEIGHTED_FN(call_weighted))
-            engine.integrate_weighted = C.cast(keep[-1], C.c_void_p)
+            engine.integrate_weighted = trampoline(INTEGRATE_WEIGHTED_FN, call_weighted)
         if temperatures is not None:
-            def call_temperatures(_, tables, out):
-                try:
-                    struct = DustHeating.from_address(tables)
-                    shape = (struct.num_components + 1, struct.num_cells)
-                    np.ctypeslib.as_array(out, shape=shape)[:] = np.asarray(temperatures(heating_tables_from(struct)), dtype=np.float64).reshape(shape)
-                    return 0
-                except Exception as error:
-                    failure.append(error)
-                    return 1
+            def call_temperatures(tables, out):
+                struct = DustHeating.from_address(tables)
+                shape = (struct.num_components + 1, struct.num_cells)
+                array(out, *shape)[:] = np.asarray(temperatures(heating_tables_from(struct)), dtype=np.float64).reshape(shape)
 
-            keep.append(TEMPERATURE_FN(call_temperatures))
-            engine.temperatures = C.cast(keep[-1], C.c_void_p)
+            engine.temperatures = trampoline(TEMPERATURE_FN, call_temperatures)
         if rf is not None:
             table = np.ascontiguousarray(rf, dtype=np.float64).reshape(-1)
             assert table.size == self.radiation_field_size
@@ -508,20 +501,13 @@ class Simulation:
                 raise ValueError("integrator and sampler must be the same engine")
             engine.user = user
         elif sampler is not None:
-            def call_sample(_, n, positions, num_values, values, out, cells):
-                try:
-                    r = np.ctypeslib.as_array(positions, shape=(n, 3))
-                    q = np.ctypeslib.as_array(values, shape=(num_values, num_cells))
-                    np.ctypeslib.as_array(out, shape=(num_values, n))[:] = np.asarray(sampler(r, q), dtype=np.float64).reshape(num_values, n)
-                    if cells:
-                        np.ctypeslib.as_array(cells, shape=(n,))[:] = self.cell_indices(r)
-                    return 0
-                except Exception as error:
-                    failure.append(error)
-                    return 1
+            def call_sample(n, positions, num_values, values, out, cells):
+                r = array(positions, n, 3)
+                array(out, num_values, n)[:] = np.asarray(sampler(r, array(values, num_values, num_cells)), dtype=np.float64).reshape(num_values, n)
+                if cells:
+                    array(cells, n)[:] = self.cell_indices(r)
 
-            keep.append(SAMPLE_FN(call_sample))
-            sample = C.cast(keep[-1], C.c_void_p)
+            sample = trampoline(SAMPLE_FN, call_sample)
         if lib().skh_write_probes_sampled(self._h, C.byref(engine), sample, os.fsencode(outdir), code) != 0:
             if failure:
                 raise failure[0]

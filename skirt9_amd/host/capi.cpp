@@ -5,14 +5,32 @@
 #include "simulation.hpp"
 #include <cstring>
 #include <fstream>
+#include <type_traits>
 
 namespace
 {
     thread_local std::string t_error;
-    int fail(const std::exception& e)
+
+    // the frame of an entry point that can fail: "invalid argument" unless `valid`, then what the body returns (0 for a body that returns
+    // nothing); an exception leaves its text for skh_last_error and makes -1
+    template<typename Body> int guarded(bool valid, Body&& body)
     {
-        t_error = e.what();
-        return -1;
+        try
+        {
+            if (!valid) throw std::runtime_error("invalid argument");
+            if constexpr (std::is_void_v<decltype(body())>)
+            {
+                body();
+                return 0;
+            }
+            else
+                return body();
+        }
+        catch (const std::exception& e)
+        {
+            t_error = e.what();
+            return -1;
+        }
     }
 }
 
@@ -28,6 +46,29 @@ struct skh_simulation
     std::unique_ptr<skh::Simulation> sim;
 };
 
+namespace
+{
+    bool loaded(const skh_simulation* h) { return h && h->sim; }
+
+    // the one path of the four skh_write_probes* entry points: the caller's engine (null: none) and sampler as the simulation takes them
+    int writeProbes(const skh_simulation* h, bool valid, const skh_probe_engine* engine, skh_sample_fn sample, const char* outdir, int32_t when)
+    {
+        return guarded(loaded(h) && valid && outdir, [&] {
+            skh::Simulation::ProbeEngine e;
+            if (engine)
+            {
+                e.integrate = engine->integrate;
+                e.weighted = engine->integrate_weighted;
+                e.temperatures = engine->temperatures;
+                e.user = engine->user;
+                e.rf = engine->rf;
+            }
+            e.sample = sample;
+            h->sim->writeProbes(e, outdir, when);
+        });
+    }
+}
+
 extern "C" {
 
 const char* skh_last_error(void)
@@ -37,17 +78,10 @@ const char* skh_last_error(void)
 
 skh_simulation* skh_load(const char* ski_path)
 {
-    try
-    {
-        // (the simulation first: a refused ski file leaves no handle behind)
-        auto sim = skh::Simulation::fromFile(ski_path);
-        return new skh_simulation{std::move(sim)};
-    }
-    catch (const std::exception& e)
-    {
-        fail(e);
-        return nullptr;
-    }
+    skh_simulation* result = nullptr;
+    // (the simulation first: a refused ski file leaves no handle behind)
+    guarded(true, [&] { result = new skh_simulation{skh::Simulation::fromFile(ski_path)}; });
+    return result;
 }
 
 void skh_free(skh_simulation* h)
@@ -65,9 +99,7 @@ int skh_set_num_packets(skh_simulation* h, uint64_t n)
 // to the simulation: the densities of an imported particle medium are then evaluated on the GPU during skh_setup.
 int skh_set_particle_sampler(skh_simulation* h, void* create, void* density, void* destroy, void* last_error, int32_t device)
 {
-    try
-    {
-        if (!h || !h->sim || !create || !density || !destroy) throw std::runtime_error("invalid argument");
+    return guarded(loaded(h) && create && density && destroy, [&] {
         skh::ParticleSamplerApi api;
         api.create = reinterpret_cast<int (*)(const pmc_particles*, int32_t, pmc_sampler**)>(create);
         api.density = reinterpret_cast<int (*)(pmc_sampler*, const double*, int64_t, double*)>(density);
@@ -75,18 +107,12 @@ int skh_set_particle_sampler(skh_simulation* h, void* create, void* density, voi
         api.lastError = reinterpret_cast<const char* (*)()>(last_error);
         api.device = device;
         h->sim->setParticleSampler(api);
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    });
 }
 
 int skh_set_tree_topology_file(skh_simulation* h, const char* path)
 {
-    try
-    {
+    return guarded(true, [&] {
         // TreeSpatialGridTopologyProbe format (TreeSpatialGrid.cpp:225-251): comment lines, the number of children
         // of the root, then one "1"/"0" per node in depth-first order
         std::ifstream in(path);
@@ -106,25 +132,12 @@ int skh_set_tree_topology_file(skh_simulation* h, const char* path)
             topology.push_back(line[0] == '1');
         }
         h->sim->setTreeTopology(std::move(topology));
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    });
 }
 
 int skh_setup(skh_simulation* h)
 {
-    try
-    {
-        h->sim->setup();
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return guarded(true, [&] { h->sim->setup(); });
 }
 
 const pmc_scene* skh_scene(const skh_simulation* h)
@@ -173,68 +186,34 @@ int skh_frame_layout(const skh_simulation* h, int32_t instrument, pmc_frame_layo
 
 int skh_write(const skh_simulation* h, double* frames, const char* outdir)
 {
-    try
-    {
-        h->sim->write(frames, outdir);
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return guarded(true, [&] { h->sim->write(frames, outdir); });
 }
 
 // number of doubles of the radiation field table (0: the simulation does not store it)
 int64_t skh_radiation_field_size(const skh_simulation* h)
 {
-    return h && h->sim ? h->sim->radiationFieldSize() : 0;
+    return loaded(h) ? h->sim->radiationFieldSize() : 0;
+}
+
+int skh_write_fluxes_only(const skh_simulation* h, double* frames, const char* outdir)
+{
+    return guarded(true, [&] { h->sim->write(frames, outdir, false); });
 }
 
 // writes the RadiationFieldProbe files from the table rf[m * nbins + ell]
-int skh_write_fluxes_only(const skh_simulation* h, double* frames, const char* outdir)
-{
-    try
-    {
-        h->sim->write(frames, outdir, false);
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
-}
-
 int skh_write_radiation_field(const skh_simulation* h, const double* rf, const char* outdir)
 {
-    try
-    {
-        if (!h || !h->sim || !rf || !outdir) throw std::runtime_error("invalid argument");
-        h->sim->writeRadiationField(rf, outdir);
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return guarded(loaded(h) && rf && outdir, [&] { h->sim->writeRadiationField(rf, outdir); });
 }
 
 int32_t skh_num_probe_maps(const skh_simulation* h)
 {
-    try
-    {
-        return h && h->sim ? h->sim->numProbeMaps() : 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return guarded(true, [&] { return loaded(h) ? h->sim->numProbeMaps() : 0; });
 }
 
 int skh_probe_map_info(const skh_simulation* h, int32_t map, skh_probe_map* out)
 {
-    try
-    {
-        if (!h || !h->sim || !out) throw std::runtime_error("invalid argument");
+    return guarded(loaded(h) && out, [&] {
         const skh::Simulation::ProbeMapInfo info = h->sim->probeMapInfo(map);
         std::memset(out, 0, sizeof(*out));
         if (info.fileName.size() >= sizeof(out->file_name)) throw std::runtime_error("probe file name too long");
@@ -244,79 +223,35 @@ int skh_probe_map_info(const skh_simulation* h, int32_t map, skh_probe_map* out)
         out->num_values = info.numValues;
         out->after_setup = info.afterSetup ? 1 : 0;
         out->num_rays = info.numRays;
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    });
 }
 
 int32_t skh_probe_map_averaged(const skh_simulation* h, int32_t map)
 {
-    try
-    {
-        if (!h || !h->sim) throw std::runtime_error("invalid argument");
-        return h->sim->probeMapInfo(map).averaged ? 1 : 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return guarded(loaded(h), [&] { return h->sim->probeMapInfo(map).averaged ? 1 : 0; });
 }
 
 int32_t skh_probes_need_radiation_field(const skh_simulation* h, int32_t when)
 {
-    try
-    {
-        return h && h->sim && h->sim->probesNeedRadiationField(when) ? 1 : 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return guarded(true, [&] { return loaded(h) && h->sim->probesNeedRadiationField(when) ? 1 : 0; });
 }
 
 int skh_probe_map_rays(const skh_simulation* h, int32_t map, double* origins, double* directions)
 {
-    try
-    {
-        if (!h || !h->sim || !origins || !directions) throw std::runtime_error("invalid argument");
-        h->sim->probeMapRays(map, origins, directions);
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return guarded(loaded(h) && origins && directions, [&] { h->sim->probeMapRays(map, origins, directions); });
 }
 
 int skh_probe_map_values(const skh_simulation* h, int32_t map, double* cell_values)
 {
-    try
-    {
-        if (!h || !h->sim || !cell_values) throw std::runtime_error("invalid argument");
-        h->sim->probeMapValues(map, cell_values);
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return guarded(loaded(h) && cell_values, [&] { h->sim->probeMapValues(map, cell_values); });
 }
 
 int skh_write_probes_when(const skh_simulation* h, skh_integrate_fn integrate, void* user, const char* outdir, int32_t when)
 {
-    try
-    {
-        if (!h || !h->sim || !outdir) throw std::runtime_error("invalid argument");
-        h->sim->writeProbes(integrate, user, outdir, when);
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    skh_probe_engine engine{};
+    engine.integrate = integrate;
+    engine.user = user;
+    return writeProbes(h, true, &engine, nullptr, outdir, when);
 }
 
 int skh_write_probes(const skh_simulation* h, skh_integrate_fn integrate, void* user, const char* outdir)
@@ -326,134 +261,55 @@ int skh_write_probes(const skh_simulation* h, skh_integrate_fn integrate, void* 
 
 int skh_write_probes_with(const skh_simulation* h, const skh_probe_engine* engine, const char* outdir, int32_t when)
 {
-    try
-    {
-        if (!h || !h->sim || !engine || !outdir) throw std::runtime_error("invalid argument");
-        skh::Simulation::ProbeEngine e;
-        e.integrate = engine->integrate;
-        e.weighted = engine->integrate_weighted;
-        e.temperatures = engine->temperatures;
-        e.user = engine->user;
-        e.rf = engine->rf;
-        h->sim->writeProbes(e, outdir, when);
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return writeProbes(h, engine != nullptr, engine, nullptr, outdir, when);
 }
 
 int skh_write_probes_sampled(const skh_simulation* h, const skh_probe_engine* engine, skh_sample_fn sample, const char* outdir, int32_t when)
 {
-    try
-    {
-        if (!h || !h->sim || !outdir) throw std::runtime_error("invalid argument");
-        skh::Simulation::ProbeEngine e;
-        if (engine)
-        {
-            e.integrate = engine->integrate;
-            e.weighted = engine->integrate_weighted;
-            e.temperatures = engine->temperatures;
-            e.user = engine->user;
-            e.rf = engine->rf;
-        }
-        e.sample = sample;
-        h->sim->writeProbes(e, outdir, when);
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return writeProbes(h, true, engine, sample, outdir, when);
 }
 
 int32_t skh_dimension(const skh_simulation* h)
 {
-    try
-    {
-        if (!h || !h->sim) throw std::runtime_error("invalid argument");
-        return h->sim->dimension();
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return guarded(loaded(h), [&] { return h->sim->dimension(); });
 }
 
 int skh_dust_heating(const skh_simulation* h, pmc_dust_heating* out)
 {
-    try
-    {
-        if (!h || !h->sim || !out) throw std::runtime_error("invalid argument");
-        *out = h->sim->dustHeating().flat;
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return guarded(loaded(h) && out, [&] { *out = h->sim->dustHeating().flat; });
 }
 
 int32_t skh_dust_components(const skh_simulation* h, int32_t* components)
 {
-    try
-    {
-        if (!h || !h->sim || !h->sim->hasDustHeating()) return 0;
+    return guarded(true, [&] {
+        if (!loaded(h) || !h->sim->hasDustHeating()) return 0;
         const std::vector<int>& dust = h->sim->dustHeating().components;
         for (size_t b = 0; components && b != dust.size(); ++b) components[b] = dust[b];
-        return static_cast<int32_t>(dust.size());
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+        return static_cast<int>(dust.size());
+    });
 }
 
 int skh_dust_temperatures(const skh_simulation* h, const double* rf, double* out)
 {
-    try
-    {
-        if (!h || !h->sim || !rf || !out) throw std::runtime_error("invalid argument");
-        h->sim->dustTemperatures(rf, out);
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    return guarded(loaded(h) && rf && out, [&] { h->sim->dustTemperatures(rf, out); });
 }
 
 int skh_dust_temperatures_from(const pmc_dust_heating* tables, const double* rf, double* out)
 {
-    try
-    {
-        if (!tables || !rf || !out) throw std::runtime_error("invalid argument");
+    return guarded(tables && rf && out, [&] {
         if (!tables->width || !tables->sigma || !tables->planckabs || !tables->temperature || !tables->cell_factor || !tables->mass_density)
             throw std::runtime_error("null table");
         skh::Simulation::dustTemperatures(*tables, rf, out);
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    });
 }
 
 int skh_cell_indices(const skh_simulation* h, int64_t num_points, const double* positions, int32_t* cells)
 {
-    try
-    {
-        if (!h || !h->sim || num_points < 0 || (num_points > 0 && (!positions || !cells))) throw std::runtime_error("invalid argument");
+    return guarded(loaded(h) && num_points >= 0 && (num_points == 0 || (positions && cells)), [&] {
         const skh::SpatialGrid& grid = h->sim->grid();
         for (int64_t p = 0; p < num_points; ++p)
             cells[p] = grid.cellIndex(skh::Vec3{positions[3 * p], positions[3 * p + 1], positions[3 * p + 2]});
-        return 0;
-    }
-    catch (const std::exception& e)
-    {
-        return fail(e);
-    }
+    });
 }
 
 int skh_summary(const skh_simulation* h, char* buffer, int32_t capacity)

@@ -227,14 +227,14 @@ namespace skh
                 if (unit.empty()) unit = "1";
                 line("# column " + std::to_string(++_ncolumns) + ": " + quantity + " (" + unit + ")");
             }
-            void row(const std::vector<double>& values)
+            // (the values behind `s`, what a row of integer format begins with)
+            void row(const std::vector<double>& values, std::string s = std::string())
             {
-                std::string s;
-                for (size_t i = 0; i < values.size(); ++i)
+                for (double value : values)
                 {
                     char buf[40];
-                    snprintf(buf, sizeof(buf), "%1.9e", values[i]);
-                    s += (i ? " " : "");
+                    snprintf(buf, sizeof(buf), "%1.9e", value);
+                    s += (s.empty() ? "" : " ");
                     s += buf;
                 }
                 line(s);
@@ -249,6 +249,30 @@ namespace skh
     int64_t Simulation::radiationFieldSize() const
     {
         return _storeRadiationField ? static_cast<int64_t>(_grid->numCells()) * _rfGrid->numBins() : 0;
+    }
+
+    // PerCellForm::writeQuantity through TextOutFile (PerCellForm.cpp:14-38, TextOutFile.cpp:61-103): the title, a column for the cell index (an
+    // integer column: the digits of m, which is what 'd' and "%1.0f" both print) and one per value -- `quantity` alone, or per output
+    // wavelength "<quantity> at lambda = <'g', six digits> <unit>" --, then the rows that `fill` computes, 'e' with 9 digits
+    void Simulation::writePerCellTable(const std::string& path, const std::string& title, const std::string& quantity, const std::string& unit,
+                                       const Array& outWavelengths, const CellRowFn& fill) const
+    {
+        TextColumns out(path);
+        out.line("# " + title);
+        out.column("spatial cell index");
+        if (outWavelengths.empty()) out.column(quantity, unit);
+        for (double wave : outWavelengths)
+        {
+            char buf[40];
+            snprintf(buf, sizeof(buf), "%1.6g", wave);
+            out.column(quantity + " at " + _units.swavelength() + " = " + buf + " " + _units.uwavelength(), unit);
+        }
+        std::vector<double> row(std::max<size_t>(outWavelengths.size(), 1));
+        for (int m = 0, numCells = _grid->numCells(); m != numCells; ++m)
+        {
+            fill(m, row.data());
+            out.row(row, std::to_string(m));
+        }
     }
 
     // RadiationFieldProbe::probe with a PerCellForm (RadiationFieldProbe.cpp:27-78, PerCellForm.cpp:14-32): the mean
@@ -267,39 +291,26 @@ namespace skh
         const bool reverse = _units.wavelengthStyle != "Wavelength";
         std::vector<int> order(nbins);
         for (int i = 0; i != nbins; ++i) order[i] = reverse ? nbins - 1 - i : i;
-        Array conv(nbins);
-        for (int i = 0; i != nbins; ++i) conv[i] = _units.omeanintensity(wlg.wavelength(order[i]), 1.);
+        Array conv(nbins), outWavelengths(nbins);
+        for (int i = 0; i != nbins; ++i)
+        {
+            conv[i] = _units.omeanintensity(wlg.wavelength(order[i]), 1.);
+            outWavelengths[i] = _units.owavelength(wlg.wavelength(order[i]));
+        }
         for (const std::string& name : _rfProbeNames)
         {
-            std::string path = base + name + "_J.dat";
-            std::ofstream out(path);
-            if (!out) throw std::runtime_error("Could not open output file " + path);
-            out << "# Mean intensity per spatial cell" << std::endl;
-            out << "# column 1: spatial cell index (1)" << std::endl;
-            for (int i = 0; i != nbins; ++i)
-            {
-                char buf[40];
-                snprintf(buf, sizeof(buf), "%1.6g", _units.owavelength(wlg.wavelength(order[i])));
-                out << "# column " << (i + 2) << ": " << _units.smeanintensity() << " at " << _units.swavelength() << " = " << buf
-                    << " " << _units.uwavelength() << " (" << _units.umeanintensity() << ")" << std::endl;
-            }
-            const int numCells = _grid->numCells();
-            for (int m = 0; m != numCells; ++m)
-            {
-                // MediumSystem::meanIntensity
-                double factor = 1. / (4. * M_PI * _grid->volume(m));
-                std::string line = std::to_string(m);
-                for (int i = 0; i != nbins; ++i)
-                {
-                    int ell = order[i];
-                    double J = rf[static_cast<size_t>(m) * nbins + ell] * factor / wlg.effectiveWidth(ell);
-                    char buf[40];
-                    snprintf(buf, sizeof(buf), " %1.9e", conv[i] * J);
-                    line += buf;
-                }
-                out << line << std::endl;
-            }
-            files.push_back(path);
+            files.push_back(base + name + "_J.dat");
+            writePerCellTable(files.back(), "Mean intensity per spatial cell", _units.smeanintensity(), _units.umeanintensity(), outWavelengths,
+                              [&](int m, double* row) {
+                                  // MediumSystem::meanIntensity
+                                  const double factor = 1. / (4. * M_PI * _grid->volume(m));
+                                  for (int i = 0; i != nbins; ++i)
+                                  {
+                                      const int ell = order[i];
+                                      const double J = rf[static_cast<size_t>(m) * nbins + ell] * factor / wlg.effectiveWidth(ell);
+                                      row[i] = conv[i] * J;
+                                  }
+                              });
         }
         return files;
     }

@@ -33,18 +33,23 @@ namespace skh
         int numValues() const { return compound ? static_cast<int>(axis.size()) : 1; }
     };
 
+    std::vector<int> Simulation::componentsOfType(bool electrons) const
+    {
+        std::vector<int> components;
+        for (int h = 0; h != static_cast<int>(_media.size()); ++h)
+            if (_media[h]->mix->isElectrons() == electrons) components.push_back(h);
+        return components;
+    }
+
     std::vector<Simulation::ProbeQuantity> Simulation::probeQuantities(const ProbeModel& probe) const
     {
         std::vector<ProbeQuantity> result;
         if (!_hasMedium) return result;  // DensityProbe.cpp:16, OpacityProbe.cpp:39
         const int numMedia = static_cast<int>(_media.size());
-        std::vector<int> dust, electrons, all;
-        for (int h = 0; h != numMedia; ++h)
-        {
-            (_media[h]->mix->isElectrons() ? electrons : dust).push_back(h);
-            all.push_back(h);
-        }
-        if (probe.type == "DustAbsorptionPerCellProbe") return result;  // (a file of its own kind: writeProbes)
+        const std::vector<int> dust = componentsOfType(false), electrons = componentsOfType(true);
+        std::vector<int> all;
+        for (int h = 0; h != numMedia; ++h) all.push_back(h);
+        if (probe.type == "DustAbsorptionPerCellProbe") return result;  // (a file of its own kind: writeDustAbsorption)
         if (probe.type == "TemperatureProbe")
         {
             // TemperatureProbe.cpp:45-79: dust only, and only with a panchromatic radiation field (the electron components of this path
@@ -267,10 +272,8 @@ namespace skh
 
     bool Simulation::probesNeedRadiationField(int when) const
     {
-        if (!_hasMedium || !_storeRadiationField) return false;
-        bool hasDust = false;  // (MediumSystem::hasDust: without dust neither probe writes a file)
-        for (const auto& part : _media) hasDust = hasDust || !part->mix->isElectrons();
-        if (!hasDust) return false;
+        // (MediumSystem::hasDust: without dust neither probe writes a file)
+        if (!_hasMedium || !_storeRadiationField || componentsOfType(false).empty()) return false;
         for (const ProbeModel& probe : _probes)
         {
             if (when >= 0 && (when == 0) != probe.afterSetup) continue;
@@ -279,13 +282,23 @@ namespace skh
         return false;
     }
 
+    // what the writers of one writeProbes call share
+    struct Simulation::ProbeOutput
+    {
+        const ProbeEngine& engine;
+        std::string base;                  // <outdir>/<prefix>_
+        std::vector<std::string> files;    // written so far
+        std::vector<double> temperatures;  // [H + 1][numCells], once a probe has asked for them (Simulation::probeTemperatures)
+    };
+
     // ConvergenceInfoProbe::probe (ConvergenceInfoProbe.cpp:17-175): <prefix>_<probe>_convergence.dat.  Per material type present the input
     // mass against the gridded mass, the input optical depth along the coordinate axes (Medium::opticalDepthX/Y/Z) against the gridded one --
     // two rays per axis from (eps, eps, eps), eps = 1e-15 diagonals of the grid, through the caller's integrator with the opacity of that type
     // as the cell value: MediumSystem::getExtinctionOpticalDepth(path, lambda, type), MediumSystem.cpp:1264-1275 --, then the statistics of the
     // cells' diagonal optical depths.  Line formats: writeValues, StringUtils::toString 'g' with 6 digits, the percentage 'f' with 2
-    std::string Simulation::writeConvergenceInfo(const ProbeModel& probe, const ProbeEngine& engine, const std::string& base) const
+    void Simulation::writeConvergenceInfo(const ProbeModel& probe, ProbeOutput& output) const
     {
+        const ProbeEngine& engine = output.engine;
         if (!engine.integrate)
             throw std::runtime_error("probe " + probe.name + " (ConvergenceInfoProbe) needs an integrator for its gridded optical depths");
         const int numMedia = static_cast<int>(_media.size());
@@ -296,7 +309,7 @@ namespace skh
             snprintf(buf, sizeof(buf), format == 'f' ? "%1.*f" : "%1.*g", precision, value);
             return std::string(buf);
         };
-        const std::string path = base + probe.name + "_convergence.dat";
+        const std::string path = output.base + probe.name + "_convergence.dat";
         std::ofstream out(path);
         if (!out) throw std::runtime_error("Could not open output file " + path);
         auto line = [&](const std::string& text) { out << text << std::endl; };
@@ -314,9 +327,7 @@ namespace skh
         for (int h = 0; h != numMedia; ++h) all.push_back(h);
         for (int kind = 0; kind != 2; ++kind)
         {
-            std::vector<int> components;
-            for (int h = 0; h != numMedia; ++h)
-                if (_media[h]->mix->isElectrons() == (kind == 1)) components.push_back(h);
+            const std::vector<int> components = componentsOfType(kind == 1);
             if (components.empty()) continue;  // MediumSystem::hasDust / hasElectrons
             line("");
             line(std::string("------ ") + (kind ? "Electrons" : "Dust") + " ------");
@@ -400,23 +411,23 @@ namespace skh
         }
         line("");
         line("------------------------------------");
-        return path;
+        output.files.push_back(path);
     }
 
-    // ConvergenceCutsProbe::probe (ConvergenceCutsProbe.cpp:23-60) with its hard-coded DefaultCutsForm (DefaultCutsForm.cpp:20-34) and
-    // PlanarCutsForm::writePlanarCut (PlanarCutsForm.cpp:32-103): per material type the true density (an InputScalar quantity: the media's
-    // own density at the position, times the unit factor) and the gridded density (a GridScalarAccumulated quantity:
-    // ProbeFormBridge::valuesAtPosition, the value of the cell at cellIndex(position) times the unit factor, 0 outside) on 1024 x 1024
-    // positions per coordinate plane.  The true density is evaluated here (Medium::massDensities / numberDensities: all host cores, or the
-    // device sampler of an imported medium); the gridded one by the caller's point sampler, with the unit factor multiplied into the cell
-    // values beforehand (valuesInCell: one rounding)
-    void Simulation::writeConvergenceCuts(const ProbeModel& probe, const ProbeEngine& engine, const std::string& base, std::vector<std::string>& files) const
+    // a coordinate plane through the origin: the axes that run (xy: i along x, j along y; xz: x, z; yz: y, z) and its name in file names
+    struct Simulation::CutPlane
     {
-        if (!engine.sample)
-            throw std::runtime_error("probe " + probe.name + " (ConvergenceCutsProbe) needs a sampler: hand over the engine's pmc_sample_cells");
-        constexpr int Np = 1024;
-        const int numCells = _grid->numCells();
-        const int dim = dimension();
+        bool xd, yd, zd;
+        const char* name;
+    };
+
+    // PlanarCutsForm::writePlanarCut (PlanarCutsForm.cpp:32-103) as DefaultCutsForm calls it (DefaultCutsForm.cpp:20-34): the grid's bounding
+    // box in 1024 x 1024 pixels of a coordinate plane, the values that `valuesAt` gives at the pixel centres -- in output units of `quantity`,
+    // [j][i] -- and the axes of the FITS file
+    void Simulation::writePlanarCut(const std::string& path, const CutPlane& plane, const std::string& quantity, const CutValuesFn& valuesAt,
+                                    ProbeOutput& output) const
+    {
+        constexpr int Np = 1024, Ni = Np, Nj = Np;
         const Box box = _grid->extent;
         // PlanarCutsForm.cpp:36-44
         const double xpsize = (box.xmax - box.xmin) / Np;
@@ -427,25 +438,46 @@ namespace skh
         const double zbase = box.zmin + 0.5 * zpsize;
         const Vec3 center = box.center();
         const double xp = 0., yp = 0., zp = 0.;
-
-        std::vector<int> dust, electrons;
-        for (int h = 0; h != static_cast<int>(_media.size()); ++h) (_media[h]->mix->isElectrons() ? electrons : dust).push_back(h);
-        struct Plane
+        std::vector<Vec3> positions(size_t(Ni) * Nj);
+        for (int j = 0; j != Nj; ++j)
         {
-            bool xd, yd, zd;
-            const char* name;
-        };
-        std::vector<Plane> planes{{true, true, false, "xy"}};
+            const double z = plane.zd ? (zbase + j * zpsize) : zp;
+            for (int i = 0; i != Ni; ++i)
+            {
+                const double x = plane.xd ? (xbase + i * xpsize) : xp;
+                const double y = plane.yd ? (ybase + (plane.zd ? i : j) * ypsize) : yp;
+                positions[size_t(j) * Ni + i] = Vec3{x, y, z};
+            }
+        }
+        Array vvv(positions.size(), 0.);
+        valuesAt(positions, vvv);
+        writeFitsCube(path, vvv.data(), _units.unit(quantity), Ni, Nj, _units.out("length", plane.xd ? xpsize : ypsize),
+                      _units.out("length", plane.zd ? zpsize : ypsize), _units.out("length", plane.xd ? center.x : center.y),
+                      _units.out("length", plane.zd ? center.z : center.y), _units.unit("length"), Array(), std::string("1"), nullptr);
+        output.files.push_back(path);
+    }
+
+    // ConvergenceCutsProbe::probe (ConvergenceCutsProbe.cpp:23-60) with its hard-coded DefaultCutsForm: per material type the true density (an
+    // InputScalar quantity: the media's own density at the position, times the unit factor) and the gridded density (a GridScalarAccumulated
+    // quantity: ProbeFormBridge::valuesAtPosition, the value of the cell at cellIndex(position) times the unit factor, 0 outside) on every
+    // coordinate plane of the model's dimension.  The true density is evaluated here (Medium::massDensities / numberDensities: all host cores,
+    // or the device sampler of an imported medium); the gridded one by the caller's point sampler, with the unit factor multiplied into the
+    // cell values beforehand (valuesInCell: one rounding)
+    void Simulation::writeConvergenceCuts(const ProbeModel& probe, ProbeOutput& output) const
+    {
+        const ProbeEngine& engine = output.engine;
+        if (!engine.sample)
+            throw std::runtime_error("probe " + probe.name + " (ConvergenceCutsProbe) needs a sampler: hand over the engine's pmc_sample_cells");
+        const int numCells = _grid->numCells();
+        const int dim = dimension();
+        std::vector<CutPlane> planes{{true, true, false, "xy"}};
         if (dim >= 2) planes.push_back({true, false, true, "xz"});
         if (dim == 3) planes.push_back({false, true, true, "yz"});
-
-        std::vector<Vec3> positions(size_t(Np) * Np);
-        std::vector<double> flat(3 * positions.size()), one, cellValues(numCells);
-        Array vvv(positions.size());
+        std::vector<double> flat, one, cellValues(numCells);
         for (int kind = 0; kind != 2; ++kind)
         {
             const bool mass = kind == 0;
-            const std::vector<int>& components = mass ? dust : electrons;
+            const std::vector<int> components = componentsOfType(!mass);
             if (components.empty()) continue;  // MediumSystem::hasDust / hasElectrons
             const std::string quantity = mass ? "massvolumedensity" : "numbervolumedensity";
             const double unitFactor = _units.out(quantity, 1.);
@@ -453,254 +485,203 @@ namespace skh
             q.kind = mass ? ProbeQuantity::MassDensity : ProbeQuantity::NumberDensity;
             q.components = components;
             for (int m = 0; m != numCells; ++m) cellValues[m] = probeCellValue(q, 0, m) * unitFactor;
-            for (int gridded = 0; gridded != 2; ++gridded)
-                for (const Plane& plane : planes)
+            // MediumSystem::dustMassDensity(Position) / electronNumberDensity(Position) (MediumSystem.cpp:456-470): the sum over the components in
+            // order, then the unit factor
+            const CutValuesFn trueDensity = [&](const std::vector<Vec3>& positions, Array& vvv) {
+                for (int h : components)
                 {
-                    const int Ni = Np, Nj = Np;
-                    for (int j = 0; j != Nj; ++j)
-                    {
-                        const double z = plane.zd ? (zbase + j * zpsize) : zp;
-                        for (int i = 0; i != Ni; ++i)
-                        {
-                            const double x = plane.xd ? (xbase + i * xpsize) : xp;
-                            const double y = plane.yd ? (ybase + (plane.zd ? i : j) * ypsize) : yp;
-                            positions[size_t(j) * Ni + i] = Vec3{x, y, z};
-                        }
-                    }
-                    if (!gridded)
-                    {
-                        // MediumSystem::dustMassDensity(Position) / electronNumberDensity(Position) (MediumSystem.cpp:456-470): the sum over
-                        // the components in order, then the unit factor
-                        std::fill(vvv.begin(), vvv.end(), 0.);
-                        for (int h : components)
-                        {
-                            if (mass)
-                                _media[h]->massDensities(positions, one);
-                            else
-                                _media[h]->numberDensities(positions, one);
-                            for (size_t p = 0; p != vvv.size(); ++p) vvv[p] += one[p];
-                        }
-                        for (double& v : vvv) v *= unitFactor;
-                    }
+                    if (mass)
+                        _media[h]->massDensities(positions, one);
                     else
-                    {
-                        for (size_t p = 0; p != positions.size(); ++p)
-                            flat[3 * p] = positions[p].x, flat[3 * p + 1] = positions[p].y, flat[3 * p + 2] = positions[p].z;
-                        if (engine.sample(engine.user, static_cast<int64_t>(positions.size()), flat.data(), 1, cellValues.data(), vvv.data(), nullptr) != 0)
-                            throw std::runtime_error("probe " + probe.name + ": the point sampler failed");
-                    }
-                    const std::string path = base + probe.name + "_" + (mass ? "dust" : "elec") + (gridded ? "_g_" : "_t_") + plane.name + ".fits";
-                    writeFitsCube(path, vvv.data(), _units.unit(quantity), Ni, Nj, _units.out("length", plane.xd ? xpsize : ypsize),
-                                  _units.out("length", plane.zd ? zpsize : ypsize), _units.out("length", plane.xd ? center.x : center.y),
-                                  _units.out("length", plane.zd ? center.z : center.y), _units.unit("length"), Array(), std::string("1"), nullptr);
-                    files.push_back(path);
+                        _media[h]->numberDensities(positions, one);
+                    for (size_t p = 0; p != vvv.size(); ++p) vvv[p] += one[p];
                 }
+                for (double& v : vvv) v *= unitFactor;
+            };
+            const CutValuesFn griddedDensity = [&](const std::vector<Vec3>& positions, Array& vvv) {
+                flat.resize(3 * positions.size());
+                for (size_t p = 0; p != positions.size(); ++p)
+                    flat[3 * p] = positions[p].x, flat[3 * p + 1] = positions[p].y, flat[3 * p + 2] = positions[p].z;
+                if (engine.sample(engine.user, static_cast<int64_t>(positions.size()), flat.data(), 1, cellValues.data(), vvv.data(), nullptr) != 0)
+                    throw std::runtime_error("probe " + probe.name + ": the point sampler failed");
+            };
+            for (int gridded = 0; gridded != 2; ++gridded)
+                for (const CutPlane& plane : planes)
+                    writePlanarCut(output.base + probe.name + "_" + (mass ? "dust" : "elec") + (gridded ? "_g_" : "_t_") + plane.name + ".fits", plane,
+                                   quantity, gridded ? griddedDensity : trueDensity, output);
         }
     }
 
-    std::vector<std::string> Simulation::writeProbes(IntegrateFn integrate, void* user, const std::string& outdir, int when) const
+    // DustAbsorptionPerCellProbe.cpp:25-63: <prefix>_<probe>_Labs.dat, the spectral luminosity that the dust of every cell absorbs
+    void Simulation::writeDustAbsorption(const ProbeModel& probe, ProbeOutput& output) const
     {
-        ProbeEngine engine;
-        engine.integrate = integrate;
-        engine.user = user;
-        return writeProbes(engine, outdir, when);
+        const std::vector<int> dust = componentsOfType(false);
+        if (!_hasMedium || !_storeRadiationField || dust.empty()) return;  // MediumSystem::hasDust
+        const double* rf = output.engine.rf;
+        if (!rf) throw std::runtime_error("probe " + probe.name + " needs the radiation field table");
+        const WavelengthGrid& wlg = *_rfGrid;
+        const int nbins = wlg.numBins();
+        const bool reverse = _units.wavelengthStyle != "Wavelength";
+        std::vector<int> order(nbins);
+        Array outWavelengths(nbins);
+        for (int i = 0; i != nbins; ++i)
+        {
+            order[i] = reverse ? nbins - 1 - i : i;
+            outWavelengths[i] = _units.owavelength(wlg.wavelength(order[i]));
+        }
+        output.files.push_back(output.base + probe.name + "_Labs.dat");
+        writePerCellTable(output.files.back(), "Spectral luminosity absorbed by dust per spatial cell", _units.smonluminosity() + "^abs",
+                          _units.umonluminosity(), outWavelengths, [&](int m, double* row) {
+                              // MediumSystem::meanIntensity (MediumSystem.cpp:1370-1380) and the factor 4 pi V back again
+                              const double Jfactor = 1. / (4. * M_PI * _grid->volume(m));
+                              const double factor = 4. * M_PI * _grid->volume(m);
+                              for (int i = 0; i != nbins; ++i)
+                              {
+                                  const int ell = order[i];
+                                  const double lambda = wlg.wavelength(ell);
+                                  const double J = rf[size_t(m) * nbins + ell] * Jfactor / wlg.effectiveWidth(ell);
+                                  // MediumSystem::opacityAbs(lambda, m, Dust) (MediumSystem.cpp:599-605; DustMix.cpp:347-351)
+                                  double opacity = 0.;
+                                  for (int h : dust)
+                                  {
+                                      const double n = _density[h][m];
+                                      opacity += n > 0. ? n * _media[h]->mix->sectionAbs(lambda) : 0.;
+                                  }
+                                  row[i] = _units.omonluminosity(lambda, J * factor * opacity);
+                              }
+                          });
+    }
+
+    // the row of a temperature quantity in the dust temperatures [H + 1][numCells] (null: another quantity), which are computed when the first
+    // probe asks for them: by the engine from the table on the device, else by the host from the caller's copy of it
+    const double* Simulation::probeTemperatures(const ProbeModel& probe, const ProbeQuantity& q, ProbeOutput& output) const
+    {
+        if (q.kind != ProbeQuantity::Temperature) return nullptr;
+        const ProbeEngine& engine = output.engine;
+        const size_t numCells = size_t(_grid->numCells());
+        if (output.temperatures.empty())
+        {
+            const DustHeating& tables = dustHeating();
+            output.temperatures.assign(size_t(tables.flat.num_components + 1) * numCells, 0.);
+            if (engine.temperatures)
+            {
+                if (engine.temperatures(engine.user, &tables.flat, output.temperatures.data()) != 0)
+                    throw std::runtime_error("probe " + probe.name + ": the computation of the dust temperatures failed");
+            }
+            else if (engine.rf)
+                dustTemperatures(engine.rf, output.temperatures.data());
+            else
+                throw std::runtime_error("probe " + probe.name + " needs the radiation field: hand over the table or the engine that holds it");
+        }
+        return output.temperatures.data() + size_t(q.temperatureRow) * numCells;
+    }
+
+    // PerCellForm.cpp:14-38: the values of every cell times the unit factor (ProbeFormBridge::valuesInCell)
+    void Simulation::writePerCell(const ProbeModel& probe, const ProbeQuantity& q, ProbeOutput& output) const
+    {
+        const double* temperature = probeTemperatures(probe, q, output);
+        const double unitFactor = _units.out(q.quantity, 1.);
+        const int numValues = q.numValues();
+        std::string title = q.description + " per spatial cell";
+        title[0] = static_cast<char>(std::toupper(static_cast<unsigned char>(title[0])));
+        output.files.push_back(output.base + probe.name + (q.fileid.empty() ? "" : "_" + q.fileid) + ".dat");
+        writePerCellTable(output.files.back(), title, q.description, _units.unit(q.quantity), q.compound ? q.axis : Array(), [&](int m, double* row) {
+            for (int v = 0; v != numValues; ++v) row[v] = (temperature ? temperature[m] : probeCellValue(q, v, m)) * unitFactor;
+        });
+    }
+
+    // ParallelProjectionForm.cpp:18-116: the rays of the map through the caller's integrator in batches of rows, the sums (of an averaged
+    // quantity the weighted sums over the sums of the weights) in output units, averaged over the sub-samples of a pixel
+    void Simulation::writeProjection(const ProbeModel& probe, const ProbeQuantity& q, ProbeOutput& output) const
+    {
+        const ProbeEngine& engine = output.engine;
+        const double* temperature = probeTemperatures(probe, q, output);
+        const bool averaged = temperature != nullptr;
+        if (averaged ? !engine.weighted : !engine.integrate)
+            throw std::runtime_error("probe " + probe.name + " is a projected map: it needs an integrator");
+        const int numCells = _grid->numCells(), numValues = q.numValues();
+        const int Nxp = probe.numPixelsX, Nyp = probe.numPixelsY, Ns = probe.numSampling;
+        const int Nsampling2 = Ns * Ns;
+        const double projectedUnitFactor = _units.out(q.projectedQuantity, 1.);
+        // (an averaged quantity: the weights of the cells -- probeCellValue of a temperature is its weight -- next to the values)
+        std::vector<double> cellValues(size_t(numValues) * numCells);
+        for (int v = 0; v != numValues; ++v)
+            for (int m = 0; m != numCells; ++m) cellValues[size_t(v) * numCells + m] = probeCellValue(q, v, m);
+        Array vvv(size_t(numValues) * Nyp * Nxp, 0.);
+        // (rows in batches of about a million rays: the rays of a 10000 x 10000 map with 81 samples would not fit in memory at once)
+        const int raysPerRow = Nxp * Nsampling2;
+        const int rowsPerBatch = std::max(1, (1 << 20) / raysPerRow);
+        const int sumsPerRay = averaged ? 2 : numValues;
+        std::vector<double> origins, directions, sums;
+        for (int j0 = 0; j0 < Nyp; j0 += rowsPerBatch)
+        {
+            const int j1 = std::min(Nyp, j0 + rowsPerBatch);
+            const size_t numRays = size_t(j1 - j0) * raysPerRow;
+            origins.resize(3 * numRays);
+            directions.resize(3 * numRays);
+            sums.assign(numRays * sumsPerRay, 0.);
+            projectionRays(probe, j0, j1, origins.data(), directions.data());
+            const int rc = averaged ? engine.weighted(engine.user, static_cast<int64_t>(numRays), origins.data(), directions.data(), 1,
+                                                      cellValues.data(), temperature, sums.data())
+                                    : engine.integrate(engine.user, static_cast<int64_t>(numRays), origins.data(), directions.data(), numValues,
+                                                       cellValues.data(), sums.data());
+            if (rc != 0) throw std::runtime_error("probe " + probe.name + ": the ray integrator failed");
+            size_t ray = 0;
+            for (int j = j0; j != j1; ++j)
+                for (int i = 0; i != Nxp; ++i)
+                    for (int s = 0; s != Nsampling2; ++s, ++ray)
+                        for (int p = 0; p != numValues; ++p)
+                        {
+                            double value;
+                            if (averaged)
+                            {
+                                // valuesAlongPath, GridScalarAveraged: if (totalWeight) value *= unit factor / totalWeight
+                                const double totalWeight = sums[ray * 2];
+                                value = sums[ray * 2 + 1];
+                                if (totalWeight) value *= projectedUnitFactor / totalWeight;
+                            }
+                            else
+                                // valuesAlongPath: the sum times the projected unit factor
+                                value = sums[ray * numValues + p] * projectedUnitFactor;
+                            // ... then the share of the sub-sample
+                            vvv[(size_t(p) * Nyp + j) * Nxp + i] += value / Nsampling2;
+                        }
+        }
+        const double xpsiz = probe.fieldOfViewX / probe.numPixelsX, ypsiz = probe.fieldOfViewY / probe.numPixelsY;
+        const std::string path = output.base + probe.name + (q.projectedFileid.empty() ? "" : "_" + q.projectedFileid) + ".fits";
+        writeFitsCube(path, vvv.data(), _units.unit(q.projectedQuantity), Nxp, Nyp, _units.out("length", xpsiz), _units.out("length", ypsiz),
+                      _units.out("length", probe.centerX), _units.out("length", probe.centerY), _units.unit("length"),
+                      q.compound ? q.axis : Array(), q.compound ? _units.uwavelength() : std::string("1"), nullptr);
+        output.files.push_back(path);
     }
 
     std::vector<std::string> Simulation::writeProbes(const ProbeEngine& engine, const std::string& outdir, int when) const
     {
-        std::vector<std::string> files;
-        std::string base = outdir;
-        if (!base.empty() && base.back() != '/') base += '/';
-        base += _prefix + "_";
-        const int numCells = _grid->numCells();
-        // the dust temperatures [H + 1][numCells], computed when the first probe asks for them: by the engine from the table on the device,
-        // else by the host from the caller's copy of it
-        std::vector<double> temperatures;
-        auto needTemperatures = [&](const std::string& probeName) {
-            if (!temperatures.empty()) return;
-            const DustHeating& tables = dustHeating();
-            temperatures.assign(size_t(tables.flat.num_components + 1) * numCells, 0.);
-            if (engine.temperatures)
-            {
-                if (engine.temperatures(engine.user, &tables.flat, temperatures.data()) != 0)
-                    throw std::runtime_error("probe " + probeName + ": the computation of the dust temperatures failed");
-            }
-            else if (engine.rf)
-                dustTemperatures(engine.rf, temperatures.data());
-            else
-                throw std::runtime_error("probe " + probeName + " needs the radiation field: hand over the table or the engine that holds it");
-        };
+        ProbeOutput output{engine, outdir, {}, {}};
+        if (!output.base.empty() && output.base.back() != '/') output.base += '/';
+        output.base += _prefix + "_";
         for (const ProbeModel& probe : _probes)
         {
             if (when >= 0 && (when == 0) != probe.afterSetup) continue;
             if (probe.type == "ConvergenceInfoProbe")
             {
-                if (_hasMedium) files.push_back(writeConvergenceInfo(probe, engine, base));  // ConvergenceInfoProbe.cpp:152
-                continue;
+                if (_hasMedium) writeConvergenceInfo(probe, output);  // ConvergenceInfoProbe.cpp:152
             }
-            if (probe.type == "ConvergenceCutsProbe")
+            else if (probe.type == "ConvergenceCutsProbe")
             {
-                if (_hasMedium) writeConvergenceCuts(probe, engine, base, files);  // ConvergenceCutsProbe.cpp:25
-                continue;
+                if (_hasMedium) writeConvergenceCuts(probe, output);  // ConvergenceCutsProbe.cpp:25
             }
-            if (probe.type == "DustAbsorptionPerCellProbe")
-            {
-                // DustAbsorptionPerCellProbe.cpp:25-63 through TextOutFile; MediumSystem::hasDust
-                if (!_hasMedium || !_storeRadiationField) continue;
-                std::vector<int> dust;
-                for (size_t h = 0; h != _media.size(); ++h)
-                    if (!_media[h]->mix->isElectrons()) dust.push_back(static_cast<int>(h));
-                if (dust.empty()) continue;
-                if (!engine.rf) throw std::runtime_error("probe " + probe.name + " needs the radiation field table");
-                const WavelengthGrid& wlg = *_rfGrid;
-                const int nbins = wlg.numBins();
-                const bool reverse = _units.wavelengthStyle != "Wavelength";
-                const std::string path = base + probe.name + "_Labs.dat";
-                std::ofstream out(path);
-                if (!out) throw std::runtime_error("Could not open output file " + path);
-                out << "# Spectral luminosity absorbed by dust per spatial cell" << std::endl;
-                out << "# column 1: spatial cell index (1)" << std::endl;
-                for (int i = 0; i != nbins; ++i)
-                {
-                    const int ell = reverse ? nbins - 1 - i : i;
-                    char buf[40];
-                    snprintf(buf, sizeof(buf), "%1.6g", _units.owavelength(wlg.wavelength(ell)));
-                    out << "# column " << (i + 2) << ": " << _units.smonluminosity() << "^abs at " << _units.swavelength() << " = " << buf << " "
-                        << _units.uwavelength() << " (" << _units.umonluminosity() << ")" << std::endl;
-                }
-                for (int m = 0; m != numCells; ++m)
-                {
-                    char buf[40];
-                    snprintf(buf, sizeof(buf), "%1.0f", double(m));
-                    std::string line = buf;
-                    // MediumSystem::meanIntensity (MediumSystem.cpp:1370-1380) and the factor 4 pi V back again
-                    const double Jfactor = 1. / (4. * M_PI * _grid->volume(m));
-                    const double factor = 4. * M_PI * _grid->volume(m);
-                    for (int i = 0; i != nbins; ++i)
-                    {
-                        const int ell = reverse ? nbins - 1 - i : i;
-                        const double lambda = wlg.wavelength(ell);
-                        const double J = engine.rf[size_t(m) * nbins + ell] * Jfactor / wlg.effectiveWidth(ell);
-                        // MediumSystem::opacityAbs(lambda, m, Dust) (MediumSystem.cpp:599-605; DustMix.cpp:347-351)
-                        double opacity = 0.;
-                        for (int h : dust)
-                        {
-                            const double n = _density[h][m];
-                            opacity += n > 0. ? n * _media[h]->mix->sectionAbs(lambda) : 0.;
-                        }
-                        const double Labs = J * factor * opacity;
-                        snprintf(buf, sizeof(buf), " %1.9e", _units.omonluminosity(lambda, Labs));
-                        line += buf;
-                    }
-                    out << line << std::endl;
-                }
-                files.push_back(path);
-                continue;
-            }
-            for (const ProbeQuantity& q : probeQuantities(probe))
-            {
-                const int numValues = q.numValues();
-                const bool averaged = q.kind == ProbeQuantity::Temperature;
-                if (averaged) needTemperatures(probe.name);
-                const double* temperature = averaged ? temperatures.data() + size_t(q.temperatureRow) * numCells : nullptr;
-                if (!probe.projected)
-                {
-                    // PerCellForm.cpp:14-38 through TextOutFile (TextOutFile.cpp:61-103): the cell index as 'd', the values as 'e' with 9 digits
-                    const double unitFactor = _units.out(q.quantity, 1.);
-                    const std::string unit = _units.unit(q.quantity);
-                    const std::string path = base + probe.name + (q.fileid.empty() ? "" : "_" + q.fileid) + ".dat";
-                    std::ofstream out(path);
-                    if (!out) throw std::runtime_error("Could not open output file " + path);
-                    std::string title = q.description + " per spatial cell";
-                    title[0] = static_cast<char>(std::toupper(static_cast<unsigned char>(title[0])));
-                    out << "# " << title << std::endl;
-                    out << "# column 1: spatial cell index (1)" << std::endl;
-                    if (!q.compound)
-                        out << "# column 2: " << q.description << " (" << unit << ")" << std::endl;
+            else if (probe.type == "DustAbsorptionPerCellProbe")
+                writeDustAbsorption(probe, output);
+            else
+                for (const ProbeQuantity& q : probeQuantities(probe))
+                    if (probe.projected)
+                        writeProjection(probe, q, output);
                     else
-                        for (int v = 0; v != numValues; ++v)
-                        {
-                            // (StringUtils::toString(outwave, 'g'): six significant digits)
-                            char buf[40];
-                            snprintf(buf, sizeof(buf), "%1.6g", q.axis[v]);
-                            out << "# column " << (v + 2) << ": opacity at " << _units.swavelength() << " = " << buf << " " << _units.uwavelength()
-                                << " (" << unit << ")" << std::endl;
-                        }
-                    for (int m = 0; m != numCells; ++m)
-                    {
-                        char buf[40];
-                        snprintf(buf, sizeof(buf), "%1.0f", double(m));
-                        std::string line = buf;
-                        for (int v = 0; v != numValues; ++v)
-                        {
-                            // ProbeFormBridge::valuesInCell: the value times the unit factor
-                            snprintf(buf, sizeof(buf), " %1.9e", (averaged ? temperature[m] : probeCellValue(q, v, m)) * unitFactor);
-                            line += buf;
-                        }
-                        out << line << std::endl;
-                    }
-                    files.push_back(path);
-                    continue;
-                }
-
-                // ParallelProjectionForm.cpp:18-116
-                if (averaged ? !engine.weighted : !engine.integrate)
-                    throw std::runtime_error("probe " + probe.name + " is a projected map: it needs an integrator");
-                const int Nxp = probe.numPixelsX, Nyp = probe.numPixelsY, Ns = probe.numSampling;
-                const int Nsampling2 = Ns * Ns;
-                const double projectedUnitFactor = _units.out(q.projectedQuantity, 1.);
-                // (an averaged quantity: the weights of the cells -- probeCellValue of a temperature is its weight -- next to the values)
-                std::vector<double> cellValues(size_t(numValues) * numCells);
-                for (int v = 0; v != numValues; ++v)
-                    for (int m = 0; m != numCells; ++m) cellValues[size_t(v) * numCells + m] = probeCellValue(q, v, m);
-                Array vvv(size_t(numValues) * Nyp * Nxp, 0.);
-                // (rows in batches of about a million rays: the rays of a 10000 x 10000 map with 81 samples would not fit in memory at once)
-                const int raysPerRow = Nxp * Nsampling2;
-                const int rowsPerBatch = std::max(1, (1 << 20) / raysPerRow);
-                const int sumsPerRay = averaged ? 2 : numValues;
-                std::vector<double> origins, directions, sums;
-                for (int j0 = 0; j0 < Nyp; j0 += rowsPerBatch)
-                {
-                    const int j1 = std::min(Nyp, j0 + rowsPerBatch);
-                    const size_t numRays = size_t(j1 - j0) * raysPerRow;
-                    origins.resize(3 * numRays);
-                    directions.resize(3 * numRays);
-                    sums.assign(numRays * sumsPerRay, 0.);
-                    projectionRays(probe, j0, j1, origins.data(), directions.data());
-                    const int rc = averaged ? engine.weighted(engine.user, static_cast<int64_t>(numRays), origins.data(), directions.data(), 1,
-                                                              cellValues.data(), temperature, sums.data())
-                                            : engine.integrate(engine.user, static_cast<int64_t>(numRays), origins.data(), directions.data(), numValues,
-                                                               cellValues.data(), sums.data());
-                    if (rc != 0) throw std::runtime_error("probe " + probe.name + ": the ray integrator failed");
-                    size_t ray = 0;
-                    for (int j = j0; j != j1; ++j)
-                        for (int i = 0; i != Nxp; ++i)
-                            for (int s = 0; s != Nsampling2; ++s, ++ray)
-                                for (int p = 0; p != numValues; ++p)
-                                {
-                                    double value;
-                                    if (averaged)
-                                    {
-                                        // valuesAlongPath, GridScalarAveraged: if (totalWeight) value *= unit factor / totalWeight
-                                        const double totalWeight = sums[ray * 2];
-                                        value = sums[ray * 2 + 1];
-                                        if (totalWeight) value *= projectedUnitFactor / totalWeight;
-                                    }
-                                    else
-                                        // valuesAlongPath: the sum times the projected unit factor
-                                        value = sums[ray * numValues + p] * projectedUnitFactor;
-                                    // ... then the share of the sub-sample
-                                    vvv[(size_t(p) * Nyp + j) * Nxp + i] += value / Nsampling2;
-                                }
-                }
-                const double xpsiz = probe.fieldOfViewX / probe.numPixelsX, ypsiz = probe.fieldOfViewY / probe.numPixelsY;
-                const std::string path = base + probe.name + (q.projectedFileid.empty() ? "" : "_" + q.projectedFileid) + ".fits";
-                writeFitsCube(path, vvv.data(), _units.unit(q.projectedQuantity), Nxp, Nyp, _units.out("length", xpsiz), _units.out("length", ypsiz),
-                              _units.out("length", probe.centerX), _units.out("length", probe.centerY), _units.unit("length"),
-                              q.compound ? q.axis : Array(), q.compound ? _units.uwavelength() : std::string("1"), nullptr);
-                files.push_back(path);
-            }
+                        writePerCell(probe, q, output);
         }
-        return files;
+        return output.files;
     }
 }
+
+

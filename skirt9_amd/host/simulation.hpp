@@ -8,6 +8,7 @@
 
 #include "model.hpp"
 #include <cstdint>
+#include <functional>
 #include <mutex>
 
 namespace skh
@@ -73,9 +74,6 @@ namespace skh
         void probeMapRays(int map, double* origins, double* directions) const;
         // its cell values [numValues][numCells] in internal units (the projected unit factor is applied to the sums)
         void probeMapValues(int map, double* cellValues) const;
-        // writes the probe files; when: 0 the probes with probeAfter Setup, 1 those with Run, -1 all.  The per-cell files need no
-        // integrator, which may be null when no projected map is written
-        std::vector<std::string> writeProbes(IntegrateFn integrate, void* user, const std::string& outdir, int when = -1) const;
 
         // Dust temperatures from the stored radiation field (temperature.cpp): the tables of EquilibriumDustEmissionCalculator::precalculate
         // (EquilibriumDustEmissionCalculator.cpp:18-93) per dust component, in the layout of pmc_dust_heating (include/pmc.h) together with the
@@ -113,6 +111,8 @@ namespace skh
             const double* rf{nullptr};
             SampleFn sample{nullptr};  // ConvergenceCutsProbe (user as for the others)
         };
+        // writes the probe files; when: 0 the probes with probeAfter Setup, 1 those with Run, -1 all.  The per-cell files need no
+        // integrator, which may be null when no projected map is written
         std::vector<std::string> writeProbes(const ProbeEngine& engine, const std::string& outdir, int when = -1) const;
         // whether a probe written with `when` reads the radiation field (a TemperatureProbe or DustAbsorptionPerCellProbe that writes a file)
         bool probesNeedRadiationField(int when = -1) const;
@@ -178,8 +178,6 @@ namespace skh
         static ProbeModel readFormProbe(const XmlElement& probe, const Reader& rd);
         static ProbeModel readConvergenceCutsProbe(const XmlElement& probe, const Reader& rd);
         static ProbeModel readConvergenceInfoProbe(const XmlElement& probe, const Reader& rd);
-        std::string writeConvergenceInfo(const ProbeModel& probe, const ProbeEngine& engine, const std::string& base) const;
-        void writeConvergenceCuts(const ProbeModel& probe, const ProbeEngine& engine, const std::string& base, std::vector<std::string>& files) const;
         static std::string readRadiationFieldProbe(const XmlElement& probe, const Reader& rd);
 
         // simulation.cpp: the stages of setup(), in order
@@ -251,6 +249,23 @@ namespace skh
         struct ProbeQuantity;
         std::vector<ProbeQuantity> probeQuantities(const ProbeModel& probe) const;
         double probeCellValue(const ProbeQuantity& quantity, int value, int m) const;
+        // the medium components of a material type, in order: the dust components, or the electron components
+        std::vector<int> componentsOfType(bool electrons) const;
+        // probes.cpp: what the writers of one writeProbes call share (ProbeOutput), a writer per kind of probe and per form
+        struct ProbeOutput;
+        struct CutPlane;
+        typedef std::function<void(const std::vector<Vec3>& positions, Array& values)> CutValuesFn;
+        void writeConvergenceInfo(const ProbeModel& probe, ProbeOutput& out) const;
+        void writeConvergenceCuts(const ProbeModel& probe, ProbeOutput& out) const;
+        void writeDustAbsorption(const ProbeModel& probe, ProbeOutput& out) const;
+        const double* probeTemperatures(const ProbeModel& probe, const ProbeQuantity& q, ProbeOutput& out) const;
+        void writePerCell(const ProbeModel& probe, const ProbeQuantity& q, ProbeOutput& out) const;
+        void writeProjection(const ProbeModel& probe, const ProbeQuantity& q, ProbeOutput& out) const;
+        void writePlanarCut(const std::string& path, const CutPlane& plane, const std::string& quantity, const CutValuesFn& valuesAt, ProbeOutput& out) const;
+        // output.cpp: the text file of a PerCellForm; fill computes the values of cell m, in output units
+        typedef std::function<void(int m, double* row)> CellRowFn;
+        void writePerCellTable(const std::string& path, const std::string& title, const std::string& quantity, const std::string& unit,
+                               const Array& outWavelengths, const CellRowFn& fill) const;
         // instruments
         std::unique_ptr<WavelengthGrid> _defaultGrid;     // as configured in the ski (panchromatic)
         std::unique_ptr<WavelengthGrid> _oligoGrid;       // OligoWavelengthGrid

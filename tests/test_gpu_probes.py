@@ -13,7 +13,7 @@ import pytest
 
 import probe_checks as P
 from conftest import ROOT, ski
-from skirt9_amd.engine import INTEGRATE_PASS_VALUES, Engine, clear_tuning, set_tuning
+from skirt9_amd.engine import INTEGRATE_BATCH_RAYS, INTEGRATE_PASS_VALUES, Engine, clear_tuning, set_tuning
 from skirt9_amd.host import Simulation, scene_head
 
 pytestmark = pytest.mark.gpu
@@ -131,6 +131,21 @@ def test_order_of_the_rays_does_not_matter(name):
     eng = Engine(sim.scene, 0)
     assert _same_bits(eng.integrate_rays(r[perm], k[perm], q), ref[perm])
     eng.close()
+
+
+def test_more_rays_than_one_batch():
+    """INTEGRATE_BATCH_RAYS + 65 rays on cfg1, the ray set tiled (ray i = set[i % NUM_RAYS]), V values: two batches of two passes each, the
+    second batch a wave and one lane -- where a batch offset and a pass offset meet"""
+    sim, r, k, q, ref, count = _case("cfg1")
+    tile = np.arange(INTEGRATE_BATCH_RAYS + 65) % NUM_RAYS
+    eng = Engine(sim.scene, 0)
+    sums = eng.integrate_rays(r[tile], k[tile], q)
+    work = eng.last_integrate_work()
+    eng.close()
+    assert sums.shape == (len(tile), V)
+    assert _same_bits(sums, ref[tile]), int((sums != ref[tile]).any(axis=1).sum())
+    # the tiled segment count, once per pass: each of the two passes walks every ray of its batch (224 202 842 = 2 x 112 101 421)
+    assert work["lane_steps"] == 2 * count[tile].sum()
 
 
 def test_argument_errors_are_reported():

@@ -18,7 +18,7 @@ import temperature_checks as T
 from conftest import ROOT, ski
 from scene_variants import with_field_grid
 from skirt9_amd import host
-from skirt9_amd.engine import INTEGRATE_PASS_VALUES, Engine, clear_tuning, lib, set_tuning
+from skirt9_amd.engine import INTEGRATE_BATCH_RAYS, INTEGRATE_PASS_VALUES, Engine, clear_tuning, lib, set_tuning
 from skirt9_amd.host import Simulation, scene_head
 
 pytestmark = pytest.mark.gpu
@@ -200,6 +200,21 @@ def test_weighted_sums_equal_the_sum_over_the_traced_segments(name):
     plain = eng.integrate_rays(r, k, w)
     assert _same_bits(plain, ref[:, 0])
     eng.close()
+
+
+def test_more_weighted_rays_than_one_batch():
+    """INTEGRATE_BATCH_RAYS + 65 rays on cfg5small (1500 cells: the smallest grid of RAY_SCENES), the ray set tiled (ray i = set[i % NUM_RAYS]), V values: two
+    batches -- the second a wave and one lane -- of two passes each, a pass the weight and three values.  The sum of the weights is taken
+    from the first pass, in the first batch and in the second"""
+    sim, r, k, w, q, ref = _case("cfg5small")
+    tile =np.arange(INTEGRATE_BATCH_RAYS + 65) % NUM_RAYS
+    eng = Engine(sim.scene, 0)
+    sums = eng.integrate_weighted_rays(r[tile], k[tile], w, q)
+    eng.close()
+    assert sums.shape == (len(tile), 1 + V)
+    for batch in (slice(0, INTEGRATE_BATCH_RAYS), slice(INTEGRATE_BATCH_RAYS, None)):
+        assert _same_bits(sums[batch, 0], ref[tile[batch], 0]), batch
+    assert _same_bits(sums, ref[tile]), int((sums != ref[tile]).any(axis=1).sum())
 
 
 # ---- the probe files

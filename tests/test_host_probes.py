@@ -97,6 +97,63 @@ def test_a_failing_integrator_is_an_error(tmp_path):
         sim.write_probes(str(tmp_path))
 
 
+def test_the_four_entry_points_write_the_same_files(tmp_path):
+    """skh_write_probes, skh_write_probes_when(-1), skh_write_probes_with and skh_write_probes_sampled without a sampler, each with the same
+    Python integrator handed over as a C function: the same set of files with the same bytes (the DATE card of a FITS file, a time stamp,
+    apart as everywhere)"""
+    import ctypes as C
+    from skirt9_amd import host as H
+    sim = Simulation(ski("cfg1probe.ski")).setup()
+    num_cells = int(H.scene_head(sim).grid.num_cells)
+    calls = []
+
+    def integrate(_, n, origins, directions, num_values, values, sums):
+        r = np.ctypeslib.as_array(origins, shape=(n, 3))
+        k = np.ctypeslib.as_array(directions, shape=(n, 3))
+        q = np.ctypeslib.as_array(values, shape=(num_values, num_cells))
+        calls.append(n)
+        np.ctypeslib.as_array(sums, shape=(n, num_values))[:] = ((r * k) @ np.array([1., 2., 3.]))[:, None] * q.sum(axis=1)[None, :]
+        return 0
+
+    fn = H.INTEGRATE_FN(integrate)
+    pointer = C.cast(fn, C.c_void_p)
+    engine = H.ProbeEngine()
+    engine.integrate = pointer
+    L = H.lib()
+    out = [str(tmp_path / name) for name in ("plain", "when", "with", "sampled")]
+    for folder in out:
+        os.makedirs(folder)
+    assert L.skh_write_probes(sim._h, pointer, None, os.fsencode(out[0])) == 0
+    assert L.skh_write_probes_when(sim._h, pointer, None, os.fsencode(out[1]), -1) == 0
+    assert L.skh_write_probes_with(sim._h, C.byref(engine), os.fsencode(out[2]), -1) == 0
+    assert L.skh_write_probes_sampled(sim._h, C.byref(engine), None, os.fsencode(out[3]), -1) == 0
+    maps = sim.probe_maps()
+    assert calls == 4 * [m["num_rays"] for m in maps] and calls
+    files = sorted(os.listdir(out[0]))
+    assert files == sorted(["cfg1probe_dns_dust_rho.dat", "cfg1probe_opc_k.dat"] + [m["file_name"] for m in maps])
+    for folder in out[1:]:
+        assert sorted(os.listdir(folder)) == files
+        for f in files:
+            assert P.same_file(os.path.join(out[0], f), os.path.join(folder, f)), (folder, f)
+
+
+def test_null_engine_rules_of_the_entry_points(tmp_path):
+    """skh_write_probes_with refuses a null engine; skh_write_probes_sampled takes one (and no sampler) where no probe needs either"""
+    from skirt9_amd import host as H
+    path = _variant(tmp_path, "cfg1probe", "cfg1probe", lambda t: re.sub(r"\n\s*<(DensityProbe|OpacityProbe)[^\n]*<ParallelProjectionForm[^\n]*", "", t))
+    sim = Simulation(path).setup()
+    assert sim.probe_maps() == []
+    L = H.lib()
+    out = tmp_path / "out"
+    out.mkdir()
+    assert L.skh_write_probes_with(sim._h, None, os.fsencode(str(out)), -1) != 0
+    assert "invalid argument" in L.skh_last_error().decode()
+    assert os.listdir(out) == []
+    assert L.skh_write_probes_sampled(sim._h, None, None, os.fsencode(str(out)), -1) == 0
+    assert sorted(os.listdir(out)) == ["cfg1probe_dns_dust_rho.dat", "cfg1probe_opc_k.dat"]
+    P.assert_files_equal_golden("cfg1probe", str(out), suffixes=(".dat",))
+
+
 def _reference_rays(form, nx, ny, ns):
     """ParallelProjectionForm.cpp:22-51, 67-88 restated with numpy; form: angles in rad, lengths in m"""
     ct, st = np.cos(form["inclination"]), np.sin(form["inclination"])
