@@ -26,7 +26,8 @@
  *                        EquilibriumDustEmissionCalculator.cpp:120-130): what TemperatureProbe writes, and the first step of a
  *                        secondary dust emission source
  *   pmc_sampler_*     <- ParticleSnapshot::density(Position) evaluated for the sample positions of the setup phase
- *                        (ParticleSnapshot.cpp:233-243; DensityTreePolicy.cpp:141, MediumSystem.cpp:91-96)
+ *                        (ParticleSnapshot.cpp:233-243; DensityTreePolicy.cpp:141, MediumSystem.cpp:91-96); created by
+ *                        pmc_sampler_create_mesh: AdaptiveMeshSnapshot::density(Position) (AdaptiveMeshSnapshot.cpp:108-148,276-280)
  *   pmc_sample_cells  <- SpatialGrid::cellIndex(Position) for many positions and the cell values there: ProbeFormBridge::valuesAtPosition,
  *                        the operation behind every cut form of a probe (ProbeFormBridge.cpp, PlanarCutsForm.cpp)
  *   pmc_counters      <- no reference counterpart: counted cell visits / detector updates for the roofline
@@ -530,6 +531,30 @@ int  pmc_sampler_create(const pmc_particles* particles, int32_t device, pmc_samp
 /* positions: host array [n][3]; density: host array [n] (mass or number density as the particle weights imply) */
 int  pmc_sampler_density(pmc_sampler* sampler, const double* positions, int64_t n, double* density);
 void pmc_sampler_destroy(pmc_sampler* sampler);
+
+/* AdaptiveMeshSnapshot::density(Position) (SKIRT/core/AdaptiveMeshSnapshot.cpp:276-280) for MANY positions at once, for a medium
+   imported from an adaptive mesh: 0 outside the closed root box, else the density of the leaf that Node::leaf finds (:141-148).  Per level
+   Node::child (:108-136) estimates the child indices as Box::cellIndices does (SKIRT/utils/Box.hpp:171-176:
+   i = max(0, min(nx-1, int(nx * (x - xmin) / (xmax - xmin)))), the product first), takes child (k*ny + j)*nx + i and, if its closed box does
+   not hold the position, moves each index by one towards the position; if that child does not hold it either, or an index leaves [0, n), the
+   position cannot be located ("Can't locate the appropriate child node", :133).  The nodes are a table: node 0 is the root, every parent
+   comes before its children, and the children of a node have consecutive ids in the order k, j, i (i fastest); the boxes are the ones the
+   reference's nodes hold (Box::fracPos with integer fractions, Box.hpp:163-167).  Plain f64 arithmetic in the reference's order: the
+   result equals the host evaluation bit for bit.
+   pmc_sampler_create_mesh checks the table before any device call (PMC_ERR_INVALID: a child range outside the table, a child id that is
+   not above its parent's, a dimension below 1 or a product of dimensions that overflows, a leaf link outside [0, num_cells)) and works
+   out the depth of the tree, which caps the descent on the device.  pmc_sampler_density and pmc_sampler_destroy serve both kinds of
+   sampler; pmc_sampler_density returns PMC_ERR_DEVICE with the reference's sentence and the lowest index of a position that could not be
+   located. */
+typedef struct pmc_adaptive_mesh
+{
+    int32_t        num_nodes, num_cells;
+    const double*  node_box;     /* [num_nodes][6] xmin, ymin, zmin, xmax, ymax, zmax as the reference's nodes hold them */
+    const int32_t* node_dims;    /* [num_nodes][3] nx, ny, nz; 0,0,0: leaf */
+    const int32_t* node_link;    /* nonleaf: id of child 0 (> own id); leaf: cell index */
+    const double*  cell_density; /* [num_cells] */
+} pmc_adaptive_mesh;
+int  pmc_sampler_create_mesh(const pmc_adaptive_mesh* mesh, int32_t device, pmc_sampler** out);
 
 #ifdef __cplusplus
 }

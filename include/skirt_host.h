@@ -28,6 +28,9 @@ int skh_set_tree_topology_file(skh_simulation* sim, const char* treetop_path);
    four pointers are libpmc.so's pmc_sampler_create, pmc_sampler_density, pmc_sampler_destroy and pmc_last_error (passed
    at run time so that this library does not link against the HIP engine); results are bit-identical to the host's */
 int skh_set_particle_sampler(skh_simulation* sim, void* create, void* density, void* destroy, void* last_error, int32_t device);
+/* the same for a medium imported from an adaptive mesh (AdaptiveMeshMedium): create_mesh is libpmc.so's pmc_sampler_create_mesh, the other
+   three are as above */
+int skh_set_mesh_sampler(skh_simulation* sim, void* create_mesh, void* density, void* destroy, void* last_error, int32_t device);
 /* Simulation::setupSimulation */
 int skh_setup(skh_simulation* sim);
 /* valid after skh_setup, owned by the simulation */
@@ -140,6 +143,18 @@ int32_t skh_dimension(const skh_simulation* sim);
    Voronoi mesh), on one thread: the domain box is closed and a position on a wall between two cells belongs to the upper one.  It is the CPU
    yardstick of pmc_sample_cells, as skh_dust_temperatures is of pmc_dust_temperatures. */
 int skh_cell_indices(const skh_simulation* sim, int64_t num_points, const double* positions, int32_t* cells);
+
+/* Imported media (valid after skh_setup).  skh_adaptive_mesh: the tree of an AdaptiveMeshMedium component and the densities of its cells as
+   the tables of pmc_adaptive_mesh (include/pmc.h) -- pointers into the simulation, valid until skh_free; an error for a component of another
+   kind.  skh_imported_densities: Snapshot::density(Position) of an imported component (ParticleMedium, AdaptiveMeshMedium) at positions
+   [n][3] -- the mass or number density as the file implies, before the conversion by the material mix --, on the device when a sampler is
+   bound (skh_set_particle_sampler, skh_set_mesh_sampler), else on the host cores; a position that the reference cannot locate in an adaptive
+   mesh fails with its words ("Can't locate the appropriate child node") and the lowest such index.  skh_imported_mass: Snapshot::mass(), the
+   total effective mass or number of the component's entities after the policy of ImportedMedium (mass fraction, metallicity, temperature
+   cutoff). */
+int skh_imported_mass(const skh_simulation* sim, int32_t component, double* out);
+int skh_adaptive_mesh(const skh_simulation* sim, int32_t component, pmc_adaptive_mesh* out);
+int skh_imported_densities(const skh_simulation* sim, int32_t component, int64_t n, const double* positions, double* out);
 
 /* A set-up scene as ONE file: everything pmc_create reads plus the numbers a driver of the photon loop needs.  In a job of
    one process per GPU, one process sets the simulation up (all host cores) and saves it, the others load it instead of

@@ -1,4 +1,5 @@
-// pmc_sampler.hip -- setup-time density of a smoothed-particle medium on the MI355X (include/pmc.h, pmc_sampler_*).
+// pmc_sampler.hip -- setup-time density of an imported medium on the MI355X (include/pmc.h, pmc_sampler_*): smoothed particles, and
+// the cells of an adaptive mesh (second half of this file).
 //
 // One lane per sample position: locate the block of the search grid (three binary searches over the separation arrays,
 // staged in LDS), then walk the block's particle list IN ORDER and accumulate kernel(u) * rho -- exactly the loop of
@@ -10,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -90,12 +92,119 @@ namespace
             density[s] = sum > 0. ? sum : 0.;
         }
     }
+
+    // ---------------------------------------------------------------- adaptive mesh
+    //
+    // One lane per position descends the tree of AdaptiveMeshSnapshot::Node::leaf (SKIRT/core/AdaptiveMeshSnapshot.cpp:108-148).  A node
+    // is ONE 64-byte aligned record -- box, dimensions, link -- so that a level of the descent costs one 64-byte request per lane: the
+    // record of the estimated child, which serves the `contains` test of Node::child and, when it passes, is the node of the next level.
+    // The top levels are shared by all lanes (the root is a broadcast) and stay in the vector L1 / L2; the deep levels are gathers, and
+    // positions of one cell (100 samples each in the setup phase) are neighbours in the batch, so their lanes walk the same records.  Plain
+    // f64 in the reference's expression order (-ffp-contract=off); no LDS.
+    struct alignas(64) MeshNode
+    {
+        double xmin, ymin, zmin, xmax, ymax, zmax;
+        int32_t nx, ny, nz;  // 0, 0, 0: leaf
+        int32_t link;        // nonleaf: id of child 0; leaf: cell index
+    };
+    static_assert(sizeof(MeshNode) == 64, "one node per 64-byte line");
+
+    struct DevMesh
+    {
+        const MeshNode* node;
+        const double* cell_density;
+        int32_t depth;  // levels below the root: the cap of the descent
+    };
+
+    // the record as four 16-byte loads
+    __device__ __forceinline__ MeshNode loadNode(const MeshNode* node, int32_t id)
+    {
+        const double2* d = reinterpret_cast<const double2*>(node + id);
+        const double2 a = d[0], b = d[1], c = d[2];
+        const int4 t = *reinterpret_cast<const int4*>(d + 3);
+        MeshNode n;
+        n.xmin = a.x, n.ymin = a.y, n.zmin = b.x, n.xmax = b.y, n.ymax = c.x, n.zmax = c.y;
+        n.nx = t.x, n.ny = t.y, n.nz = t.z, n.link = t.w;
+        return n;
+    }
+
+    // Box::contains (SKIRT/utils/Box.hpp:99-102): the box is closed; false for a coordinate that is not a number
+    __device__ __forceinline__ bool holds(const MeshNode& n, double x, double y, double z)
+    {
+        return x >= n.xmin && x <= n.xmax && y >= n.ymin && y <= n.ymax && z >= n.zmin && z <= n.zmax;
+    }
+
+    // Box::cellIndices (Box.hpp:171-176) for one axis: the product first, then the quotient
+    __device__ __forceinline__ int childIndex(int n, double x, double lo, double hi)
+    {
+        return max(0, min(n - 1, static_cast<int>(n * (x - lo) / (hi - lo))));
+    }
+
+    __global__ __launch_bounds__(256) void sampleMeshDensityKernel(DevMesh M, const double* __restrict__ positions, long long n, long long first,
+                                                                   double* __restrict__ density, unsigned long long* __restrict__ failed)
+    {
+        for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (long long)gridDim.x * blockDim.x)
+        {
+            const double x = positions[3 * s], y = positions[3 * s + 1], z = positions[3 * s + 2];
+            MeshNode node = loadNode(M.node, 0);
+            double rho = 0.;
+            if (holds(node, x, y, z))  // Node::leaf: outside the root box there is no cell
+            {
+                bool lost = false;
+                for (int level = 0; level < M.depth && node.nx != 0; ++level)
+                {
+                    // Node::child: estimate the child, correct the indices by one if the point is not in it
+                    int i = childIndex(node.nx, x, node.xmin, node.xmax);
+                    int j = childIndex(node.ny, y, node.ymin, node.ymax);
+                    int k = childIndex(node.nz, z, node.zmin, node.zmax);
+                    MeshNode child = loadNode(M.node, node.link + (k * node.ny + j) * node.nx + i);
+                    if (!holds(child, x, y, z))
+                    {
+                        if (x < child.xmin)
+                            i--;
+                        else if (x > child.xmax)
+                            i++;
+                        if (y < child.ymin)
+                            j--;
+                        else if (y > child.ymax)
+                            j++;
+                        if (z < child.zmin)
+                            k--;
+                        else if (z > child.zmax)
+                            k++;
+                        // (an index outside the node's children: the reference reads outside its list here)
+                        if (i < 0 || i >= node.nx || j < 0 || j >= node.ny || k < 0 || k >= node.nz)
+                        {
+                            lost = true;
+                            break;
+                        }
+                        child = loadNode(M.node, node.link + (k * node.ny + j) * node.nx + i);
+                        if (!holds(child, x, y, z))
+                        {
+                            lost = true;
+                            break;
+                        }
+                    }
+                    node = child;
+                }
+                // a nonleaf node after `depth` levels cannot happen with the depth worked out from the table: the cap only bounds the loop
+                if (lost || node.nx != 0)
+                    atomicMin(failed, static_cast<unsigned long long>(first + s));
+                else
+                    rho = M.cell_density[node.link];
+            }
+            density[s] = rho;
+        }
+    }
 }
 
 struct pmc_sampler
 {
     int device{0};
+    bool mesh{false};  // which of the two tables this sampler holds
     DevParticles dev{};
+    DevMesh devMesh{};
+    unsigned long long* dfailed{nullptr};  // mesh: the lowest index of a position that could not be located, or all ones
     std::vector<void*> allocations;
     double* dpos{nullptr};
     double* dout{nullptr};
@@ -172,13 +281,20 @@ int pmc_sampler_density(pmc_sampler* s, const double* positions, int64_t n, doub
     if (!positions || !density) return failSampler(PMC_ERR_INVALID, "null buffer");
     if (hipSetDevice(s->device) != hipSuccess) return failSampler(PMC_ERR_DEVICE, "hipSetDevice failed");
     const size_t lds = 3 * size_t(s->dev.nb + 1) * sizeof(double);
+    const unsigned long long none = ~0ull;
+    unsigned long long failed = none;
+    if (s->mesh && hipMemsetAsync(s->dfailed, 0xff, sizeof(failed), s->stream) != hipSuccess)
+        return failSampler(PMC_ERR_DEVICE, "hipMemset of the sampler's error word failed");
     for (int64_t first = 0; first < n; first += s->batch)
     {
         const long long m = std::min<long long>(s->batch, n - first);
         if (hipMemcpyAsync(s->dpos, positions + 3 * first, size_t(m) * 3 * sizeof(double), hipMemcpyHostToDevice, s->stream) != hipSuccess)
             return failSampler(PMC_ERR_DEVICE, "hipMemcpy of the sample positions failed");
         const int blocks = int(std::min<long long>((m + 255) / 256, 256 * 16));
-        if (s->dev.kernel == PMC_KERNEL_CUBIC_SPLINE)
+        if (s->mesh)
+            hipLaunchKernelGGL(sampleMeshDensityKernel, dim3(blocks), dim3(256), 0, s->stream, s->devMesh, s->dpos, m, (long long)first, s->dout,
+                               s->dfailed);
+        else if (s->dev.kernel == PMC_KERNEL_CUBIC_SPLINE)
             hipLaunchKernelGGL(sampleDensityKernel<PMC_KERNEL_CUBIC_SPLINE>, dim3(blocks), dim3(256), lds, s->stream, s->dev, s->dpos, m, s->dout);
         else
             hipLaunchKernelGGL(sampleDensityKernel<PMC_KERNEL_UNIFORM>, dim3(blocks), dim3(256), lds, s->stream, s->dev, s->dpos, m, s->dout);
@@ -187,6 +303,77 @@ int pmc_sampler_density(pmc_sampler* s, const double* positions, int64_t n, doub
             || hipStreamSynchronize(s->stream) != hipSuccess)
             return failSampler(PMC_ERR_DEVICE, "density sampling kernel failed");
     }
+    if (s->mesh)
+    {
+        if (hipMemcpyAsync(&failed, s->dfailed, sizeof(failed), hipMemcpyDeviceToHost, s->stream) != hipSuccess
+            || hipStreamSynchronize(s->stream) != hipSuccess)
+            return failSampler(PMC_ERR_DEVICE, "density sampling kernel failed");
+        // AdaptiveMeshSnapshot.cpp:133
+        if (failed != none) return failSampler(PMC_ERR_DEVICE, "Can't locate the appropriate child node (position " + std::to_string(failed) + ")");
+    }
+    return PMC_OK;
+}
+
+int pmc_sampler_create_mesh(const pmc_adaptive_mesh* M, int32_t device, pmc_sampler** out)
+{
+    if (!M || !out) return failSampler(PMC_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (M->num_nodes < 1 || M->num_cells < 1 || !M->node_box || !M->node_dims || !M->node_link || !M->cell_density)
+        return failSampler(PMC_ERR_INVALID, "adaptive mesh tables are missing");
+    // ---- the table, before any device call: every index the kernel forms from it stays inside it; the depth of the tree in the same pass
+    // (a child id is above its parent's, so the depth of a node is final when the pass reaches it)
+    const int64_t numNodes = M->num_nodes;
+    std::vector<MeshNode> nodes(static_cast<size_t>(numNodes));
+    std::vector<int32_t> depth(static_cast<size_t>(numNodes), 0);
+    int32_t maxDepth = 0;
+    for (int64_t id = 0; id != numNodes; ++id)
+    {
+        const int32_t* dims = M->node_dims + 3 * id;
+        const int32_t link = M->node_link[id];
+        const std::string where = " (node " + std::to_string(id) + ")";
+        if (dims[0] == 0 && dims[1] == 0 && dims[2] == 0)
+        {
+            if (link < 0 || link >= M->num_cells) return failSampler(PMC_ERR_INVALID, "adaptive mesh: leaf link outside the cells" + where);
+        }
+        else
+        {
+            if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return failSampler(PMC_ERR_INVALID, "adaptive mesh: dimension below 1" + where);
+            const int64_t plane = int64_t(dims[0]) * dims[1];
+            if (plane > INT32_MAX || plane * dims[2] > INT32_MAX)
+                return failSampler(PMC_ERR_INVALID, "adaptive mesh: product of the dimensions overflows" + where);
+            const int64_t count = plane * dims[2];
+            if (link <= id) return failSampler(PMC_ERR_INVALID, "adaptive mesh: child id not above its parent's" + where);
+            if (link + count > numNodes) return failSampler(PMC_ERR_INVALID, "adaptive mesh: child range outside the table" + where);
+            const int32_t below = depth[size_t(id)] + 1;
+            for (int64_t c = link; c != link + count; ++c) depth[size_t(c)] = std::max(depth[size_t(c)], below);
+            maxDepth = std::max(maxDepth, below);
+        }
+        const double* box = M->node_box + 6 * id;
+        MeshNode& node = nodes[size_t(id)];
+        node.xmin = box[0], node.ymin = box[1], node.zmin = box[2], node.xmax = box[3], node.ymax = box[4], node.zmax = box[5];
+        node.nx = dims[0], node.ny = dims[1], node.nz = dims[2], node.link = link;
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1)
+        return failSampler(PMC_ERR_DEVICE, "no HIP device available: the device sampler cannot run");
+    if (device < 0 || device >= count) return failSampler(PMC_ERR_INVALID, "invalid device index");
+    if (hipSetDevice(device) != hipSuccess) return failSampler(PMC_ERR_DEVICE, "hipSetDevice failed");
+    pmc_sampler* s = new pmc_sampler();
+    s->device = device;
+    s->mesh = true;
+    s->devMesh.depth = maxDepth;
+    // (hipMalloc returns memory aligned to more than the 64 bytes of a record)
+    bool ok = uploadTo(s, nodes.data(), nodes.size(), &s->devMesh.node) && uploadTo(s, M->cell_density, size_t(M->num_cells), &s->devMesh.cell_density);
+    s->batch = 1 << 22;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&s->dpos), size_t(s->batch) * 3 * sizeof(double)) == hipSuccess
+         && hipMalloc(reinterpret_cast<void**>(&s->dout), size_t(s->batch) * sizeof(double)) == hipSuccess
+         && hipMalloc(reinterpret_cast<void**>(&s->dfailed), sizeof(unsigned long long)) == hipSuccess && hipStreamCreate(&s->stream) == hipSuccess;
+    if (!ok)
+    {
+        pmc_sampler_destroy(s);
+        return failSampler(PMC_ERR_NOMEM, "device allocation for the mesh sampler failed");
+    }
+    *out = s;
     return PMC_OK;
 }
 
@@ -198,6 +385,7 @@ void pmc_sampler_destroy(pmc_sampler* s)
     for (void* p : s->allocations) hipFree(p);
     if (s->dpos) hipFree(s->dpos);
     if (s->dout) hipFree(s->dout);
+    if (s->dfailed) hipFree(s->dfailed);
     delete s;
 }
 }

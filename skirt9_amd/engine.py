@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .host import CounterValues, DustHeating, FrameLayout, SceneExt, SceneHead, heating_struct
+from .host import AdaptiveMesh, CounterValues, DustHeating, FrameLayout, SceneExt, SceneHead, heating_struct, mesh_struct
 
 _LIBDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 
@@ -22,7 +22,7 @@ SYMBOLS = ["pmc_abi_version", "pmc_build_info", "pmc_last_error", "pmc_frame_lay
            "pmc_last_temperature_ms", "pmc_set_launch",
            "pmc_set_num_slots", "pmc_last_timing", "pmc_last_walk_timing", "pmc_walk_work", "pmc_radiation_field_size", "pmc_radiation_field_device",
            "pmc_download_radiation_field", "pmc_clear_radiation_field", "pmc_bind_radiation_field", "pmc_sampler_create",
-           "pmc_sampler_density", "pmc_sampler_destroy", "pmc_history_range", "pmc_comm_init_all", "pmc_comm_unique_id",
+           "pmc_sampler_density", "pmc_sampler_destroy", "pmc_sampler_create_mesh", "pmc_history_range", "pmc_comm_init_all", "pmc_comm_unique_id",
            "pmc_comm_init_rank", "pmc_comm_size", "pmc_comm_destroy", "pmc_reduce_frames", "pmc_allreduce_radiation_field",
            "pmc_debug_tables", "pmc_tuning_set", "pmc_tuning_clear", "pmc_tune_dipole_cosines", "pmc_tune_source_velocities",
            "pmc_launch_flavour", "pmc_tune_log_geometry", "pmc_tune_log_partition", "pmc_tune_rf_log_flush", "pmc_tune_stat_log_flush",
@@ -144,6 +144,11 @@ def lib():
         L.pmc_comm_destroy.argtypes = [C.c_void_p]
         L.pmc_reduce_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.pmc_allreduce_radiation_field.argtypes = [C.c_void_p, C.c_void_p]
+        L.pmc_sampler_density.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.pmc_sampler_destroy.restype = None
+        L.pmc_sampler_destroy.argtypes = [C.c_void_p]
+        if hasattr(L, "pmc_sampler_create_mesh"):  # (absent from engines built from an older commit and loaded through PMC_LIBRARY)
+            L.pmc_sampler_create_mesh.argtypes = [C.POINTER(AdaptiveMesh), C.c_int32, C.POINTER(C.c_void_p)]
         if hasattr(L, "pmc_tuning_set"):
             L.pmc_tuning_set.argtypes = [C.c_char_p, C.c_char_p]
             L.pmc_tuning_clear.restype = None
@@ -263,6 +268,37 @@ class Communicator:
         for h in self.handles:
             lib().pmc_comm_destroy(h)
         self.handles = []
+
+
+class MeshSampler:
+    """The density of a medium imported from an adaptive mesh at many positions, on one MI355X (pmc_sampler_create_mesh,
+    pmc_sampler_density): ``tables`` as ``skirt9_amd.host.Simulation.adaptive_mesh`` returns them.  A malformed table is refused before any
+    device call; there is no CPU fallback."""
+
+    def __init__(self, tables, device=0):
+        struct, keep = mesh_struct(tables)
+        self._h = C.c_void_p()
+        _check(lib().pmc_sampler_create_mesh(C.byref(struct), device, C.byref(self._h)))
+        del keep  # (the tables are copied to the device)
+
+    def density(self, positions):
+        """the density at the positions [n][3]: 0 outside the root box; RuntimeError with the reference's words and the lowest failing index
+        for a position that the reference's descent cannot locate"""
+        r = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        out = np.empty(r.shape[0], dtype=np.float64)
+        _check(lib().pmc_sampler_density(self._h, _ptr(r), r.shape[0], _ptr(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            lib().pmc_sampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Engine:

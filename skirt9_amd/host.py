@@ -113,6 +113,33 @@ class DustHeating(C.Structure):
                 ("temperature", C.POINTER(C.c_double)), ("cell_factor", C.POINTER(C.c_double)), ("mass_density", C.POINTER(C.c_double))]
 
 
+class AdaptiveMesh(C.Structure):
+    """pmc_adaptive_mesh (include/pmc.h)"""
+    _fields_ = [("num_nodes", C.c_int32), ("num_cells", C.c_int32), ("node_box", C.POINTER(C.c_double)), ("node_dims", C.POINTER(C.c_int32)),
+                ("node_link", C.POINTER(C.c_int32)), ("cell_density", C.POINTER(C.c_double))]
+
+
+MESH_ARRAYS = ("node_box", "node_dims", "node_link", "cell_density")
+
+
+def mesh_struct(tables):
+    """the pmc_adaptive_mesh of a dict as ``Simulation.adaptive_mesh`` returns it (sizes from the shapes of the arrays); returns
+    (struct, arrays): the struct points into the arrays, which the caller keeps alive while it is in use"""
+    import numpy as np
+    arrays = {"node_box": np.ascontiguousarray(tables["node_box"], dtype=np.float64).reshape(-1, 6),
+              "node_dims": np.ascontiguousarray(tables["node_dims"], dtype=np.int32).reshape(-1, 3),
+              "node_link": np.ascontiguousarray(tables["node_link"], dtype=np.int32).reshape(-1),
+              "cell_density": np.ascontiguousarray(tables["cell_density"], dtype=np.float64).reshape(-1)}
+    n = arrays["node_link"].shape[0]
+    if arrays["node_box"].shape[0] != n or arrays["node_dims"].shape[0] != n:
+        raise ValueError("node_box, node_dims and node_link must describe the same nodes")
+    struct = AdaptiveMesh(n, arrays["cell_density"].shape[0])
+    for name in MESH_ARRAYS:
+        ctype = C.c_double if arrays[name].dtype == np.float64 else C.c_int32
+        setattr(struct, name, arrays[name].ctypes.data_as(C.POINTER(ctype)))
+    return struct, arrays
+
+
 class ProbeEngine(C.Structure):
     """skh_probe_engine (include/skirt_host.h)"""
     _fields_ = [("integrate", C.c_void_p), ("integrate_weighted", C.c_void_p), ("temperatures", C.c_void_p), ("user", C.c_void_p),
@@ -200,6 +227,10 @@ def lib():
         L.skh_write.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
         L.skh_summary.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
         L.skh_set_particle_sampler.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.skh_set_mesh_sampler.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.skh_adaptive_mesh.argtypes = [C.c_void_p, C.c_int32, C.POINTER(AdaptiveMesh)]
+        L.skh_imported_mass.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
+        L.skh_imported_densities.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
         L.skh_radiation_field_size.restype = C.c_int64
         L.skh_radiation_field_size.argtypes = [C.c_void_p]
         L.skh_write_radiation_field.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
@@ -256,13 +287,16 @@ class Simulation:
         self._setup = False
 
     def use_device_sampler(self, device=0):
-        """before setup(): evaluate the densities of an imported particle medium on the MI355X (libpmc.so
-        pmc_sampler_*): bit-identical to the host evaluation, and the setup of 10^6 particles takes seconds"""
+        """before setup(): evaluate the densities of an imported medium -- smoothed particles or the cells of an adaptive mesh -- on the
+        MI355X (libpmc.so pmc_sampler_*): bit-identical to the host evaluation, and the setup of 10^6 particles takes seconds"""
         from . import engine
         E = engine.lib()
         ptr = lambda f: C.cast(f, C.c_void_p)  # noqa: E731
         if lib().skh_set_particle_sampler(self._h, ptr(E.pmc_sampler_create), ptr(E.pmc_sampler_density),
                                           ptr(E.pmc_sampler_destroy), ptr(E.pmc_last_error), device) != 0:
+            raise RuntimeError(lib().skh_last_error().decode())
+        if lib().skh_set_mesh_sampler(self._h, ptr(E.pmc_sampler_create_mesh), ptr(E.pmc_sampler_density),
+                                      ptr(E.pmc_sampler_destroy), ptr(E.pmc_last_error), device) != 0:
             raise RuntimeError(lib().skh_last_error().decode())
         return self
 
@@ -378,6 +412,40 @@ class Simulation:
         r = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
         out = np.full(r.shape[0], -2, dtype=np.int32)
         if lib().skh_cell_indices(self._h, r.shape[0], r.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError(lib().skh_last_error().decode())
+        return out
+
+    def adaptive_mesh(self, component=0):
+        """the tree and the cell densities of an AdaptiveMeshMedium component (skh_adaptive_mesh) as a dict of numpy arrays (copies):
+        node_box [nodes][6], node_dims [nodes][3] (0, 0, 0: leaf), node_link [nodes] (id of child 0, or the cell index of a leaf),
+        cell_density [cells]; node 0 is the root, parents come before their children, the children of a node are consecutive"""
+        import numpy as np
+        assert self._setup, "call setup() first"
+        mesh = AdaptiveMesh()
+        if lib().skh_adaptive_mesh(self._h, component, C.byref(mesh)) != 0:
+            raise RuntimeError(lib().skh_last_error().decode())
+        n = mesh.num_nodes
+        return {"node_box": np.ctypeslib.as_array(mesh.node_box, shape=(n, 6)).copy(),
+                "node_dims": np.ctypeslib.as_array(mesh.node_dims, shape=(n, 3)).copy(),
+                "node_link": np.ctypeslib.as_array(mesh.node_link, shape=(n,)).copy(),
+                "cell_density": np.ctypeslib.as_array(mesh.cell_density, shape=(mesh.num_cells,)).copy()}
+
+    def imported_mass(self, component=0):
+        """Snapshot::mass() of an imported medium component (skh_imported_mass): its total effective mass, or number of entities"""
+        assert self._setup, "call setup() first"
+        out = C.c_double(0.)
+        if lib().skh_imported_mass(self._h, component, C.byref(out)) != 0:
+            raise RuntimeError(lib().skh_last_error().decode())
+        return float(out.value)
+
+    def imported_densities(self, component, positions):
+        """Snapshot::density of an imported medium component at the positions [n][3] (skh_imported_densities): the mass or number density as
+        the file implies; on the device when ``use_device_sampler`` was called before setup(), else on the host cores"""
+        import numpy as np
+        assert self._setup, "call setup() first"
+        r = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
+        out = np.empty(r.shape[0], dtype=np.float64)
+        if lib().skh_imported_densities(self._h, component, r.shape[0], r.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0:
             raise RuntimeError(lib().skh_last_error().decode())
         return out
 

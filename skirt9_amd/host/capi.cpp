@@ -3,6 +3,7 @@
 
 #include "../../include/skirt_host.h"
 #include "simulation.hpp"
+#include <algorithm>
 #include <cstring>
 #include <fstream>
 #include <type_traits>
@@ -107,6 +108,48 @@ int skh_set_particle_sampler(skh_simulation* h, void* create, void* density, voi
         api.lastError = reinterpret_cast<const char* (*)()>(last_error);
         api.device = device;
         h->sim->setParticleSampler(api);
+    });
+}
+
+// The same for a medium imported from an adaptive mesh: pmc_sampler_create_mesh in the place of pmc_sampler_create.
+int skh_set_mesh_sampler(skh_simulation* h, void* create_mesh, void* density, void* destroy, void* last_error, int32_t device)
+{
+    return guarded(loaded(h) && create_mesh && density && destroy, [&] {
+        skh::MeshSamplerApi api;
+        api.create = reinterpret_cast<int (*)(const pmc_adaptive_mesh*, int32_t, pmc_sampler**)>(create_mesh);
+        api.density = reinterpret_cast<int (*)(pmc_sampler*, const double*, int64_t, double*)>(density);
+        api.destroy = reinterpret_cast<void (*)(pmc_sampler*)>(destroy);
+        api.lastError = reinterpret_cast<const char* (*)()>(last_error);
+        api.device = device;
+        h->sim->setMeshSampler(api);
+    });
+}
+
+int skh_adaptive_mesh(const skh_simulation* h, int32_t component, pmc_adaptive_mesh* out)
+{
+    return guarded(loaded(h) && out, [&] {
+        const skh::ImportedMedium& medium = h->sim->importedMedium(component);
+        const skh::AdaptiveMeshMedium* mesh = dynamic_cast<const skh::AdaptiveMeshMedium*>(&medium);
+        if (!mesh) throw std::runtime_error("medium component " + std::to_string(component) + " is a " + medium.type() + ", not an AdaptiveMeshMedium");
+        if (!mesh->snapshot.numNodes()) throw std::runtime_error("the simulation has not been set up");
+        *out = mesh->snapshot.tables();
+    });
+}
+
+int skh_imported_mass(const skh_simulation* h, int32_t component, double* out)
+{
+    return guarded(loaded(h) && out, [&] { *out = h->sim->importedMedium(component).imported().mass(); });
+}
+
+int skh_imported_densities(const skh_simulation* h, int32_t component, int64_t n, const double* positions, double* out)
+{
+    return guarded(loaded(h) && n >= 0 && (n == 0 || (positions && out)), [&] {
+        const skh::ImportedMedium& medium = h->sim->importedMedium(component);
+        std::vector<skh::Vec3> r(static_cast<size_t>(n));
+        for (int64_t p = 0; p < n; ++p) r[p] = skh::Vec3{positions[3 * p], positions[3 * p + 1], positions[3 * p + 2]};
+        std::vector<double> density;
+        medium.imported().densities(r, density);
+        std::copy(density.begin(), density.end(), out);
     });
 }
 

@@ -4,7 +4,7 @@
 //        -g 0,1,2,3   the devices that share the segment: one host thread per device, the histories split statically by
 //                     index (pmc_history_range), ONE RCCL reduce of the detector arrays onto the first device at the end
 //                     of the segment (ProcessManager::sumToRoot, FluxRecorder.cpp:487-493), which writes the output
-//        -s           particle-medium densities sampled on the GPU during setup
+//        -s           densities of an imported medium (smoothed particles, adaptive mesh) sampled on the GPU during setup
 //        --rccl       run the collective also with a single device (a one-rank communicator: checks the call path)
 //
 // Counterpart of SKIRT/main (SkirtCommandLineHandler.cpp:295-372 doSimulation): construct the simulation from the
@@ -38,7 +38,7 @@ int main(int argc, char** argv)
     {
         if (!strcmp(argv[i], "-s"))
         {
-            deviceSetup = true;  // sample the densities of an imported particle medium on the GPU during setup
+            deviceSetup = true;  // sample the densities of an imported medium on the GPU during setup
             continue;
         }
         else if (!strcmp(argv[i], "-o") && i + 1 < argc)
@@ -89,9 +89,12 @@ int main(int argc, char** argv)
     }
     if (packets) skh_set_num_packets(sim, packets);
     if (deviceSetup
-        && skh_set_particle_sampler(sim, reinterpret_cast<void*>(&pmc_sampler_create), reinterpret_cast<void*>(&pmc_sampler_density),
+        && (skh_set_particle_sampler(sim, reinterpret_cast<void*>(&pmc_sampler_create), reinterpret_cast<void*>(&pmc_sampler_density),
+                                     reinterpret_cast<void*>(&pmc_sampler_destroy), reinterpret_cast<void*>(&pmc_last_error), device)
+                != 0
+            || skh_set_mesh_sampler(sim, reinterpret_cast<void*>(&pmc_sampler_create_mesh), reinterpret_cast<void*>(&pmc_sampler_density),
                                     reinterpret_cast<void*>(&pmc_sampler_destroy), reinterpret_cast<void*>(&pmc_last_error), device)
-               != 0)
+                   != 0))
     {
         fprintf(stderr, "Fatal error: %s\n", skh_last_error());
         return 1;

@@ -1082,13 +1082,13 @@ namespace skh
         {
             // VoronoiMeshSpatialGrid.cpp:127-132: the positions of the entities of the first imported medium component
             // (MediumSystem::interface<SiteListInterface>; ImportedMedium.cpp:268-278), in file order
-            const ParticleMedium* imported = dynamic_cast<const ParticleMedium*>(&medium);
+            const ImportedMedium* imported = dynamic_cast<const ImportedMedium*>(&medium);
             if (!imported)
                 if (const CompositeMedium* all = dynamic_cast<const CompositeMedium*>(&medium))
                     for (const Medium* part : all->parts)
-                        if (!imported) imported = dynamic_cast<const ParticleMedium*>(part);
+                        if (!imported) imported = dynamic_cast<const ImportedMedium*>(part);
             if (!imported) throw std::runtime_error("VoronoiMeshSpatialGrid policy ImportedSites: no medium component offers a list of sites (an imported medium)");
-            sites = imported->snapshot.sitePositions();
+            sites = imported->sitePositions();
         }
         else
         {

@@ -7,6 +7,7 @@
 #define SKH_MODEL_HPP
 
 #include "../../include/pmc.h"
+#include "adaptive_mesh.hpp"
 #include "mathutil.hpp"
 #include "particles.hpp"
 #include "units.hpp"
@@ -482,24 +483,23 @@ namespace skh
         }
     };
 
-    // ParticleMedium: a dust medium imported from smoothed particles (SKIRT/core/ParticleMedium.cpp:12-63,
-    // ImportedMedium.cpp:12-55,188-214); see particles.hpp
-    class ParticleMedium : public Medium
+    // ImportedMedium (SKIRT/core/ImportedMedium.cpp:12-55,188-278): what the media read from a snapshot share -- everything but the
+    // snapshot itself (particles.hpp ImportedSnapshot)
+    class ImportedMedium : public Medium
     {
     public:
-        ParticleImportOptions options;
-        std::string kernelType{"CubicSplineSmoothingKernel"};
-        ParticleSnapshot snapshot;
-
-        std::string type() const override { return "ParticleMedium"; }
+        virtual const ImportedSnapshot& imported() const = 0;
         int dimension() const override { return 3; }
+        // the sites of a Voronoi grid with the ImportedSites policy (SiteListInterface, ImportedMedium.cpp:268-278)
+        const std::vector<Vec3>& sitePositions() const { return imported().sitePositions(); }
         // ImportedMedium.cpp:234-257 with Snapshot::SigmaX / Y / Z (Snapshot.cpp:535-590): the mean of 10000 densities along the axis of the
         // snapshot's extent, at the offset 1e-12 diagonals from it, times the length; evaluated as a batch (the device sampler serves it
         // when bound) and added up in the reference's order
         double opticalDepth(int axis, double lambda) const override
         {
+            const ImportedSnapshot& snapshot = imported();
             const int numSamples = 10000;
-            const Box& box = snapshot.search().extent();  // ParticleSnapshot::extent (ParticleSnapshot.cpp:198-204)
+            const Box box = snapshot.extent();
             const double eps = 1e-12 * box.diagonal();
             const double lo = axis == 0 ? box.xmin : axis == 1 ? box.ymin : box.zmin;
             const double hi = axis == 0 ? box.xmax : axis == 1 ? box.ymax : box.zmax;
@@ -517,46 +517,79 @@ namespace skh
             if (!snapshot.holdsNumber()) result /= mix->mass();
             return result;
         }
-        void setup() override { snapshot.load(options, SmoothingKernel::create(kernelType)); }
         double numberDensity(Vec3 r) const override
         {
-            double result = snapshot.density(r);
-            if (!snapshot.holdsNumber()) result /= mix->mass();
+            double result = imported().density(r);
+            if (!imported().holdsNumber()) result /= mix->mass();
             return result;
         }
         double massDensity(Vec3 r) const override
         {
-            double result = snapshot.density(r);
-            if (snapshot.holdsNumber()) result *= mix->mass();
+            double result = imported().density(r);
+            if (imported().holdsNumber()) result *= mix->mass();
             return result;
         }
         double totalMass() const override
         {
-            double result = snapshot.mass();
-            if (snapshot.holdsNumber()) result *= mix->mass();
+            double result = imported().mass();
+            if (imported().holdsNumber()) result *= mix->mass();
             return result;
         }
         double totalNumber() const override
         {
-            double result = snapshot.mass();
-            if (!snapshot.holdsNumber()) result /= mix->mass();
+            double result = imported().mass();
+            if (!imported().holdsNumber()) result /= mix->mass();
             return result;
-        }
-        Vec3 generatePosition(Random&) const override
-        {
-            throw std::runtime_error("random positions from an imported particle medium are not supported on the MI355X path");
         }
         void massDensities(const std::vector<Vec3>& positions, std::vector<double>& out) const override
         {
-            snapshot.densities(positions, out);
-            if (snapshot.holdsNumber())
+            imported().densities(positions, out);
+            if (imported().holdsNumber())
                 for (double& v : out) v *= mix->mass();
         }
         void numberDensities(const std::vector<Vec3>& positions, std::vector<double>& out) const override
         {
-            snapshot.densities(positions, out);
-            if (!snapshot.holdsNumber())
+            imported().densities(positions, out);
+            if (!imported().holdsNumber())
                 for (double& v : out) v /= mix->mass();
+        }
+    };
+
+    // ParticleMedium: a dust medium imported from smoothed particles (SKIRT/core/ParticleMedium.cpp:12-63); see particles.hpp
+    class ParticleMedium : public ImportedMedium
+    {
+    public:
+        ParticleImportOptions options;
+        std::string kernelType{"CubicSplineSmoothingKernel"};
+        ParticleSnapshot snapshot;
+
+        std::string type() const override { return "ParticleMedium"; }
+        const ImportedSnapshot& imported() const override { return snapshot; }
+        void setup() override { snapshot.load(options, SmoothingKernel::create(kernelType)); }
+        Vec3 generatePosition(Random&) const override
+        {
+            throw std::runtime_error("random positions from an imported particle medium are not supported on the MI355X path");
+        }
+    };
+
+    // AdaptiveMeshMedium: a medium imported from the cells of an adaptive mesh (SKIRT/core/AdaptiveMeshMedium.cpp:11-41,
+    // MeshMedium.cpp:11-22); see adaptive_mesh.hpp
+    class AdaptiveMeshMedium : public ImportedMedium
+    {
+    public:
+        MeshImportOptions options;
+        AdaptiveMeshSnapshot snapshot;
+
+        std::string type() const override { return "AdaptiveMeshMedium"; }
+        const ImportedSnapshot& imported() const override { return snapshot; }
+        void setup() override
+        {
+            options.isDust = !mix->isElectrons();
+            snapshot.load(options);
+        }
+        Vec3 generatePosition(Random&) const override
+        {
+            throw std::runtime_error("random positions from an imported adaptive mesh medium are not supported on the MI355X path");
         }
     };
 

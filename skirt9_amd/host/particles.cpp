@@ -220,9 +220,19 @@ namespace skh
         }
     }
 
-    std::vector<Array> readColumnFile(const std::string& path, const std::vector<ColumnSpec>& columns, const std::string& description)
+    struct ColumnTextFile::State
     {
-        std::ifstream in(path);
+        std::ifstream in;
+        std::vector<UnitFactor> conv;
+    };
+
+    ColumnTextFile::~ColumnTextFile() {}
+
+    ColumnTextFile::ColumnTextFile(const std::string& path, const std::vector<ColumnSpec>& columns, const std::string& description)
+        : _state(std::make_unique<State>())
+    {
+        std::ifstream& in = _state->in;
+        in.open(path);
         if (!in) throw std::runtime_error("Could not open the " + description + " text file " + path);
         // ---- header: "# column N: description (unit)" lines (TextInFile.cpp:16-47,87-101); other '#' lines are comments
         struct FileColumn
@@ -253,7 +263,8 @@ namespace skh
         }
         // ---- logical columns in file order (TextInFile::addColumn without column remapping, :214-262)
         const size_t ncol = columns.size();
-        std::vector<UnitFactor> conv(ncol);
+        std::vector<UnitFactor>& conv = _state->conv;
+        conv.resize(ncol);
         for (size_t c = 0; c != ncol; ++c)
         {
             std::string unit = columns[c].defaultUnit;
@@ -286,14 +297,19 @@ namespace skh
                 conv[c] = unitTable().factorOf(columns[c].quantity, unit);
             }
         }
-        // ---- rows (TextInFile::readRow, :286-330): value = factor * value^power
-        std::vector<Array> rows;
+    }
+
+    // TextInFile::readRow (:286-330): value = factor * value^power
+    bool ColumnTextFile::readRow(Array& row)
+    {
+        const std::vector<UnitFactor>& conv = _state->conv;
+        const size_t ncol = conv.size();
         std::string line;
-        while (std::getline(in, line))
+        while (std::getline(_state->in, line))
         {
             auto pos = line.find_first_not_of(" \t\r");
             if (pos == std::string::npos || line[pos] == '#') continue;
-            Array row(ncol);
+            row.assign(ncol, 0.);
             const char* p = line.c_str() + pos;
             for (size_t c = 0; c != ncol; ++c)
             {
@@ -313,8 +329,43 @@ namespace skh
                 value *= conv[c].factor;
                 row[c] = value;
             }
-            rows.push_back(std::move(row));
+            return true;
         }
+        return false;
+    }
+
+    // TextInFile::readNonLeaf (TextInFile.cpp:478-523)
+    bool ColumnTextFile::readNonLeaf(int& nx, int& ny, int& nz)
+    {
+        std::ifstream& in = _state->in;
+        std::string line;
+        while (true)
+        {
+            const int c = in.peek();
+            if (c == '#')
+                std::getline(in, line);
+            else if (c == '!')
+            {
+                in.get();
+                std::getline(in, line);
+                std::stringstream linestream(line);
+                linestream >> nx >> ny >> nz;
+                if (linestream.fail()) throw std::runtime_error("Nonleaf subdivision specifiers are missing or not formatted as integers");
+                return true;
+            }
+            else if (c == ' ' || c == '\t' || c == '\n' || c == '\r')
+                in.get();
+            else
+                return false;
+        }
+    }
+
+    std::vector<Array> readColumnFile(const std::string& path, const std::vector<ColumnSpec>& columns, const std::string& description)
+    {
+        ColumnTextFile file(path, columns, description);
+        std::vector<Array> rows;
+        Array row;
+        while (file.readRow(row)) rows.push_back(row);
         return rows;
     }
 

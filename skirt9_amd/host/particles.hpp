@@ -77,7 +77,23 @@ namespace skh
         int32_t device{0};
     };
 
-    class ParticleSnapshot
+    // what an imported medium asks of its snapshot, whatever the kind of its entities (SKIRT/core/Snapshot.hpp): ImportedMedium in
+    // model.hpp is written against this
+    class ImportedSnapshot
+    {
+    public:
+        virtual ~ImportedSnapshot() {}
+        virtual double density(Vec3 r) const = 0;
+        // the same for many positions: on the MI355X if a device sampler has been set, otherwise on the host cores
+        virtual void densities(const std::vector<Vec3>& positions, std::vector<double>& out) const = 0;
+        virtual double mass() const = 0;
+        virtual bool holdsNumber() const = 0;
+        virtual Box extent() const = 0;  // Snapshot::extent()
+        // the positions of ALL imported entities in file order (SiteListInterface of ImportedMedium, ImportedMedium.cpp:268-278)
+        virtual const std::vector<Vec3>& sitePositions() const = 0;
+    };
+
+    class ParticleSnapshot : public ImportedSnapshot
     {
     public:
         ~ParticleSnapshot();
@@ -88,20 +104,21 @@ namespace skh
         };
         // reads the file and builds the search grid; throws std::runtime_error on malformed input
         void load(const ParticleImportOptions& options, std::unique_ptr<SmoothingKernel> kernel);
-        double density(Vec3 r) const;  // ParticleSnapshot.cpp:233-243
+        double density(Vec3 r) const override;  // ParticleSnapshot.cpp:233-243
         // the same for many positions: on the MI355X if a device sampler has been set (bit-identical results for the
         // cubic-spline and uniform kernels), otherwise on the host cores
-        void densities(const std::vector<Vec3>& positions, std::vector<double>& out) const;
+        void densities(const std::vector<Vec3>& positions, std::vector<double>& out) const override;
         void useDeviceSampler(const ParticleSamplerApi& api) { _api = api; }
         bool onDevice() const { return _sampler != nullptr; }
-        double mass() const { return _mass; }
-        bool holdsNumber() const { return _holdsNumber; }
+        double mass() const override { return _mass; }
+        bool holdsNumber() const override { return _holdsNumber; }
+        Box extent() const override { return _search.extent(); }  // ParticleSnapshot::extent (ParticleSnapshot.cpp:198-204)
         size_t numParticles() const { return _pv.size(); }
         const BoxSearch& search() const { return _search; }
         const std::vector<Particle>& particles() const { return _pv; }
         // the positions of ALL imported entities in file order, also those that carry no mass (SiteListInterface of ImportedMedium,
         // ImportedMedium.cpp:268-278: the sites of a Voronoi grid with the ImportedSites policy)
-        const std::vector<Vec3>& sitePositions() const { return _sites; }
+        const std::vector<Vec3>& sitePositions() const override { return _sites; }
         const SmoothingKernel& kernel() const { return *_kernel; }
 
     private:
@@ -120,6 +137,19 @@ namespace skh
     struct ColumnSpec
     {
         std::string description, quantity, defaultUnit;
+    };
+    // the open file: the header is read at construction, then the rows one at a time.  An adaptive mesh file mixes data rows with
+    // "! nx ny nz" lines of nonleaf nodes (TextInFile::readNonLeaf, TextInFile.cpp:478-523)
+    class ColumnTextFile
+    {
+    public:
+        ColumnTextFile(const std::string& path, const std::vector<ColumnSpec>& columns, const std::string& description);
+        ~ColumnTextFile();
+        bool readRow(Array& row);                   // the next data row in internal units; false at the end of the file
+        bool readNonLeaf(int& nx, int& ny, int& nz);  // true, and the three numbers, if the next line that holds anything starts with '!'
+    private:
+        struct State;
+        std::unique_ptr<State> _state;
     };
     std::vector<Array> readColumnFile(const std::string& path, const std::vector<ColumnSpec>& columns,
                                       const std::string& description = "smoothed particles");

@@ -155,6 +155,7 @@ namespace skh
                 unsupported("ElectronMix with a source or instrument wavelength below 10 nm (Compton scattering)");
             part->mix->setup(simulation.range.min, simulation.range.max, simulation.wavelengths);
             if (auto pm = dynamic_cast<ParticleMedium*>(part.get())) pm->snapshot.useDeviceSampler(_samplerApi);
+            if (auto am = dynamic_cast<AdaptiveMeshMedium*>(part.get())) am->snapshot.useDeviceSampler(_meshSamplerApi);
             part->setup();
         }
     }

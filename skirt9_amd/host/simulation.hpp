@@ -146,6 +146,16 @@ namespace skh
         // evaluate the densities of an imported particle medium on the GPU during setup (include/pmc.h pmc_sampler_*);
         // ignored for other media
         void setParticleSampler(const ParticleSamplerApi& api) { _samplerApi = api; }
+        // the same for a medium imported from an adaptive mesh (pmc_sampler_create_mesh)
+        void setMeshSampler(const MeshSamplerApi& api) { _meshSamplerApi = api; }
+        // medium component h as an imported medium; throws for a component of another kind
+        const ImportedMedium& importedMedium(int h) const
+        {
+            if (h < 0 || h >= static_cast<int>(_media.size())) throw std::runtime_error("no such medium component");
+            const ImportedMedium* medium = dynamic_cast<const ImportedMedium*>(_media[h].get());
+            if (!medium) throw std::runtime_error("medium component " + std::to_string(h) + " is a " + _media[h]->type() + ", not an imported medium");
+            return *medium;
+        }
         void setTreeTopology(std::vector<char> topology) { _topology = std::move(topology); }
 
     private:
@@ -203,6 +213,7 @@ namespace skh
         std::string _prefix;
         std::string _inputPath{"."};
         ParticleSamplerApi _samplerApi;
+        MeshSamplerApi _meshSamplerApi;
         OutputUnits _units;
         int _seed{0};
         // cosmology (Configuration.cpp:52-55): redshift of the model and the two distances of an observer at that redshift

@@ -424,7 +424,8 @@ namespace skh
                 if (rd.boolean(mm, "includePolarization", false)) unsupported("ElectronMix with includePolarization");
                 if (rd.boolean(mm, "includeThermalDispersion", false) && !rd.oligo)
                     unsupported("ElectronMix with includeThermalDispersion in a panchromatic simulation");
-                if (mediumType != "GeometricMedium") unsupported("ElectronMix in a " + mediumType);
+                // (an ionised gas on an adaptive mesh comes as NumberDensity / Number; for particles it stays out)
+                if (mediumType != "GeometricMedium" && mediumType != "AdaptiveMeshMedium") unsupported("ElectronMix in a " + mediumType);
                 auto electrons = std::make_unique<ElectronMix>();
                 electrons->typeName = mm.name;
                 return electrons;
@@ -500,9 +501,38 @@ namespace skh
             return pm;
         }
 
+        // AdaptiveMeshMedium (AdaptiveMeshMedium.hpp, MeshMedium.hpp, ImportedMedium.hpp): a text column file of the cells of an adaptive mesh
+        std::unique_ptr<Medium> readAdaptiveMeshMedium(const XmlElement& med, const Reader& rd)
+        {
+            auto am = std::make_unique<AdaptiveMeshMedium>();
+            MeshImportOptions& o = am->options;
+            o.path = rd.inputFile(med, "AdaptiveMeshMedium");
+            o.extent = Box(rd.quantity(med, "minX", "length"), rd.quantity(med, "minY", "length"), rd.quantity(med, "minZ", "length"),
+                           rd.quantity(med, "maxX", "length"), rd.quantity(med, "maxY", "length"), rd.quantity(med, "maxZ", "length"));
+            // MeshMedium.cpp:19-21
+            if (o.extent.xmax - o.extent.xmin <= 0) throw std::runtime_error("The extent of the domain should be positive in the X direction");
+            if (o.extent.ymax - o.extent.ymin <= 0) throw std::runtime_error("The extent of the domain should be positive in the Y direction");
+            if (o.extent.zmax - o.extent.zmin <= 0) throw std::runtime_error("The extent of the domain should be positive in the Z direction");
+            // AdaptiveMeshMedium.cpp:21-36
+            std::string massType = med.attr("massType", "MassDensity");
+            requireOneOf(massType, {"MassDensity", "Mass", "MassDensityAndMass", "NumberDensity", "Number", "NumberDensityAndNumber"}, "massType ");
+            o.holdsNumber = massType.compare(0, 6, "Number") == 0;
+            o.hasDensity = massType != "Mass" && massType != "Number";
+            o.hasMass = massType != "MassDensity" && massType != "NumberDensity";
+            o.massFraction = rd.number(med, "massFraction", "1");
+            o.importMetallicity = rd.boolean(med, "importMetallicity", false);
+            o.importTemperature = rd.boolean(med, "importTemperature", false);
+            o.maxTemperature = rd.quantity(med, "maxTemperature", "temperature", "0 K");
+            if (rd.boolean(med, "importVelocity", false) && !rd.oligo) unsupported("an imported medium with a velocity field");
+            if (rd.boolean(med, "importMagneticField", false)) unsupported("an imported medium with a magnetic field");
+            if (rd.boolean(med, "importVariableMixParams", false)) unsupported("an imported medium with a variable material mix");
+            if (!med.attr("useColumns", "").empty()) unsupported("useColumns (column remapping)");
+            return am;
+        }
+
         std::unique_ptr<Medium> readMedium(const XmlElement& med, const Reader& rd)
         {
-            requireOneOf(med.name, {"GeometricMedium", "ParticleMedium"}, "medium ");
+            requireOneOf(med.name, {"GeometricMedium", "ParticleMedium", "AdaptiveMeshMedium"}, "medium ");
             if (med.item("velocityDistribution") && rd.quantity(med, "velocityMagnitude", "velocity", "0") && !rd.oligo)
                 unsupported("a medium with a velocity field");
             if (med.item("magneticFieldDistribution") && rd.quantity(med, "magneticFieldStrength", "magneticfield", "0"))
@@ -510,7 +540,9 @@ namespace skh
             const XmlElement* mm = med.item("materialMix");
             if (!mm) throw std::runtime_error("ski: " + med.name + " lacks a material mix");
             std::unique_ptr<MaterialMix> material = readMaterialMix(*mm, rd, med.name);
-            std::unique_ptr<Medium> medium = med.name == "GeometricMedium" ? readGeometricMedium(med, rd) : readParticleMedium(med, rd);
+            std::unique_ptr<Medium> medium = med.name == "GeometricMedium"  ? readGeometricMedium(med, rd)
+                                             : med.name == "ParticleMedium" ? readParticleMedium(med, rd)
+                                                                            : readAdaptiveMeshMedium(med, rd);
             medium->mix = std::move(material);
             return medium;
         }
