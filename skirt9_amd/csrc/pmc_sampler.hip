@@ -12,11 +12,29 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
 extern "C" const char* pmc_last_error(void);
 void pmcSetError(const std::string& message);  // pmc_api.hip
+
+// The frame of a sampler, whatever the kind of its tables: positions and results cross in batches through two buffers on one stream; the
+// kind (second half of this file) adds its tables to `allocations` and the launch of its kernel.
+struct pmc_sampler
+{
+    int device{0};
+    hipStream_t stream{nullptr};
+    long long batch{0};
+    double* dpos{nullptr};  // [batch][3]
+    double* dout{nullptr};  // [batch]
+    std::vector<void*> allocations;
+    // only for a kind whose kernel can fail at a position: the lowest index of such a position, or all ones, and the sentence to report it with
+    unsigned long long* dfailed{nullptr};
+    const char* failedSentence{nullptr};
+    // the kind's kernel on `stream`, in `blocks` workgroups of 256, for the m positions in dpos of which the first has the index `first`
+    std::function<void(const pmc_sampler&, int blocks, long long m, long long first)> launch;
+};
 
 namespace
 {
@@ -30,7 +48,8 @@ namespace
         const int32_t* block_list;
     };
 
-    // NR::locateClip on a separation array (NR.hpp:152-159)
+    // NR::locateClip on a separation array (NR.hpp:152-159).  (Its own copy: written as pmc_kernels.hip writes its locateClip, on locateBasic,
+    // the compiler emits other bytes for sampleDensityKernel; and this form there changes 34 of that file's kernels.)
     __device__ __forceinline__ int locateClip(const double* xv, int n, double x)
     {
         if (x < xv[0]) return 0;
@@ -198,26 +217,37 @@ namespace
     }
 }
 
-struct pmc_sampler
-{
-    int device{0};
-    bool mesh{false};  // which of the two tables this sampler holds
-    DevParticles dev{};
-    DevMesh devMesh{};
-    unsigned long long* dfailed{nullptr};  // mesh: the lowest index of a position that could not be located, or all ones
-    std::vector<void*> allocations;
-    double* dpos{nullptr};
-    double* dout{nullptr};
-    long long batch{0};
-    hipStream_t stream{nullptr};
-};
-
 namespace
 {
     int failSampler(int code, const std::string& message)
     {
         pmcSetError(message);
         return code;
+    }
+    // the common failure path of the create functions
+    int failAllocation(pmc_sampler* s, const char* kind)
+    {
+        pmc_sampler_destroy(s);
+        return failSampler(PMC_ERR_NOMEM, std::string("device allocation for the ") + kind + " sampler failed");
+    }
+    // the frame on `device`, after the kind's checks of its tables: stream and batch buffers, and the word for failed positions if the kind wants one
+    int openSampler(int32_t device, bool wantsFailWord, const char* kind, pmc_sampler** out)
+    {
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count < 1)
+            return failSampler(PMC_ERR_DEVICE, "no HIP device available: the device sampler cannot run");
+        if (device < 0 || device >= count) return failSampler(PMC_ERR_INVALID, "invalid device index");
+        if (hipSetDevice(device) != hipSuccess) return failSampler(PMC_ERR_DEVICE, "hipSetDevice failed");
+        pmc_sampler* s = new pmc_sampler();
+        s->device = device;
+        s->batch = 1 << 22;
+        const bool ok = hipMalloc(reinterpret_cast<void**>(&s->dpos), size_t(s->batch) * 3 * sizeof(double)) == hipSuccess
+                        && hipMalloc(reinterpret_cast<void**>(&s->dout), size_t(s->batch) * sizeof(double)) == hipSuccess
+                        && (!wantsFailWord || hipMalloc(reinterpret_cast<void**>(&s->dfailed), sizeof(unsigned long long)) == hipSuccess)
+                        && hipStreamCreate(&s->stream) == hipSuccess;
+        if (!ok) return failAllocation(s, kind);
+        *out = s;
+        return PMC_OK;
     }
     template<typename T> bool uploadTo(pmc_sampler* s, const T* host, size_t count, const T** out)
     {
@@ -243,33 +273,27 @@ int pmc_sampler_create(const pmc_particles* P, int32_t device, pmc_sampler** out
         return failSampler(PMC_ERR_INVALID, "particle tables are missing");
     if (3 * size_t(P->num_blocks + 1) * sizeof(double) > 64 * 1024)
         return failSampler(PMC_ERR_UNSUPPORTED, "search grid with more than 2729 blocks per axis");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1)
-        return failSampler(PMC_ERR_DEVICE, "no HIP device available: the device sampler cannot run");
-    if (device < 0 || device >= count) return failSampler(PMC_ERR_INVALID, "invalid device index");
-    if (hipSetDevice(device) != hipSuccess) return failSampler(PMC_ERR_DEVICE, "hipSetDevice failed");
-    pmc_sampler* s = new pmc_sampler();
-    s->device = device;
+    pmc_sampler* s = nullptr;
+    if (const int code = openSampler(device, false, "particle", &s)) return code;
     const size_t nb = size_t(P->num_blocks), nb3 = nb * nb * nb;
     std::vector<double> grid;
     grid.insert(grid.end(), P->xgrid, P->xgrid + nb + 1);
     grid.insert(grid.end(), P->ygrid, P->ygrid + nb + 1);
     grid.insert(grid.end(), P->zgrid, P->zgrid + nb + 1);
     std::vector<long long> starts(P->block_start, P->block_start + nb3 + 1);
-    bool ok = uploadTo(s, P->particle, 5 * size_t(P->num_particles), &s->dev.particle) && uploadTo(s, grid.data(), grid.size(), &s->dev.grid)
-              && uploadTo(s, starts.data(), starts.size(), &s->dev.block_start)
-              && uploadTo(s, P->block_list, size_t(P->block_start[nb3]), &s->dev.block_list);
-    s->dev.kernel = P->kernel;
-    s->dev.nb = P->num_blocks;
-    s->batch = 1 << 22;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&s->dpos), size_t(s->batch) * 3 * sizeof(double)) == hipSuccess
-         && hipMalloc(reinterpret_cast<void**>(&s->dout), size_t(s->batch) * sizeof(double)) == hipSuccess
-         && hipStreamCreate(&s->stream) == hipSuccess;
-    if (!ok)
-    {
-        pmc_sampler_destroy(s);
-        return failSampler(PMC_ERR_NOMEM, "device allocation for the particle sampler failed");
-    }
+    DevParticles dev{};
+    dev.kernel = P->kernel;
+    dev.nb = P->num_blocks;
+    if (!(uploadTo(s, P->particle, 5 * size_t(P->num_particles), &dev.particle) && uploadTo(s, grid.data(), grid.size(), &dev.grid)
+          && uploadTo(s, starts.data(), starts.size(), &dev.block_start) && uploadTo(s, P->block_list, size_t(P->block_start[nb3]), &dev.block_list)))
+        return failAllocation(s, "particle");
+    const size_t lds = grid.size() * sizeof(double);
+    s->launch = [dev, lds](const pmc_sampler& f, int blocks, long long m, long long) {
+        if (dev.kernel == PMC_KERNEL_CUBIC_SPLINE)
+            hipLaunchKernelGGL(sampleDensityKernel<PMC_KERNEL_CUBIC_SPLINE>, dim3(blocks), dim3(256), lds, f.stream, dev, f.dpos, m, f.dout);
+        else
+            hipLaunchKernelGGL(sampleDensityKernel<PMC_KERNEL_UNIFORM>, dim3(blocks), dim3(256), lds, f.stream, dev, f.dpos, m, f.dout);
+    };
     *out = s;
     return PMC_OK;
 }
@@ -280,10 +304,9 @@ int pmc_sampler_density(pmc_sampler* s, const double* positions, int64_t n, doub
     if (n == 0) return PMC_OK;
     if (!positions || !density) return failSampler(PMC_ERR_INVALID, "null buffer");
     if (hipSetDevice(s->device) != hipSuccess) return failSampler(PMC_ERR_DEVICE, "hipSetDevice failed");
-    const size_t lds = 3 * size_t(s->dev.nb + 1) * sizeof(double);
     const unsigned long long none = ~0ull;
     unsigned long long failed = none;
-    if (s->mesh && hipMemsetAsync(s->dfailed, 0xff, sizeof(failed), s->stream) != hipSuccess)
+    if (s->dfailed && hipMemsetAsync(s->dfailed, 0xff, sizeof(failed), s->stream) != hipSuccess)
         return failSampler(PMC_ERR_DEVICE, "hipMemset of the sampler's error word failed");
     for (int64_t first = 0; first < n; first += s->batch)
     {
@@ -291,25 +314,18 @@ int pmc_sampler_density(pmc_sampler* s, const double* positions, int64_t n, doub
         if (hipMemcpyAsync(s->dpos, positions + 3 * first, size_t(m) * 3 * sizeof(double), hipMemcpyHostToDevice, s->stream) != hipSuccess)
             return failSampler(PMC_ERR_DEVICE, "hipMemcpy of the sample positions failed");
         const int blocks = int(std::min<long long>((m + 255) / 256, 256 * 16));
-        if (s->mesh)
-            hipLaunchKernelGGL(sampleMeshDensityKernel, dim3(blocks), dim3(256), 0, s->stream, s->devMesh, s->dpos, m, (long long)first, s->dout,
-                               s->dfailed);
-        else if (s->dev.kernel == PMC_KERNEL_CUBIC_SPLINE)
-            hipLaunchKernelGGL(sampleDensityKernel<PMC_KERNEL_CUBIC_SPLINE>, dim3(blocks), dim3(256), lds, s->stream, s->dev, s->dpos, m, s->dout);
-        else
-            hipLaunchKernelGGL(sampleDensityKernel<PMC_KERNEL_UNIFORM>, dim3(blocks), dim3(256), lds, s->stream, s->dev, s->dpos, m, s->dout);
+        s->launch(*s, blocks, m, (long long)first);
         if (hipGetLastError() != hipSuccess) return failSampler(PMC_ERR_DEVICE, "launch of the density sampling kernel failed");
         if (hipMemcpyAsync(density + first, s->dout, size_t(m) * sizeof(double), hipMemcpyDeviceToHost, s->stream) != hipSuccess
             || hipStreamSynchronize(s->stream) != hipSuccess)
             return failSampler(PMC_ERR_DEVICE, "density sampling kernel failed");
     }
-    if (s->mesh)
+    if (s->dfailed)
     {
         if (hipMemcpyAsync(&failed, s->dfailed, sizeof(failed), hipMemcpyDeviceToHost, s->stream) != hipSuccess
             || hipStreamSynchronize(s->stream) != hipSuccess)
             return failSampler(PMC_ERR_DEVICE, "density sampling kernel failed");
-        // AdaptiveMeshSnapshot.cpp:133
-        if (failed != none) return failSampler(PMC_ERR_DEVICE, "Can't locate the appropriate child node (position " + std::to_string(failed) + ")");
+        if (failed != none) return failSampler(PMC_ERR_DEVICE, s->failedSentence + (" (position " + std::to_string(failed) + ")"));
     }
     return PMC_OK;
 }
@@ -353,26 +369,17 @@ int pmc_sampler_create_mesh(const pmc_adaptive_mesh* M, int32_t device, pmc_samp
         node.xmin = box[0], node.ymin = box[1], node.zmin = box[2], node.xmax = box[3], node.ymax = box[4], node.zmax = box[5];
         node.nx = dims[0], node.ny = dims[1], node.nz = dims[2], node.link = link;
     }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count < 1)
-        return failSampler(PMC_ERR_DEVICE, "no HIP device available: the device sampler cannot run");
-    if (device < 0 || device >= count) return failSampler(PMC_ERR_INVALID, "invalid device index");
-    if (hipSetDevice(device) != hipSuccess) return failSampler(PMC_ERR_DEVICE, "hipSetDevice failed");
-    pmc_sampler* s = new pmc_sampler();
-    s->device = device;
-    s->mesh = true;
-    s->devMesh.depth = maxDepth;
+    pmc_sampler* s = nullptr;
+    if (const int code = openSampler(device, true, "mesh", &s)) return code;
+    DevMesh dev{};
+    dev.depth = maxDepth;
     // (hipMalloc returns memory aligned to more than the 64 bytes of a record)
-    bool ok = uploadTo(s, nodes.data(), nodes.size(), &s->devMesh.node) && uploadTo(s, M->cell_density, size_t(M->num_cells), &s->devMesh.cell_density);
-    s->batch = 1 << 22;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&s->dpos), size_t(s->batch) * 3 * sizeof(double)) == hipSuccess
-         && hipMalloc(reinterpret_cast<void**>(&s->dout), size_t(s->batch) * sizeof(double)) == hipSuccess
-         && hipMalloc(reinterpret_cast<void**>(&s->dfailed), sizeof(unsigned long long)) == hipSuccess && hipStreamCreate(&s->stream) == hipSuccess;
-    if (!ok)
-    {
-        pmc_sampler_destroy(s);
-        return failSampler(PMC_ERR_NOMEM, "device allocation for the mesh sampler failed");
-    }
+    if (!(uploadTo(s, nodes.data(), nodes.size(), &dev.node) && uploadTo(s, M->cell_density, size_t(M->num_cells), &dev.cell_density)))
+        return failAllocation(s, "mesh");
+    s->failedSentence = "Can't locate the appropriate child node";  // AdaptiveMeshSnapshot.cpp:133
+    s->launch = [dev](const pmc_sampler& f, int blocks, long long m, long long first) {
+        hipLaunchKernelGGL(sampleMeshDensityKernel, dim3(blocks), dim3(256), 0, f.stream, dev, f.dpos, m, first, f.dout, f.dfailed);
+    };
     *out = s;
     return PMC_OK;
 }

@@ -144,6 +144,7 @@ def lib():
         L.pmc_comm_destroy.argtypes = [C.c_void_p]
         L.pmc_reduce_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.pmc_allreduce_radiation_field.argtypes = [C.c_void_p, C.c_void_p]
+        L.pmc_sampler_create.argtypes = [C.POINTER(Particles), C.c_int32, C.POINTER(C.c_void_p)]
         L.pmc_sampler_density.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.pmc_sampler_destroy.restype = None
         L.pmc_sampler_destroy.argtypes = [C.c_void_p]
@@ -270,20 +271,22 @@ class Communicator:
         self.handles = []
 
 
-class MeshSampler:
-    """The density of a medium imported from an adaptive mesh at many positions, on one MI355X (pmc_sampler_create_mesh,
-    pmc_sampler_density): ``tables`` as ``skirt9_amd.host.Simulation.adaptive_mesh`` returns them.  A malformed table is refused before any
-    device call; there is no CPU fallback."""
+class Particles(C.Structure):
+    """pmc_particles (include/pmc.h)"""
+    _fields_ = [("kernel", C.c_int32), ("num_particles", C.c_int64), ("particle", C.POINTER(C.c_double)), ("num_blocks", C.c_int32),
+                ("xgrid", C.POINTER(C.c_double)), ("ygrid", C.POINTER(C.c_double)), ("zgrid", C.POINTER(C.c_double)),
+                ("block_start", C.POINTER(C.c_int64)), ("block_list", C.POINTER(C.c_int32))]
 
-    def __init__(self, tables, device=0):
-        struct, keep = mesh_struct(tables)
-        self._h = C.c_void_p()
-        _check(lib().pmc_sampler_create_mesh(C.byref(struct), device, C.byref(self._h)))
-        del keep  # (the tables are copied to the device)
+
+KERNEL_CUBIC_SPLINE, KERNEL_UNIFORM = 1, 2  # PMC_KERNEL_* (include/pmc.h)
+
+
+class _Sampler:
+    """what the two kinds of density sampler share: pmc_sampler_density and pmc_sampler_destroy serve both"""
+    _h = None
 
     def density(self, positions):
-        """the density at the positions [n][3]: 0 outside the root box; RuntimeError with the reference's words and the lowest failing index
-        for a position that the reference's descent cannot locate"""
+        """the density at the positions [n][3]"""
         r = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1, 3)
         out = np.empty(r.shape[0], dtype=np.float64)
         _check(lib().pmc_sampler_density(self._h, _ptr(r), r.shape[0], _ptr(out)))
@@ -299,6 +302,43 @@ class MeshSampler:
             self.close()
         except Exception:
             pass
+
+
+class MeshSampler(_Sampler):
+    """The density of a medium imported from an adaptive mesh at many positions, on one MI355X (pmc_sampler_create_mesh,
+    pmc_sampler_density): ``tables`` as ``skirt9_amd.host.Simulation.adaptive_mesh`` returns them.  A malformed table is refused before any
+    device call; there is no CPU fallback.  ``density`` is 0 outside the root box; RuntimeError with the reference's words and the lowest
+    failing index for a position that the reference's descent cannot locate."""
+
+    def __init__(self, tables, device=0):
+        struct, keep = mesh_struct(tables)
+        self._h = C.c_void_p()
+        _check(lib().pmc_sampler_create_mesh(C.byref(struct), device, C.byref(self._h)))
+        del keep  # (the tables are copied to the device)
+
+
+class ParticleSampler(_Sampler):
+    """The density of a medium imported from smoothed particles at many positions, on one MI355X (pmc_sampler_create, pmc_sampler_density).
+    ``tables``: a dict with the members of pmc_particles -- kernel (KERNEL_*), particle [n][5], xgrid / ygrid / zgrid [num_blocks + 1],
+    block_start [num_blocks^3 + 1], block_list.  The lists are trusted as they come; there is no CPU fallback."""
+
+    def __init__(self, tables, device=0):
+        keep = {"particle": np.ascontiguousarray(tables["particle"], dtype=np.float64).reshape(-1, 5),
+                "block_start": np.ascontiguousarray(tables["block_start"], dtype=np.int64).reshape(-1),
+                "block_list": np.ascontiguousarray(tables["block_list"], dtype=np.int32).reshape(-1)}
+        for axis in ("xgrid", "ygrid", "zgrid"):
+            keep[axis] = np.ascontiguousarray(tables[axis], dtype=np.float64).reshape(-1)
+        nb = keep["xgrid"].shape[0] - 1
+        if keep["ygrid"].shape[0] != nb + 1 or keep["zgrid"].shape[0] != nb + 1 or keep["block_start"].shape[0] != nb ** 3 + 1:
+            raise ValueError("xgrid, ygrid, zgrid and block_start must describe the same blocks")
+        if keep["block_list"].shape[0] != keep["block_start"][-1]:
+            raise ValueError("block_list must have block_start[-1] entries")
+        struct = Particles(int(tables["kernel"]), keep["particle"].shape[0], num_blocks=nb)
+        for name, array in keep.items():
+            setattr(struct, name, array.ctypes.data_as(dict(Particles._fields_)[name]))
+        self._h = C.c_void_p()
+        _check(lib().pmc_sampler_create(C.byref(struct), device, C.byref(self._h)))
+        del keep  # (the tables are copied to the device)
 
 
 class Engine:

@@ -1,7 +1,6 @@
 // adaptive_mesh.cpp -- see adaptive_mesh.hpp
 #include "adaptive_mesh.hpp"
 #include <algorithm>
-#include <atomic>
 #include <limits>
 #include <stdexcept>
 
@@ -68,38 +67,20 @@ namespace skh
         // column roles in the reference's order: AdaptiveMeshMedium.cpp:21-36 (the density before the mass) then ImportedMedium.cpp:20-22;
         // default units of Snapshot.cpp:143-197
         std::vector<ColumnSpec> cols;
-        int densityIndex = -1, massIndex = -1, metallicityIndex = -1, temperatureIndex = -1;
+        int densityIndex = -1, massIndex = -1;
         if (o.hasDensity)
         {
             densityIndex = static_cast<int>(cols.size());
-            if (o.holdsNumber)
-                cols.push_back({"number density", "numbervolumedensity", "1/cm3"});
-            else
-                cols.push_back({"mass density", "massvolumedensity", "Msun/pc3"});
+            cols.push_back(o.holdsNumber ? ColumnSpec{"number density", "numbervolumedensity", "1/cm3"}
+                                         : ColumnSpec{"mass density", "massvolumedensity", "Msun/pc3"});
         }
         if (o.hasMass)
         {
             massIndex = static_cast<int>(cols.size());
-            if (o.holdsNumber)
-                cols.push_back({"number", "", ""});
-            else
-                cols.push_back({"mass", "mass", "Msun"});
+            cols.push_back(o.holdsNumber ? ColumnSpec{"number", "", ""} : ColumnSpec{"mass", "mass", "Msun"});
         }
         if (densityIndex < 0 && massIndex < 0) throw std::runtime_error("adaptive mesh medium without a density or mass column");
-        if (o.importMetallicity)
-        {
-            metallicityIndex = static_cast<int>(cols.size());
-            cols.push_back({"metallicity", "", ""});
-        }
-        if (o.importTemperature)
-        {
-            temperatureIndex = static_cast<int>(cols.size());
-            cols.push_back({"temperature", "temperature", "K"});
-        }
-        // Snapshot::setMassDensityPolicy as called by ImportedMedium (dust: Tmax and metallicity apply; otherwise not)
-        const double maxTemperature = (o.isDust && o.importTemperature) ? o.maxTemperature : 0.;
-        const bool useMetallicity = o.isDust && o.importMetallicity && metallicityIndex >= 0;
-        const bool useTemperatureCutoff = maxTemperature > 0 && temperatureIndex >= 0;
+        const MassPolicy policy = appendPolicyColumns(o, cols);
 
         // AdaptiveMeshSnapshot::readAndClose (AdaptiveMeshSnapshot.cpp:192-208)
         _box = {o.extent.xmin, o.extent.ymin, o.extent.zmin, o.extent.xmax, o.extent.ymax, o.extent.zmax};
@@ -120,14 +101,14 @@ namespace skh
         for (int node = 0; node != numNodes(); ++node)
             if (_dims[3 * static_cast<size_t>(node)] == 0) volume[_link[node]] = boxOf(node).volume();
         _rho.assign(numCells, 0.);
-        const double maxT = useTemperatureCutoff ? maxTemperature : 0.;
+        const double maxT = policy.maxTemperature;  // (0: no cutoff)
         double totalEffectiveMass = 0.;
         for (size_t m = 0; m != numCells; ++m)
         {
             const Array& prop = properties[m];
             double originalDensity = 0.;
             double originalMass = 0.;
-            if (maxT && prop[temperatureIndex] > maxT)
+            if (maxT && prop[policy.temperatureIndex] > maxT)
             {
                 // (ignored: above the temperature cutoff)
             }
@@ -137,8 +118,8 @@ namespace skh
                 originalDensity = std::max(0., densityIndex >= 0 ? prop[densityIndex] : prop[massIndex] / V);
                 originalMass = std::max(0., massIndex >= 0 ? prop[massIndex] : prop[densityIndex] * V);
             }
-            const double effectiveDensity = originalDensity * (useMetallicity ? prop[metallicityIndex] : 1.) * o.massFraction;
-            const double metallicMass = originalMass * (useMetallicity ? prop[metallicityIndex] : 1.);
+            const double effectiveDensity = originalDensity * (policy.useMetallicity ? prop[policy.metallicityIndex] : 1.) * o.massFraction;
+            const double metallicMass = originalMass * (policy.useMetallicity ? prop[policy.metallicityIndex] : 1.);
             const double effectiveMass = metallicMass * o.massFraction;
             _rho[m] = effectiveDensity;
             totalEffectiveMass += effectiveMass;
@@ -146,17 +127,7 @@ namespace skh
         _mass = totalEffectiveMass;
 
         // ---- optional: the same evaluation on the MI355X (include/pmc.h pmc_sampler_create_mesh)
-        if (_api.create && numCells)
-        {
-            const pmc_adaptive_mesh mesh = tables();
-            if (_api.create(&mesh, _api.device, &_sampler) != 0)
-                throw std::runtime_error(std::string("device density sampler: ") + (_api.lastError ? _api.lastError() : "create failed"));
-        }
-    }
-
-    AdaptiveMeshSnapshot::~AdaptiveMeshSnapshot()
-    {
-        if (_sampler && _api.destroy) _api.destroy(_sampler);
+        if (_sampler.api.createMesh && numCells) _sampler.attach(tables());
     }
 
     pmc_adaptive_mesh AdaptiveMeshSnapshot::tables() const
@@ -215,38 +186,5 @@ namespace skh
     {
         const int m = cellIndex(r);
         return m >= 0 ? _rho[m] : 0;
-    }
-
-    void AdaptiveMeshSnapshot::densities(const std::vector<Vec3>& positions, std::vector<double>& out) const
-    {
-        out.resize(positions.size());
-        if (positions.empty()) return;
-        if (_sampler)
-        {
-            static_assert(sizeof(Vec3) == 3 * sizeof(double), "Vec3 must be three packed doubles");
-            if (_api.density(_sampler, reinterpret_cast<const double*>(positions.data()), static_cast<int64_t>(positions.size()), out.data())
-                != 0)
-                throw std::runtime_error(std::string("device density sampler: ") + (_api.lastError ? _api.lastError() : "failed"));
-            return;
-        }
-        // (an exception must not leave a worker thread: the lowest failing position is reported afterwards, as the device sampler does)
-        const size_t none = std::numeric_limits<size_t>::max();
-        std::atomic<size_t> failed{none};
-        parallelFor(positions.size(), [&](size_t b, size_t e) {
-            for (size_t i = b; i != e; ++i)
-            {
-                try
-                {
-                    out[i] = density(positions[i]);
-                }
-                catch (const std::runtime_error&)
-                {
-                    size_t seen = failed.load();
-                    while (i < seen && !failed.compare_exchange_weak(seen, i)) {}
-                    return;
-                }
-            }
-        });
-        if (failed.load() != none) throw std::runtime_error(std::string(cannotLocate) + " (position " + std::to_string(failed.load()) + ")");
     }
 }

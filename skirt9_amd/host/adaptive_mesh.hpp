@@ -12,51 +12,19 @@
 #ifndef SKH_ADAPTIVE_MESH_HPP
 #define SKH_ADAPTIVE_MESH_HPP
 
-#include "particles.hpp"
+#include "imported.hpp"
 
 namespace skh
 {
-    struct MeshImportOptions
-    {
-        std::string path;  // resolved file path
-        Box extent;        // the configured domain (MeshMedium minX ... maxZ)
-        // massType (AdaptiveMeshMedium.cpp:21-36): which of the density and the mass column the file has -- the density column first -- and
-        // whether they hold numbers of entities
-        bool hasDensity{true}, hasMass{false}, holdsNumber{false};
-        double massFraction{1.};
-        bool importMetallicity{false};
-        bool importTemperature{false};
-        double maxTemperature{0.};
-        bool isDust{true};  // ImportedMedium.cpp:47-57: the temperature cut and the metallicity apply to dust only
-    };
-
-    // entry points of the device sampler (include/pmc.h pmc_sampler_create_mesh, pmc_sampler_density, pmc_sampler_destroy), handed over
-    // at run time as the particle sampler's are
-    struct MeshSamplerApi
-    {
-        int (*create)(const pmc_adaptive_mesh*, int32_t, pmc_sampler**){nullptr};
-        int (*density)(pmc_sampler*, const double*, int64_t, double*){nullptr};
-        void (*destroy)(pmc_sampler*){nullptr};
-        const char* (*lastError)(){nullptr};
-        int32_t device{0};
-    };
-
     class AdaptiveMeshSnapshot : public ImportedSnapshot
     {
     public:
-        ~AdaptiveMeshSnapshot();
         // reads the file and computes the cell densities; throws std::runtime_error on malformed input
         void load(const MeshImportOptions& options);
         double density(Vec3 r) const override;  // AdaptiveMeshSnapshot.cpp:276-280
         int cellIndex(Vec3 r) const;            // AdaptiveMeshSnapshot.cpp:311-315: the leaf that holds r, -1 outside the domain
-        void densities(const std::vector<Vec3>& positions, std::vector<double>& out) const override;
-        void useDeviceSampler(const MeshSamplerApi& api) { _api = api; }
-        bool onDevice() const { return _sampler != nullptr; }
-        double mass() const override { return _mass; }
-        bool holdsNumber() const override { return _holdsNumber; }
         Box extent() const override { return _extent; }
-        // the centres of the leaves in file order (AdaptiveMeshSnapshot.cpp:241-244)
-        const std::vector<Vec3>& sitePositions() const override { return _sites; }
+        // (sitePositions(): the centres of the leaves in file order, AdaptiveMeshSnapshot.cpp:241-244)
         // the tree as arrays, which is what the device gets: node 0 is the root, every parent comes before its children, the children of a
         // node have consecutive ids in the order k, j, i (i fastest)
         int numNodes() const { return static_cast<int>(_link.size()); }
@@ -78,11 +46,6 @@ namespace skh
         std::vector<double> _box;
         std::vector<int32_t> _dims, _link;
         std::vector<double> _rho;
-        std::vector<Vec3> _sites;
-        double _mass{0};
-        bool _holdsNumber{false};
-        MeshSamplerApi _api;
-        pmc_sampler* _sampler{nullptr};
     };
 }
 

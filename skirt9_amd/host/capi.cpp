@@ -68,6 +68,24 @@ namespace
             h->sim->writeProbes(e, outdir, when);
         });
     }
+
+    // the one body of skh_set_particle_sampler and skh_set_mesh_sampler: hands the entry points of the device sampler (include/pmc.h:
+    // pmc_sampler_create or pmc_sampler_create_mesh, and pmc_sampler_density / _destroy, pmc_last_error, which serve both kinds) to the
+    // simulation; the densities of an imported medium of that kind are then evaluated on the GPU during skh_setup
+    template<class Create>
+    int setSampler(skh_simulation* h, Create skh::SamplerApi::*create, void (skh::Simulation::*set)(const skh::SamplerApi&), void* entry,
+                   void* density, void* destroy, void* last_error, int32_t device)
+    {
+        return guarded(loaded(h) && entry && density && destroy, [&] {
+            skh::SamplerApi api;
+            api.*create = reinterpret_cast<Create>(entry);
+            api.density = reinterpret_cast<decltype(api.density)>(density);
+            api.destroy = reinterpret_cast<decltype(api.destroy)>(destroy);
+            api.lastError = reinterpret_cast<decltype(api.lastError)>(last_error);
+            api.device = device;
+            (h->sim.get()->*set)(api);
+        });
+    }
 }
 
 extern "C" {
@@ -96,33 +114,14 @@ int skh_set_num_packets(skh_simulation* h, uint64_t n)
     return 0;
 }
 
-// Hands the entry points of the device sampler (include/pmc.h: pmc_sampler_create / _density / _destroy, pmc_last_error)
-// to the simulation: the densities of an imported particle medium are then evaluated on the GPU during skh_setup.
 int skh_set_particle_sampler(skh_simulation* h, void* create, void* density, void* destroy, void* last_error, int32_t device)
 {
-    return guarded(loaded(h) && create && density && destroy, [&] {
-        skh::ParticleSamplerApi api;
-        api.create = reinterpret_cast<int (*)(const pmc_particles*, int32_t, pmc_sampler**)>(create);
-        api.density = reinterpret_cast<int (*)(pmc_sampler*, const double*, int64_t, double*)>(density);
-        api.destroy = reinterpret_cast<void (*)(pmc_sampler*)>(destroy);
-        api.lastError = reinterpret_cast<const char* (*)()>(last_error);
-        api.device = device;
-        h->sim->setParticleSampler(api);
-    });
+    return setSampler(h, &skh::SamplerApi::createParticles, &skh::Simulation::setParticleSampler, create, density, destroy, last_error, device);
 }
 
-// The same for a medium imported from an adaptive mesh: pmc_sampler_create_mesh in the place of pmc_sampler_create.
 int skh_set_mesh_sampler(skh_simulation* h, void* create_mesh, void* density, void* destroy, void* last_error, int32_t device)
 {
-    return guarded(loaded(h) && create_mesh && density && destroy, [&] {
-        skh::MeshSamplerApi api;
-        api.create = reinterpret_cast<int (*)(const pmc_adaptive_mesh*, int32_t, pmc_sampler**)>(create_mesh);
-        api.density = reinterpret_cast<int (*)(pmc_sampler*, const double*, int64_t, double*)>(density);
-        api.destroy = reinterpret_cast<void (*)(pmc_sampler*)>(destroy);
-        api.lastError = reinterpret_cast<const char* (*)()>(last_error);
-        api.device = device;
-        h->sim->setMeshSampler(api);
-    });
+    return setSampler(h, &skh::SamplerApi::createMesh, &skh::Simulation::setMeshSampler, create_mesh, density, destroy, last_error, device);
 }
 
 int skh_adaptive_mesh(const skh_simulation* h, int32_t component, pmc_adaptive_mesh* out)

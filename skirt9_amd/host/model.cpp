@@ -1,5 +1,6 @@
 // model.cpp -- implementation of the host model layer (see model.hpp).  Citations are to the SKIRT 9 tree.
 
+#include "column_file.hpp"
 #include "model.hpp"
 #include "units.hpp"
 #include <cstring>

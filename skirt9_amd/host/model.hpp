@@ -484,12 +484,17 @@ namespace skh
     };
 
     // ImportedMedium (SKIRT/core/ImportedMedium.cpp:12-55,188-278): what the media read from a snapshot share -- everything but the
-    // snapshot itself (particles.hpp ImportedSnapshot)
+    // snapshot itself (imported.hpp ImportedSnapshot)
     class ImportedMedium : public Medium
     {
     public:
         virtual const ImportedSnapshot& imported() const = 0;
+        ImportedSnapshot& imported() { return const_cast<ImportedSnapshot&>(static_cast<const ImportedMedium*>(this)->imported()); }
         int dimension() const override { return 3; }
+        Vec3 generatePosition(Random&) const override
+        {
+            throw std::runtime_error("random positions from an imported " + _entities + " medium are not supported on the MI355X path");
+        }
         // the sites of a Voronoi grid with the ImportedSites policy (SiteListInterface, ImportedMedium.cpp:268-278)
         const std::vector<Vec3>& sitePositions() const { return imported().sitePositions(); }
         // ImportedMedium.cpp:234-257 with Snapshot::SigmaX / Y / Z (Snapshot.cpp:535-590): the mean of 10000 densities along the axis of the
@@ -513,63 +518,45 @@ namespace skh
             snapshot.densities(positions, density);
             double sum = 0;
             for (int k = 0; k < numSamples; k++) sum += density[k];
-            double result = (sum / numSamples) * (hi - lo) * mix->sectionExt(lambda);
-            if (!snapshot.holdsNumber()) result /= mix->mass();
-            return result;
+            return asNumber((sum / numSamples) * (hi - lo) * mix->sectionExt(lambda));
         }
-        double numberDensity(Vec3 r) const override
-        {
-            double result = imported().density(r);
-            if (!imported().holdsNumber()) result /= mix->mass();
-            return result;
-        }
-        double massDensity(Vec3 r) const override
-        {
-            double result = imported().density(r);
-            if (imported().holdsNumber()) result *= mix->mass();
-            return result;
-        }
-        double totalMass() const override
-        {
-            double result = imported().mass();
-            if (imported().holdsNumber()) result *= mix->mass();
-            return result;
-        }
-        double totalNumber() const override
-        {
-            double result = imported().mass();
-            if (!imported().holdsNumber()) result /= mix->mass();
-            return result;
-        }
+        double numberDensity(Vec3 r) const override { return asNumber(imported().density(r)); }
+        double massDensity(Vec3 r) const override { return asMass(imported().density(r)); }
+        double totalMass() const override { return asMass(imported().mass()); }
+        double totalNumber() const override { return asNumber(imported().mass()); }
         void massDensities(const std::vector<Vec3>& positions, std::vector<double>& out) const override
         {
             imported().densities(positions, out);
-            if (imported().holdsNumber())
-                for (double& v : out) v *= mix->mass();
+            for (double& v : out) v = asMass(v);
         }
         void numberDensities(const std::vector<Vec3>& positions, std::vector<double>& out) const override
         {
             imported().densities(positions, out);
-            if (!imported().holdsNumber())
-                for (double& v : out) v /= mix->mass();
+            for (double& v : out) v = asNumber(v);
         }
+
+    protected:
+        explicit ImportedMedium(const char* entities) : _entities(entities) {}
+
+    private:
+        // what the snapshot holds, a mass or a number of entities, as the other
+        double asNumber(double value) const { return imported().holdsNumber() ? value : value / mix->mass(); }
+        double asMass(double value) const { return imported().holdsNumber() ? value * mix->mass() : value; }
+        std::string _entities;  // what the medium is imported from, in words
     };
 
     // ParticleMedium: a dust medium imported from smoothed particles (SKIRT/core/ParticleMedium.cpp:12-63); see particles.hpp
     class ParticleMedium : public ImportedMedium
     {
     public:
-        ParticleImportOptions options;
+        ParticleMedium() : ImportedMedium("particle") {}
+        ImportOptions options;
         std::string kernelType{"CubicSplineSmoothingKernel"};
         ParticleSnapshot snapshot;
 
         std::string type() const override { return "ParticleMedium"; }
         const ImportedSnapshot& imported() const override { return snapshot; }
         void setup() override { snapshot.load(options, SmoothingKernel::create(kernelType)); }
-        Vec3 generatePosition(Random&) const override
-        {
-            throw std::runtime_error("random positions from an imported particle medium are not supported on the MI355X path");
-        }
     };
 
     // AdaptiveMeshMedium: a medium imported from the cells of an adaptive mesh (SKIRT/core/AdaptiveMeshMedium.cpp:11-41,
@@ -577,6 +564,7 @@ namespace skh
     class AdaptiveMeshMedium : public ImportedMedium
     {
     public:
+        AdaptiveMeshMedium() : ImportedMedium("adaptive mesh") {}
         MeshImportOptions options;
         AdaptiveMeshSnapshot snapshot;
 
@@ -586,10 +574,6 @@ namespace skh
         {
             options.isDust = !mix->isElectrons();
             snapshot.load(options);
-        }
-        Vec3 generatePosition(Random&) const override
-        {
-            throw std::runtime_error("random positions from an imported adaptive mesh medium are not supported on the MI355X path");
         }
     };
 

@@ -1,11 +1,6 @@
 // particles.cpp -- see particles.hpp
 #include "particles.hpp"
-#include "units.hpp"
-#include <cstring>
-#include <fstream>
 #include <limits>
-#include <regex>
-#include <sstream>
 #include <stdexcept>
 
 namespace skh
@@ -191,187 +186,9 @@ namespace skh
         return n;
     }
 
-    // ================================================================ column text file
-
-    namespace
-    {
-        std::string squeezeText(const std::string& text)
-        {
-            std::string out;
-            bool haveSpace = true;
-            for (char c : text)
-            {
-                if (c == ' ' || c == '\t' || c == '\n' || c == '\r')
-                {
-                    if (!haveSpace)
-                    {
-                        out.push_back(' ');
-                        haveSpace = true;
-                    }
-                }
-                else
-                {
-                    out.push_back(c);
-                    haveSpace = false;
-                }
-            }
-            if (haveSpace && !out.empty()) out.pop_back();
-            return out;
-        }
-    }
-
-    struct ColumnTextFile::State
-    {
-        std::ifstream in;
-        std::vector<UnitFactor> conv;
-    };
-
-    ColumnTextFile::~ColumnTextFile() {}
-
-    ColumnTextFile::ColumnTextFile(const std::string& path, const std::vector<ColumnSpec>& columns, const std::string& description)
-        : _state(std::make_unique<State>())
-    {
-        std::ifstream& in = _state->in;
-        in.open(path);
-        if (!in) throw std::runtime_error("Could not open the " + description + " text file " + path);
-        // ---- header: "# column N: description (unit)" lines (TextInFile.cpp:16-47,87-101); other '#' lines are comments
-        struct FileColumn
-        {
-            std::string title, unit;
-        };
-        std::vector<FileColumn> fileCols;
-        static const std::regex syntax("#\\s*column\\s*(\\d*)\\s*:\\s*([^()]*)\\(\\s*([a-zA-Z0-9/]*)\\s*\\)\\s*", std::regex::icase);
-        while (true)
-        {
-            while (true)
-            {
-                int ch = in.peek();
-                if (ch != ' ' && ch != '\t' && ch != '\n' && ch != '\r') break;
-                in.get();
-            }
-            if (in.peek() != '#') break;
-            std::string line;
-            std::getline(in, line);
-            std::smatch matches;
-            if (std::regex_match(line, matches, syntax) && matches.size() == 4)
-            {
-                std::string index = matches[1].str();
-                fileCols.push_back(FileColumn{squeezeText(matches[2].str()), matches[3].str()});
-                if (!index.empty() && std::stoul(index) != fileCols.size())
-                    throw std::runtime_error("Incorrect column index in file header for column " + std::to_string(fileCols.size()));
-            }
-        }
-        // ---- logical columns in file order (TextInFile::addColumn without column remapping, :214-262)
-        const size_t ncol = columns.size();
-        std::vector<UnitFactor>& conv = _state->conv;
-        conv.resize(ncol);
-        for (size_t c = 0; c != ncol; ++c)
-        {
-            std::string unit = columns[c].defaultUnit;
-            if (!fileCols.empty())
-            {
-                if (c + 1 > fileCols.size()) throw std::runtime_error("No column info in file header for column " + std::to_string(c + 1));
-                unit = fileCols[c].unit;
-            }
-            if (columns[c].quantity == "specific")
-            {
-                // an arbitrarily scaled value per unit of wavelength (TextInFile.cpp:232-245): the unit must be one of the
-                // per-wavelength styles, and NO conversion factor is applied (waveExponent 0); the per-frequency, neutral
-                // and per-energy styles would need the wavelength column and are not supported here
-                if (!unitTable().has("wavelengthmonluminosity", unit))
-                    throw std::runtime_error("Invalid or unsupported units (" + unit + ") for specific quantity in column "
-                                             + std::to_string(c + 1) + " (only per-wavelength units are supported)");
-                conv[c] = UnitFactor{1., 1., 0.};
-            }
-            else if (columns[c].quantity.empty())
-            {
-                if (!unit.empty() && unit != "1")
-                    throw std::runtime_error("Invalid units (" + unit + ") for dimensionless quantity in column " + std::to_string(c + 1));
-                conv[c] = UnitFactor{1., 1., 0.};
-            }
-            else
-            {
-                if (!unitTable().has(columns[c].quantity, unit))
-                    throw std::runtime_error("Invalid units (" + unit + ") for quantity '" + columns[c].quantity + "' in column "
-                                             + std::to_string(c + 1));
-                conv[c] = unitTable().factorOf(columns[c].quantity, unit);
-            }
-        }
-    }
-
-    // TextInFile::readRow (:286-330): value = factor * value^power
-    bool ColumnTextFile::readRow(Array& row)
-    {
-        const std::vector<UnitFactor>& conv = _state->conv;
-        const size_t ncol = conv.size();
-        std::string line;
-        while (std::getline(_state->in, line))
-        {
-            auto pos = line.find_first_not_of(" \t\r");
-            if (pos == std::string::npos || line[pos] == '#') continue;
-            row.assign(ncol, 0.);
-            const char* p = line.c_str() + pos;
-            for (size_t c = 0; c != ncol; ++c)
-            {
-                while (*p == ' ' || *p == '\t') ++p;
-                if (!*p || *p == '\r') throw std::runtime_error("One or more required value(s) on text line are missing");
-                char* end = nullptr;
-                double value = strtod(p, &end);
-                if (end == p)
-                {
-                    if (strncasecmp(p, "nan", 3) != 0)
-                        throw std::runtime_error(std::string("Input text is not formatted as a floating point number: ") + p);
-                    value = std::numeric_limits<double>::quiet_NaN();
-                    end = const_cast<char*>(p) + 3;
-                }
-                p = end;
-                if (conv[c].power != 1.) value = pow(value, conv[c].power);
-                value *= conv[c].factor;
-                row[c] = value;
-            }
-            return true;
-        }
-        return false;
-    }
-
-    // TextInFile::readNonLeaf (TextInFile.cpp:478-523)
-    bool ColumnTextFile::readNonLeaf(int& nx, int& ny, int& nz)
-    {
-        std::ifstream& in = _state->in;
-        std::string line;
-        while (true)
-        {
-            const int c = in.peek();
-            if (c == '#')
-                std::getline(in, line);
-            else if (c == '!')
-            {
-                in.get();
-                std::getline(in, line);
-                std::stringstream linestream(line);
-                linestream >> nx >> ny >> nz;
-                if (linestream.fail()) throw std::runtime_error("Nonleaf subdivision specifiers are missing or not formatted as integers");
-                return true;
-            }
-            else if (c == ' ' || c == '\t' || c == '\n' || c == '\r')
-                in.get();
-            else
-                return false;
-        }
-    }
-
-    std::vector<Array> readColumnFile(const std::string& path, const std::vector<ColumnSpec>& columns, const std::string& description)
-    {
-        ColumnTextFile file(path, columns, description);
-        std::vector<Array> rows;
-        Array row;
-        while (file.readRow(row)) rows.push_back(row);
-        return rows;
-    }
-
     // ================================================================ ParticleSnapshot
 
-    void ParticleSnapshot::load(const ParticleImportOptions& o, std::unique_ptr<SmoothingKernel> kernel)
+    void ParticleSnapshot::load(const ImportOptions& o, std::unique_ptr<SmoothingKernel> kernel)
     {
         _kernel = std::move(kernel);
         _holdsNumber = o.holdsNumber;
@@ -379,27 +196,10 @@ namespace skh
         std::vector<ColumnSpec> cols = {{"position x", "length", "pc"}, {"position y", "length", "pc"}, {"position z", "length", "pc"},
                                         {"size h", "length", "pc"}};
         const int massIndex = 4;
-        if (o.holdsNumber)
-            cols.push_back({"number", "", ""});
-        else
-            cols.push_back({"mass", "mass", "Msun"});
-        int metallicityIndex = -1, temperatureIndex = -1;
-        if (o.importMetallicity)
-        {
-            metallicityIndex = static_cast<int>(cols.size());
-            cols.push_back({"metallicity", "", ""});
-        }
-        if (o.importTemperature)
-        {
-            temperatureIndex = static_cast<int>(cols.size());
-            cols.push_back({"temperature", "temperature", "K"});
-        }
-        // Snapshot::setMassDensityPolicy as called by ImportedMedium (dust: Tmax and metallicity apply; otherwise not)
-        const double maxTemperature = (o.isDust && o.importTemperature) ? o.maxTemperature : 0.;
-        const bool useMetallicity = o.isDust && o.importMetallicity && metallicityIndex >= 0;
-        const bool useTemperatureCutoff = maxTemperature > 0 && temperatureIndex >= 0;
+        cols.push_back(o.holdsNumber ? ColumnSpec{"number", "", ""} : ColumnSpec{"mass", "mass", "Msun"});
+        const MassPolicy policy = appendPolicyColumns(o, cols);
 
-        std::vector<Array> rows = readColumnFile(o.path, cols);
+        std::vector<Array> rows = readColumnFile(o.path, cols, "smoothed particles");
         // ParticleSnapshot::readAndClose (ParticleSnapshot.cpp:79-151)
         _pv.clear();
         _pv.reserve(rows.size());
@@ -409,10 +209,10 @@ namespace skh
         for (const Array& prop : rows)
         {
             _sites.push_back(Vec3{prop[0], prop[1], prop[2]});  // (every imported row: ParticleSnapshot::position(m), ParticleSnapshot.cpp:286-289)
-            if (useTemperatureCutoff && prop[temperatureIndex] > maxTemperature) continue;
+            if (policy.maxTemperature && prop[policy.temperatureIndex] > policy.maxTemperature) continue;
             if (prop[massIndex] == 0.) continue;
             double imported = prop[massIndex];
-            double metallic = imported * (useMetallicity ? prop[metallicityIndex] : 1.);
+            double metallic = imported * (policy.useMetallicity ? prop[policy.metallicityIndex] : 1.);
             double effective = metallic * o.massFraction;
             _pv.push_back(Particle{prop[0], prop[1], prop[2], prop[3], effective});
             sumImported += imported;
@@ -434,7 +234,7 @@ namespace skh
             [this](int m, const Box& box) { return sphereReachesBox(box, _pv[m].x, _pv[m].y, _pv[m].z, _pv[m].h); });
 
         // ---- optional: the same evaluation on the MI355X (include/pmc.h pmc_sampler_*)
-        if (_api.create && !_pv.empty())
+        if (_sampler.api.createParticles && !_pv.empty())
         {
             pmc_particles P{};
             if (_kernel->type() == "CubicSplineSmoothingKernel")
@@ -459,31 +259,8 @@ namespace skh
             P.xgrid = _search.xgrid().data(), P.ygrid = _search.ygrid().data(), P.zgrid = _search.zgrid().data();
             P.block_start = start.data();
             P.block_list = list.data();
-            if (_api.create(&P, _api.device, &_sampler) != 0)
-                throw std::runtime_error(std::string("device density sampler: ") + (_api.lastError ? _api.lastError() : "create failed"));
+            _sampler.attach(P);
         }
-    }
-
-    ParticleSnapshot::~ParticleSnapshot()
-    {
-        if (_sampler && _api.destroy) _api.destroy(_sampler);
-    }
-
-    void ParticleSnapshot::densities(const std::vector<Vec3>& positions, std::vector<double>& out) const
-    {
-        out.resize(positions.size());
-        if (positions.empty()) return;
-        if (_sampler)
-        {
-            static_assert(sizeof(Vec3) == 3 * sizeof(double), "Vec3 must be three packed doubles");
-            if (_api.density(_sampler, reinterpret_cast<const double*>(positions.data()), static_cast<int64_t>(positions.size()), out.data())
-                != 0)
-                throw std::runtime_error(std::string("device density sampler: ") + (_api.lastError ? _api.lastError() : "failed"));
-            return;
-        }
-        parallelFor(positions.size(), [&](size_t b, size_t e) {
-            for (size_t i = b; i != e; ++i) out[i] = density(positions[i]);
-        });
     }
 
     double ParticleSnapshot::density(Vec3 r) const

@@ -154,8 +154,7 @@ namespace skh
             if (part->mix->isElectrons() && simulation.range.min < ElectronMix::comptonWavelength)
                 unsupported("ElectronMix with a source or instrument wavelength below 10 nm (Compton scattering)");
             part->mix->setup(simulation.range.min, simulation.range.max, simulation.wavelengths);
-            if (auto pm = dynamic_cast<ParticleMedium*>(part.get())) pm->snapshot.useDeviceSampler(_samplerApi);
-            if (auto am = dynamic_cast<AdaptiveMeshMedium*>(part.get())) am->snapshot.useDeviceSampler(_meshSamplerApi);
+            if (auto imported = dynamic_cast<ImportedMedium*>(part.get())) imported->imported().useDeviceSampler(_samplerApi);
             part->setup();
         }
     }

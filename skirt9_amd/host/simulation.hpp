@@ -143,11 +143,10 @@ namespace skh
 
         // optional overrides applied before setup()
         void setNumPackets(uint64_t n) { _numPackets = n; }
-        // evaluate the densities of an imported particle medium on the GPU during setup (include/pmc.h pmc_sampler_*);
-        // ignored for other media
-        void setParticleSampler(const ParticleSamplerApi& api) { _samplerApi = api; }
-        // the same for a medium imported from an adaptive mesh (pmc_sampler_create_mesh)
-        void setMeshSampler(const MeshSamplerApi& api) { _meshSamplerApi = api; }
+        // evaluate the densities of the imported media on the GPU during setup (include/pmc.h pmc_sampler_*): each call takes the create
+        // function of its kind of medium from `api` and the entry points that the kinds share; ignored for other media
+        void setParticleSampler(const SamplerApi& api) { setSampler(api, api.createParticles, _samplerApi.createMesh); }
+        void setMeshSampler(const SamplerApi& api) { setSampler(api, _samplerApi.createParticles, api.createMesh); }
         // medium component h as an imported medium; throws for a component of another kind
         const ImportedMedium& importedMedium(int h) const
         {
@@ -212,8 +211,11 @@ namespace skh
 
         std::string _prefix;
         std::string _inputPath{"."};
-        ParticleSamplerApi _samplerApi;
-        MeshSamplerApi _meshSamplerApi;
+        void setSampler(const SamplerApi& api, decltype(SamplerApi::createParticles) createParticles, decltype(SamplerApi::createMesh) createMesh)
+        {
+            _samplerApi = api, _samplerApi.createParticles = createParticles, _samplerApi.createMesh = createMesh;
+        }
+        SamplerApi _samplerApi;
         OutputUnits _units;
         int _seed{0};
         // cosmology (Configuration.cpp:52-55): redshift of the model and the two distances of an observer at that redshift

@@ -4,6 +4,7 @@
 // into members, are Simulation's and run in document order.  Within every reader the checks stand in the order in which a ski file with several
 // defects is to name them: moving one changes which refusal such a file gets.
 
+#include "column_file.hpp"
 #include "simulation.hpp"
 #include "units.hpp"
 #include <sstream>
@@ -481,6 +482,19 @@ namespace skh
             return gm;
         }
 
+        // what the imported media share (ImportedMedium.hpp): the mass policy options, and the refusals of what is not imported
+        void readImportOptions(const XmlElement& med, const Reader& rd, ImportOptions& o)
+        {
+            o.massFraction = rd.number(med, "massFraction", "1");
+            o.importMetallicity = rd.boolean(med, "importMetallicity", false);
+            o.importTemperature = rd.boolean(med, "importTemperature", false);
+            o.maxTemperature = rd.quantity(med, "maxTemperature", "temperature", "0 K");
+            if (rd.boolean(med, "importVelocity", false) && !rd.oligo) unsupported("an imported medium with a velocity field");
+            if (rd.boolean(med, "importMagneticField", false)) unsupported("an imported medium with a magnetic field");
+            if (rd.boolean(med, "importVariableMixParams", false)) unsupported("an imported medium with a variable material mix");
+            if (!med.attr("useColumns", "").empty()) unsupported("useColumns (column remapping)");
+        }
+
         // ParticleMedium (ParticleMedium.hpp, ImportedMedium.hpp): a text column file of smoothed particles
         std::unique_ptr<Medium> readParticleMedium(const XmlElement& med, const Reader& rd)
         {
@@ -489,14 +503,7 @@ namespace skh
             std::string massType = med.attr("massType", "Mass");
             requireOneOf(massType, {"Mass", "Number"}, "massType ");
             pm->options.holdsNumber = massType == "Number";
-            pm->options.massFraction = rd.number(med, "massFraction", "1");
-            pm->options.importMetallicity = rd.boolean(med, "importMetallicity", false);
-            pm->options.importTemperature = rd.boolean(med, "importTemperature", false);
-            pm->options.maxTemperature = rd.quantity(med, "maxTemperature", "temperature", "0 K");
-            if (rd.boolean(med, "importVelocity", false) && !rd.oligo) unsupported("an imported medium with a velocity field");
-            if (rd.boolean(med, "importMagneticField", false)) unsupported("an imported medium with a magnetic field");
-            if (rd.boolean(med, "importVariableMixParams", false)) unsupported("an imported medium with a variable material mix");
-            if (!med.attr("useColumns", "").empty()) unsupported("useColumns (column remapping)");
+            readImportOptions(med, rd, pm->options);
             if (const XmlElement* sk = med.item("smoothingKernel")) pm->kernelType = sk->name;
             return pm;
         }
@@ -519,14 +526,7 @@ namespace skh
             o.holdsNumber = massType.compare(0, 6, "Number") == 0;
             o.hasDensity = massType != "Mass" && massType != "Number";
             o.hasMass = massType != "MassDensity" && massType != "NumberDensity";
-            o.massFraction = rd.number(med, "massFraction", "1");
-            o.importMetallicity = rd.boolean(med, "importMetallicity", false);
-            o.importTemperature = rd.boolean(med, "importTemperature", false);
-            o.maxTemperature = rd.quantity(med, "maxTemperature", "temperature", "0 K");
-            if (rd.boolean(med, "importVelocity", false) && !rd.oligo) unsupported("an imported medium with a velocity field");
-            if (rd.boolean(med, "importMagneticField", false)) unsupported("an imported medium with a magnetic field");
-            if (rd.boolean(med, "importVariableMixParams", false)) unsupported("an imported medium with a variable material mix");
-            if (!med.attr("useColumns", "").empty()) unsupported("useColumns (column remapping)");
+            readImportOptions(med, rd, o);
             return am;
         }
 
